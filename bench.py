@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the DwiseNeuro training hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N>1 either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...:
   RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or plainly, in which case bench.py starts that launcher
   itself as a child process before touching the GPU.
@@ -12,8 +12,14 @@ RCCL overlapped with backward), fused AdamW step, EMA update.  Workload = BASELI
 configs/true_batch_001.py single-mouse training (expansion 7, 1 readout of 7863 neurons, dropout 0.4, drop-path
 0.1), bf16 storage, B=32 clips of T=32 frames at 36x64 per GPU (weak scaling).
 
-Rank 0 prints ONE JSON line: metric/value/unit (+ ``roofline`` for the dominant kernel family measured live
-with HIP events on the launch stream, and ``cpu_baseline`` = the CPU oracle timed on a bounded sample).
+Rank 0 prints ONE JSON line: metric/value/unit/ms_per_step (+ ``roofline`` for the dominant kernel family measured live
+with HIP events on the launch stream).  A plain run does only that: set up, warm up, time the --steps steps, print the line.
+``--full`` adds the legs that take runs of their own: ``rooflines`` of every family, the forward+backward-only loop, the
+inference leg, the other configs, and ``cpu_baseline`` = the CPU oracle timed on a bounded sample.
+``--dump-outputs DIR`` writes what the last timed step returned as DIR/<name>.npy (dump_outputs; needs --steps >= 2).  The
+step before it restarts from the state the run started from (restored outside the timed region), so with the same arguments
+the dumped step has the same inputs from run to run and two builds can be compared output for output; what the dump sees is
+listed at dump_outputs.  Time with a plain run: a dump run drains the queue once for the restore.
 """
 from __future__ import annotations
 
@@ -214,6 +220,91 @@ def other_config(extra):
             "loss": d.get("loss"), "dominant_family": r.get("kernel"), "frac": r.get("frac"), "achieved_gbs": r.get("achieved")}
 
 
+DUMP_BUDGET = 60_000_000          # bytes --dump-outputs writes at most (.npy headers included, with room to spare)
+
+
+def snapshot_state(model, dev):
+    """Everything a training step reads besides its batch: weights and BatchNorm buffers, the EMA copies, the RNG states (the
+    Adam moments and step counts start at zero; restore_state resets them)."""
+    net = {k: v.detach().clone() for k, v in model.nn_module.state_dict().items()}
+    ema = None if model.model_ema is None else {k: v.detach().clone() for k, v in model.model_ema.ema.state_dict().items()}
+    return {"net": net, "ema": ema, "rng": torch.get_rng_state(),
+            "rng_dev": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None}
+
+
+@torch.no_grad()
+def restore_state(model, snap, dev):
+    """Put the model back in the state snapshot_state saw, in place (the optimizer's kernel tables keep their pointers)."""
+    model.sync_for_read()                    # sharded optimizer: no all-gather may still be writing the parameters
+    for k, v in model.nn_module.state_dict().items():
+        v.copy_(snap["net"][k])
+    if snap["ema"] is not None:
+        for k, v in model.model_ema.ema.state_dict().items():
+            v.copy_(snap["ema"][k])
+    if model.optimizer is not None:
+        for st in model.optimizer.state.values():
+            st["step"] = 0
+            st["exp_avg"].zero_()
+            st["exp_avg_sq"].zero_()
+    torch.set_rng_state(snap["rng"])
+    if snap["rng_dev"] is not None:
+        torch.cuda.set_rng_state(snap["rng_dev"], dev)
+
+
+def timed_steps(n, step, sync, restore=None):
+    """Run `step` n times and return (the last one's result, seconds spent in the n steps).  `restore` (--dump-outputs) runs
+    before step n-1, the second to last, and is not timed: the queue is drained before it, so that step starts with the host
+    no longer ahead of the device -- time with a plain run, not with a dump run."""
+    t0 = time.perf_counter()
+    last, elapsed = None, 0.0
+    for i in range(n):
+        if restore is not None and i == n - 2:
+            sync()
+            elapsed += time.perf_counter() - t0
+            restore()
+            sync()
+            t0 = time.perf_counter()
+        last = step()
+    sync()
+    return last, elapsed + time.perf_counter() - t0
+
+
+def _flat_sample(t, k, seed):
+    """A fixed, seeded sample of k of t's elements (flattened, in index order), as float32 on the host."""
+    import numpy as np
+    flat = t.detach().reshape(-1)
+    if flat.numel() > k:
+        idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), size=k, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(out_dir, step_out):
+    """--dump-outputs: what the last timed step returned (MouseModel.train_step), as out_dir/<name>.npy.
+      prediction_<m>  the per-readout predictions, float32, full shape;
+      loss            the loss, float64.
+    The step before it started from the run's initial state (timed_steps / restore_state), so these come from the forward of
+    weights that one backward + fused AdamW step moved from a fixed state: the dump sees the forward kernels, the backward
+    kernels and the optimizer.  It does not see the EMA update, the last step's own backward and update, or the steps before
+    the restore (their drift from float atomics is what the restore removes).
+    When the predictions do not fit in DUMP_BUDGET, each is written as prediction_<m>_sample instead: a fixed, seeded sample of
+    its flattened elements, in proportion to its size."""
+    import numpy as np
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {"loss": np.asarray(float(step_out["loss"]), dtype=np.float64)}
+    preds = step_out["prediction"]
+    preds = [preds] if torch.is_tensor(preds) else list(preds)
+    left = DUMP_BUDGET - arrays["loss"].nbytes
+    total = sum(p.numel() * 4 for p in preds)
+    for m, p in enumerate(preds):
+        if total <= left:
+            arrays[f"prediction_{m}"] = p.detach().float().cpu().numpy()
+        else:
+            arrays[f"prediction_{m}_sample"] = _flat_sample(p, max(1, p.numel() * left // total), 1 + m)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def self_launch(n, argv):
     """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
     bench.py <same args>` as a child (never an exec: this may only happen before any GPU call, and the child is a fresh
@@ -297,7 +388,20 @@ def main():
                     "configs/true_batch_001.py:76-79, sparse targets; SURVEY 8f ranks 3-4) from synthetic trials resident in HBM — "
                     "the reference's per-step H2D copy (argus_models.py:49) and DataLoader work, on the device")
     ap.add_argument("--dry-run", action="store_true", help="testing only: launcher + rendezvous + timing plumbing, no GPU work")
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline figure (the untimed per-family "
+                    "rooflines, the forward+backward-only loop, the inference leg, the other configs, the CPU baseline; each "
+                    "still subject to its --no-* switch); without it the run sets up, warms up, times the steps and prints "
+                    "the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one computed "
+                    "to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.steps < 2:
+        ap.error("--dump-outputs needs --steps 2 or more (the last step's inputs come from one step after a restore)")
+    if not args.full:
+        # a plain run: only what the headline figure needs
+        args.no_rooflines = args.no_fwd_bwd = args.no_inference = args.no_other_configs = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves, as a CHILD process and before anything in this
@@ -398,6 +502,10 @@ def main():
         cstream = torch.cuda.Stream(device=dev)
         cstream.wait_stream(torch.cuda.current_stream(dev))
         torch.cuda.set_stream(cstream)
+    # --dump-outputs: the second-to-last timed step starts again from the state the run started from, restored outside the
+    # timed region, so that the dumped last step has the same inputs in every run (the library's float atomics add in arrival
+    # order; over many AdamW steps those rounding differences grow into a different trained state)
+    start_state = snapshot_state(model, dev) if args.dump_outputs else None
     for _ in range(args.warmup):
         model.train_step(next_batch(), sync_loss=False)
     fam_names = L.FAMILIES
@@ -409,12 +517,8 @@ def main():
         mask |= 1 << 63                      # include/dwn.h DWN_PROF_ROCTX
     sync()
     L.check(L.lib.dwn_profile_enable(mask, local_rank), "profile_enable")
-    t0 = time.perf_counter()
-    last = None
-    for _ in range(args.steps):
-        last = model.train_step(next_batch(), sync_loss=False)
-    sync()
-    elapsed = time.perf_counter() - t0
+    last, elapsed = timed_steps(args.steps, lambda: model.train_step(next_batch(), sync_loss=False), sync,
+                                None if start_state is None else (lambda: restore_state(model, start_state, dev)))
     loss_value = float(last["loss"])
     import ctypes as C
     fam_ms = {}
@@ -424,6 +528,8 @@ def main():
             L.check(L.lib.dwn_profile_collect(i, C.byref(ms), C.byref(n)), "profile_collect")
             fam_ms[name] = (ms.value, n.value)
     L.check(L.lib.dwn_profile_enable(0, local_rank), "profile_disable")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), last)
     # every other kernel family: HIP events over a few extra, UNTIMED steps (events around every launch perturb the step)
     fam_all, prof_steps = {}, 0
     if not args.no_rooflines:

@@ -8,7 +8,6 @@ epoch 1, epochs from 1, ``val_*`` merged before the user's epoch_complete callba
 against how scripts/train.py uses the API, not against argus.  What IS pinned to the reference: ``init_weights`` / ``get_lr``
 (bit-exact against src/utils.py, below), the checkpoint file format (src/ema.py:67-72) and ``corr`` (src/metrics.py:11-31)."""
 import csv
-import importlib.util
 import math
 import os
 
@@ -256,16 +255,14 @@ def test_init_weights_rule():
     assert float(net[4].weight.detach().abs().max()) <= 1.0 / math.sqrt(3)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/utils.py"), reason="reference checkout not present")
-def test_init_weights_bit_exact_against_reference():
-    spec = importlib.util.spec_from_file_location("ref_utils", "/root/reference/src/utils.py")
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    a, b = _probe_net(), _probe_net()
-    torch.manual_seed(11)
-    ref.init_weights(a)
+def test_init_weights_bit_exact_against_reference(golden_dir):
+    # tests/golden/init_weights.npz: the reference's init_weights on the same probe net and seed (oracle/make_golden_init.py)
+    z = np.load(golden_dir / "init_weights.npz")
+    b = _probe_net()
     torch.manual_seed(11)
     init_weights(b)
-    for (k, va), vb in zip(a.state_dict().items(), b.state_dict().values()):
-        assert torch.equal(va, vb), k
-    assert ref.get_lr(3e-4, 32) == get_lr(3e-4, 32)
+    sd = b.state_dict()
+    assert sorted(f"sd/{k}" for k in sd) == sorted(k for k in z.files if k.startswith("sd/"))
+    for k, vb in sd.items():
+        assert torch.equal(torch.from_numpy(z[f"sd/{k}"]), vb), k
+    assert float(z["get_lr_3e-4_32"]) == get_lr(3e-4, 32)

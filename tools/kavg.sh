@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in "$@"; do
   if [ $v = base ]; then unset DWN_LIB_PATH; else export DWN_LIB_PATH=$R/build_ab/$v/libdwiseneuro_hip.so; fi
   rm -rf /tmp/ka_$v
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ka_$v -o t -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-rooflines --no-inference --no-other-configs > /tmp/ka_$v.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ka_$v -o t -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-rooflines --no-inference --no-other-configs > /tmp/ka_$v.log 2>&1
   f=$(find /tmp/ka_$v -name "t_kernel_stats.csv" | head -1)
   echo "== $v"; python3 - "$f" "$pat" <<'PY'
 import csv, re, sys

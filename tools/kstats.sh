@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in "$@"; do
   export DWN_Y1=$v
   rm -rf /tmp/ks_$v
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$v -o t -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-rooflines --no-inference --no-other-configs > /tmp/ks_$v.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$v -o t -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-rooflines --no-inference --no-other-configs > /tmp/ks_$v.log 2>&1
   f=$(find /tmp/ks_$v -name "t_kernel_stats.csv" | head -1)
   mkdir -p $R/gpurun_out/kstats; cp $f $R/gpurun_out/kstats/${v}_kernel_stats.csv
   echo "== $v"; python3 - "$f" <<'PY'

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Per-block, per-family table of one training step from rocprofv3 output (no GPU needed to run this).
 
-    rocprofv3 --kernel-trace --stats --output-format csv -d T -o t -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-rooflines
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d F -o p -- python3 bench.py --steps 1 --warmup 1 ...
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d W -o p -- python3 bench.py --steps 1 --warmup 1 ...
+    rocprofv3 --kernel-trace --stats --output-format csv -d T -o t -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-rooflines
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d F -o p -- python3 bench.py --full --steps 1 --warmup 1 ...
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d W -o p -- python3 bench.py --full --steps 1 --warmup 1 ...
     python tools/per_block.py T/t_kernel_trace.csv F W profiles/r2_per_block.json profiles/r2_dws_per_block.json
 
 One step = the dispatches between two adamw_ema_kernel launches.  Every dispatch of the step is assigned to (block, family) from

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Summarise HBM traffic per kernel from two rocprofv3 PMC passes over the same command.
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d <dir_f> -o p -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d <dir_w> -o p -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d <dir_f> -o p -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d <dir_w> -o p -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
     python tools/pmc_traffic.py <dir_f> <dir_w> profiles/r1c_pmc_traffic.json
 
 Units and corrections as MI355X_MICROARCH.md (HBM section) prescribes: FETCH_SIZE / WRITE_SIZE are KiB, summed over the

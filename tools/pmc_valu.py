@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel VALU / LDS utilisation from one rocprofv3 pass:
   rocprofv3 --kernel-trace --pmc SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS \
-            SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d <dir> -o p -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
+            SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d <dir> -o p -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
   python tools/pmc_valu.py <dir>/p_counter_collection.csv [out.json]
 SQ_BUSY_CYCLES sums the 32 shader engines; SQ_ACTIVE_INST_* count quad-cycles summed over the SIMDs (MI355X_MICROARCH.md)."""
 import collections, csv, json, re, sys
