@@ -38,6 +38,18 @@ extern "C" {
 #define DWN_F32_AUTO 0
 #define DWN_F32_NATIVE 1
 #define DWN_F32_SPLIT3 2
+/* BatchNorm mode: the `training` field of dwn_stem_args / dwn_block_args / dwn_cortex_args.
+ * EVAL: normalise with the running statistics, keep nothing for a backward (dwn_*_backward returns -7).
+ * TRAIN: batch statistics, running statistics and num_batches_tracked updated, intermediates saved, backward built.
+ * FROZEN: normalise with the running statistics and do not touch them (as EVAL), take the training kernels and save the same
+ * intermediates (as TRAIN), and run a backward in which BatchNorm is the fixed affine map it was in the forward:
+ * dx = gamma * invstd_running * dy, dgamma = sum dy * xhat, dbeta = sum dy.  For input gradients (receptive fields, most-exciting
+ * inputs) and for fine-tuning with frozen statistics.  The frozen forward follows the training kernels (native fp32 products,
+ * materialised / rebuilt y1 per y1_mode), so it equals the EVAL forward to rounding, not bit for bit.  Workspace sizes and
+ * dwn_block_forward_writes answer for FROZEN as for TRAIN. */
+#define DWN_BN_EVAL 0
+#define DWN_BN_TRAIN 1
+#define DWN_BN_FROZEN 2
 #define DWN_NREP 32 /* replicas of every cross-workgroup statistics buffer: double[DWN_NREP][2][C] */
 
 /* operand loader kinds (how a kernel reads one 16-byte channel vector of an operand) */
@@ -220,7 +232,7 @@ typedef struct dwn_bn {
 
 /* stem: Conv3d(C_in->C0, 1x1x1) + BN on the NCDHW fp32 input — dwiseneuro.py:306-309 */
 typedef struct dwn_stem_args {
-    int dtype, training, B, Cin, C0; long long S;   /* S = T*H*W */
+    int dtype, training, B, Cin, C0; long long S;   /* S = T*H*W; training: DWN_BN_EVAL / _TRAIN / _FROZEN */
     float eps, momentum;
     const float* x;      /* [B][Cin][S] fp32 */
     const float* w;      /* [C0][Cin] */
@@ -234,12 +246,25 @@ typedef struct dwn_stem_args {
     void* ws; size_t ws_bytes;
     double* xmom;        /* [8 + 8*8] input moments: sum x_k, sum x_k x_l — written by the training forward, read by the
                           * backward (y0 = W0 x is linear in the <= 8 input channels: BatchNorm statistics and the weight
-                          * gradient follow from them; saved instead of y0) */
+                          * gradient follow from them; saved instead of y0).  Not used with DWN_BN_FROZEN (may be NULL) */
 } dwn_stem_args;
+
+/* gradient of the stem's output w.r.t. its NCDHW fp32 input (dwn_stem_args has no dx): with BatchNorm as a fixed affine map,
+ * dx[b][k][s] = sum_c w[c][k] * coef[c] * dout[b*S + s][c]   (coef[c] = gamma_c * invstd_c, the first row of dwn_bn.coef as the
+ * forward wrote it).  One streaming pass over dout.  training must be DWN_BN_FROZEN: in DWN_BN_TRAIN the batch statistics add
+ * terms in x (from xmom) that are not built — the call returns -7; DWN_BN_EVAL returns -7 like every backward.
+ * C0 a multiple of 8, at most 128 (bf16) / 64 (fp32); Cin <= 8. */
+typedef struct dwn_stem_input_grad_args {
+    int dtype, training, B, Cin, C0; long long S;
+    const float* w;      /* [C0][Cin] */
+    const float* coef;   /* [4][C0] of the forward (only the scale row is read) */
+    const void* dout;    /* [B*S][C0] in dtype */
+    float* dx;           /* [B][Cin][S] fp32, written whole */
+} dwn_stem_input_grad_args;
 
 /* one InvertedResidual3d preceded by its PositionalEncoding3d — dwiseneuro.py:136-144, 184-192 */
 typedef struct dwn_block_args {
-    int dtype, training;
+    int dtype, training;                     /* training: DWN_BN_EVAL / _TRAIN / _FROZEN */
     int B, T, Hin, Win, Hout, Wout, Cin, Cmid, Cout, stride, ks, kt, se_r;
     float eps, momentum;
     const void* x; void* out;
@@ -281,7 +306,7 @@ typedef struct dwn_pool_args {
 
 /* ShuffleLayer — dwiseneuro.py:228-234 */
 typedef struct dwn_cortex_args {
-    int dtype, training, B, T, Cin, C, groups;
+    int dtype, training, B, T, Cin, C, groups;   /* training: DWN_BN_EVAL / _TRAIN / _FROZEN */
     float eps, momentum;
     const void* x; void* out; void* y;      /* y: raw conv output [B*T][C] (saved) */
     const float* w;                         /* [C][Cin/groups] */
@@ -399,6 +424,7 @@ int dwn_conv_pw_bn_stats(const void* a0, long long a0_ld, long long M, const flo
 size_t dwn_stem_workspace_bytes(const dwn_stem_args* a);
 int dwn_stem_forward(const dwn_stem_args* a, int device, void* stream);
 int dwn_stem_backward(const dwn_stem_args* a, int device, void* stream);
+int dwn_stem_input_grad(const dwn_stem_input_grad_args* a, int device, void* stream);
 size_t dwn_block_workspace_bytes(const dwn_block_args* a, int backward);
 int dwn_block_forward(const dwn_block_args* a, int device, void* stream);
 int dwn_block_backward(const dwn_block_args* a, int device, void* stream);

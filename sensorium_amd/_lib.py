@@ -36,6 +36,7 @@ LD_PLAIN, LD_PE, LD_BNACT, LD_AFFINE2, LD_DY3, LD_GATE, LD_CAT1 = 0, 1, 2, 3, 4,
 EPI_STORE, EPI_READOUT, EPI_DG, EPI_STORE_CAT, EPI_DH3 = 0, 1, 2, 3, 4
 NN_AUTO, NN_XL128, NN_XL256, NN_TILE128, NN_KD = 0, 1, 2, 3, 4
 F32_AUTO, F32_NATIVE, F32_SPLIT3 = 0, 1, 2
+BN_EVAL, BN_TRAIN, BN_FROZEN = 0, 1, 2      # the `training` field of StemArgs / BlockArgs / CortexArgs (include/dwn.h DWN_BN_*)
 FAMILIES = ("pw_fwd", "dws_fwd", "dwt_fwd", "se_pool", "pwl_fwd", "resid_fwd", "resid_bwd", "pwl_dgrad", "pwl_wgrad",
             "bn3_reduce", "dwt_bwd", "dws_bwd", "pw_dgrad", "pw_wgrad", "cortex_fwd", "cortex_bwd", "readout_fwd",
             "readout_bwd")
@@ -100,6 +101,11 @@ class StemArgs(C.Structure):
                 ("pe_t", c_p), ("pe_h", c_p), ("pe_w", c_p), ("T", c_i), ("H", c_i), ("W", c_i),
                 ("y0", c_p), ("out", c_p),
                 ("dout", c_p), ("dw", c_p), ("ws", c_p), ("ws_bytes", c_sz), ("xmom", c_p)]
+
+
+class StemInputGradArgs(C.Structure):
+    _fields_ = [("dtype", c_i), ("training", c_i), ("B", c_i), ("Cin", c_i), ("C0", c_i), ("S", c_ll),
+                ("w", c_p), ("coef", c_p), ("dout", c_p), ("dx", c_p)]
 
 
 class BlockArgs(C.Structure):
@@ -179,7 +185,7 @@ _STRUCTS = {
     "dwn_bn": BN, "dwn_stem_args": StemArgs, "dwn_block_args": BlockArgs, "dwn_pool_args": PoolArgs,
     "dwn_cortex_args": CortexArgs, "dwn_readout_args": ReadoutArgs, "dwn_tensor_entry": TensorEntry,
     "dwn_clip_src": ClipSrc, "dwn_clip_desc": ClipDesc, "dwn_pw_bwd_args": PwBwdArgs,
-    "dwn_dw_spatial_rc_fwd_args": DwSpatialRcFwdArgs,
+    "dwn_dw_spatial_rc_fwd_args": DwSpatialRcFwdArgs, "dwn_stem_input_grad_args": StemInputGradArgs,
 }
 
 # every symbol include/dwn.h declares: (restype, argtypes)
@@ -205,6 +211,7 @@ SYMBOLS = {
     "dwn_stem_workspace_bytes": (c_sz, [_P(StemArgs)]),
     "dwn_stem_forward": (c_i, [_P(StemArgs), c_i, c_p]),
     "dwn_stem_backward": (c_i, [_P(StemArgs), c_i, c_p]),
+    "dwn_stem_input_grad": (c_i, [_P(StemInputGradArgs), c_i, c_p]),
     "dwn_block_workspace_bytes": (c_sz, [_P(BlockArgs), c_i]),
     "dwn_block_forward": (c_i, [_P(BlockArgs), c_i, c_p]),
     "dwn_block_backward": (c_i, [_P(BlockArgs), c_i, c_p]),
@@ -260,11 +267,13 @@ def _load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(or `make -C {LIB_PATH.parent}`).  sensorium_amd has no fallback path.")
     lib = C.CDLL(str(LIB_PATH), mode=getattr(os, "RTLD_NOW", 2))
+    ab = bool(os.environ.get("DWN_LIB_PATH"))      # an explicitly chosen other build: a same-box A/B run of an older library
     for name, (restype, argtypes) in SYMBOLS.items():
+        if ab and name == "dwn_stem_input_grad" and not hasattr(lib, name):
+            continue                     # (A/B: a library from before the frozen-statistics mode; the training step does not call it)
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
-    ab = bool(os.environ.get("DWN_LIB_PATH"))      # an explicitly chosen other build: a same-box A/B run of an older library
     if lib.dwn_abi_version() != 7 and not (ab and lib.dwn_abi_version() == 6):
         raise ImportError("libdwiseneuro_hip.so ABI version mismatch")
     built, have = lib.dwn_source_hash().decode(), source_hash()
@@ -273,7 +282,7 @@ def _load():
                           f"`make -C {LIB_PATH.parent}` — binaries are not in git, so what runs must be what is committed")
     for cname, struct in _STRUCTS.items():
         n = lib.dwn_sizeof(cname.encode())
-        if n != C.sizeof(struct) and not (ab and 0 < n < C.sizeof(struct)):      # (A/B: ABI 7 only appended a field)
+        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname == "dwn_stem_input_grad_args")):      # (A/B: ABI 7 only appended)
             raise ImportError(f"struct layout mismatch for {cname}: C {n} bytes vs ctypes {C.sizeof(struct)}")
     return lib
 

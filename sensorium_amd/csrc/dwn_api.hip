@@ -308,6 +308,7 @@ int dwn_sizeof(const char* name) {
     SZ(dwn_dw_spatial_bwd_args); SZ(dwn_dw_temporal_fwd_args); SZ(dwn_dw_temporal_bwd_args); SZ(dwn_bn);
     SZ(dwn_stem_args); SZ(dwn_block_args); SZ(dwn_pool_args); SZ(dwn_cortex_args); SZ(dwn_readout_args);
     SZ(dwn_tensor_entry); SZ(dwn_clip_src); SZ(dwn_clip_desc); SZ(dwn_pw_bwd_args); SZ(dwn_dw_spatial_rc_fwd_args);
+    SZ(dwn_stem_input_grad_args);
 #undef SZ
     return -1;
 }
@@ -420,13 +421,13 @@ int dwn_stem_forward(const dwn_stem_args* a, int device, void* stream) {
     double* mom = c.take<double>((size_t)DWN_NREP * stem_moment_count());
     if (!c.ok()) return dwn_set_error(-6, "stem: workspace too small");
     const i64 M = (i64)a->B * a->S;
-    if (a->training) {
+    if (a->training == DWN_BN_TRAIN) {
         if (!a->xmom) return dwn_set_error(-1, "stem_forward: xmom buffer required in training mode");
         TRY(k_zero(mom, (size_t)DWN_NREP * stem_moment_count() * sizeof(double), s));
         TRY(k_stem_xmom(a->x, a->B, a->Cin, a->S, mom, s));
         TRY(k_stem_bn_finalize(mom, (double)M, a->w, a->bn.gamma, a->bn.beta, a->bn.running_mean, a->bn.running_var,
                                a->bn.num_batches_tracked, a->momentum, a->eps, a->bn.coef, a->xmom, a->C0, a->Cin, s));
-    } else {
+    } else {      // eval and frozen: coefficients from the running statistics, which stay as they are
         TRY(bn_finalize(nullptr, a->C0, (double)M, a->bn, a->C0, 0, a->momentum, a->eps, s));
     }
     return k_stem_out(a->x, a->w, a->bn.coef, a->pe_t, a->pe_h, a->pe_w, a->T, a->H, a->W, a->B, a->Cin, a->S, a->C0, a->out,
@@ -435,15 +436,36 @@ int dwn_stem_forward(const dwn_stem_args* a, int device, void* stream) {
 int dwn_stem_backward(const dwn_stem_args* a, int device, void* stream) {
     ENTER(device);
     hipStream_t s = (hipStream_t)stream;
-    if (!a->xmom) return dwn_set_error(-1, "stem_backward: xmom (saved by the forward) required");
+    const bool frozen = a->training == DWN_BN_FROZEN;
+    if (!frozen && !a->xmom) return dwn_set_error(-1, "stem_backward: xmom (saved by the forward) required");
     Carver c(a->ws, a->ws_bytes);
-    (void)c.take<double>((size_t)DWN_NREP * stem_moment_count());
+    double* mom = c.take<double>((size_t)DWN_NREP * stem_moment_count());
     double* acc = c.take<double>((size_t)DWN_NREP * a->C0 * stem_acc_stride());
     if (!c.ok()) return dwn_set_error(-6, "stem: workspace too small");
     const i64 M = (i64)a->B * a->S;
+    if (frozen) {
+        // frozen statistics: the same accumulation pass with zero input means (the workspace's moment slot, cleared with the
+        // accumulators: the two are adjacent) -> raw sums Σ dout x_k, Σ dout; the frozen finaliser needs no batch moments
+        TRY(k_zero(mom, (size_t)((char*)(acc + (size_t)DWN_NREP * a->C0 * stem_acc_stride()) - (char*)mom), s));
+        TRY(k_stem_bwd_acc(a->dout, a->x, mom, (double)M, a->B, a->Cin, a->S, a->C0, acc, a->dtype, s));
+        return k_stem_bwd_finalize_frozen(acc, a->w, a->bn.coef, a->bn.dgamma, a->bn.dbeta, a->dw, a->C0, a->Cin, s);
+    }
     TRY(k_zero(acc, (size_t)DWN_NREP * a->C0 * stem_acc_stride() * sizeof(double), s));
     TRY(k_stem_bwd_acc(a->dout, a->x, a->xmom, (double)M, a->B, a->Cin, a->S, a->C0, acc, a->dtype, s));
     return k_stem_bwd_finalize(acc, a->xmom, a->w, a->bn.coef, (double)M, a->bn.dgamma, a->bn.dbeta, a->dw, a->C0, a->Cin, s);
+}
+
+// dx of the stem with BatchNorm as a fixed affine map (dwn.h): one streaming pass over dout
+int dwn_stem_input_grad(const dwn_stem_input_grad_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a || !a->w || !a->coef || !a->dout || !a->dx) return dwn_set_error(-1, "stem_input_grad: null pointer");
+    if (a->C0 <= 0 || a->C0 % 8 || a->Cin <= 0 || a->B <= 0 || a->S <= 0)
+        return dwn_set_error(-2, "stem_input_grad: C0 must be a positive multiple of 8; B, Cin, S positive");
+    if (a->dtype != DWN_F32 && a->dtype != DWN_BF16) return dwn_set_error(-2, "stem_input_grad: dtype");
+    if (a->training != DWN_BN_FROZEN)
+        return dwn_set_error(-7, "stem_input_grad: only the frozen-statistics (DWN_BN_FROZEN) input gradient is built");
+    ENTER(device);
+    return k_stem_input_grad(a->dout, a->w, a->coef, a->B, a->Cin, a->S, a->C0, a->dx, a->dtype, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------ block
@@ -458,7 +480,12 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
     TRY(check_block(a));
     BlockWs w = carve_block(a, 0, a.ws, a.ws_bytes);
     if (w.bytes > a.ws_bytes) return dwn_set_error(-6, "block_forward: workspace too small");
-    const int dt = a.dtype, tr = a.training;
+    // tr: the training kernels and their saved intermediates (DWN_BN_TRAIN and DWN_BN_FROZEN); bs: batch statistics (DWN_BN_TRAIN).
+    // Frozen: every BatchNorm's coefficients are known before the first launch (prep, as eval), so the Gram pass, the shortcut's
+    // statistics pass and all finalisers go; the statistics epilogues of the GEMMs / stencils stay (same kernels, same arguments
+    // as training: their sums land in the zeroed arena and nobody reads them)
+    const int dt = a.dtype, tr = a.training != DWN_BN_EVAL;
+    const bool bs = a.training == DWN_BN_TRAIN;
     const i64 Min = (i64)a.B * a.T * a.Hin * a.Win, Mout = (i64)a.B * a.T * a.Hout * a.Wout;
     const int S_out = a.T * a.Hout * a.Wout;
     {   // one launch: zero the statistics arena, pack the four weights
@@ -468,7 +495,7 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
         ok = ok && pa.packw(a.w_pwl, w.wpwl, 1, a.Cout, a.Cmid, 0, a.Cout, a.Cmid);
         ok = ok && pa.packdw(a.w_dws, w.wdws, a.Cmid, a.ks * a.ks);
         ok = ok && pa.packdw(a.w_dwt, w.wdwt, a.Cmid, a.kt);
-        if (!tr) {      // eval: the five BatchNorm coefficient sets come from running statistics — same launch
+        if (!bs) {      // eval / frozen: the five BatchNorm coefficient sets come from running statistics — same launch
             ok = ok && pa.bneval(a.bn1, a.Cmid, a.eps) && pa.bneval(a.bn2, a.Cmid, a.eps) && pa.bneval(a.bn3, a.Cmid, a.eps);
             ok = ok && pa.bneval(a.bn4, a.Cout, a.eps) && pa.bneval(a.bnsc, a.Cout, a.eps);
         }
@@ -510,12 +537,14 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
         // chained stencil rebuilds the y1 rows it needs from a0 on the matrix cores: conv_pw is no pass, a.y1 is not written
         LoadDesc cat = ld_plain(a0, a.Cin);
         cat.cat_c1 = a.Cin; cat.cat_c2 = 0;
+        if (bs) {                                     // (frozen: BatchNorm-1 is known, no Gram pass)
         GemmTN g = tn_base(cat, LD_CAT1, ld_plain(a0, a.Cin), LD_PLAIN, (int)Min, a.Cin + 8, a.Cin, reinterpret_cast<float*>(w.gram), a.Cin, 1);
         g.dw_f64 = 1;                                 // fp64 atomics: the variance is a difference of these sums
         PROF(DWN_FAM_PW_FWD, launch_gemm_tn(g, dt, s));
         PROF(DWN_FAM_PW_FWD, k_bn1_gram_finalize(w.gram, a.w_pw, a.Cmid, a.Cin, (double)Min, a.bn1.gamma, a.bn1.beta, a.bn1.running_mean,
                                                  a.bn1.running_var, a.bn1.num_batches_tracked, a.momentum, a.eps, a.bn1.coef,
                                                  identity_sc ? w.stsc : nullptr, dt, s));
+        }
         DwSpatialFwd d; memset(&d, 0, sizeof(d));
         d.in = ld_bnact(nullptr, a.Cmid, a.bn1.coef, a.Cmid, 1, nullptr, 0, 1);
         d.a0 = a0; d.a0_ld = a.Cin; d.w1 = w.wpw; d.Cin = a.Cin;
@@ -538,7 +567,7 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
         g.stats = tr ? w.st1 : nullptr; g.stat_nchan = a.Cmid;
         PROF(DWN_FAM_PW_FWD, launch_gemm_nn(g, dt, s));
     }
-    if (tr) TRY(bn_finalize(w.st1, a.Cmid, (double)Min, a.bn1, a.Cmid, tr, a.momentum, a.eps, s));
+    if (bs) TRY(bn_finalize(w.st1, a.Cmid, (double)Min, a.bn1, a.Cmid, 1, a.momentum, a.eps, s));
     // spat_covn_dw (:96-102)
     {
         DwSpatialFwd d; memset(&d, 0, sizeof(d));
@@ -548,7 +577,7 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
         PROF(DWN_FAM_DWS_FWD, launch_dw_spatial_fwd(d, dt, s));
     }
     }
-    if (tr) TRY(bn_finalize(w.st2, a.Cmid, (double)Mout, a.bn2, a.Cmid, tr, a.momentum, a.eps, s));
+    if (bs) TRY(bn_finalize(w.st2, a.Cmid, (double)Mout, a.bn2, a.Cmid, 1, a.momentum, a.eps, s));
     // temp_covn_dw (:105-111)
     const bool eval_z3 = !tr;       // eval: z3 and the SE pooling sums come straight from the temporal pass (integer sums: any order)
     {
@@ -561,7 +590,7 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
         }
         PROF(DWN_FAM_DWT_FWD, launch_dw_temporal_fwd(d, dt, s));
     }
-    if (tr) TRY(bn_finalize(w.st3, a.Cmid, (double)Mout, a.bn3, a.Cmid, tr, a.momentum, a.eps, s));
+    if (bs) TRY(bn_finalize(w.st3, a.Cmid, (double)Mout, a.bn3, a.Cmid, 1, a.momentum, a.eps, s));
     // se (:38-43)
     if (!eval_z3) {
         LoadDesc z3 = ld_bnact(a.y3, a.Cmid, a.bn3.coef, a.Cmid, 1, nullptr, 0, S_out);
@@ -587,7 +616,7 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
     }
     // shortcut (:125-134) + residual (:143); the two linear BatchNorms (conv_pwl.1.bn, bn_sc.bn) finalise in one launch
     ResGeom gm = geom_of(a);
-    if (tr) {
+    if (bs) {
         // (y1-free on an identity-map block: the shortcut's sums came out of the Gram pass, k_bn1_gram_finalize)
         if (!(y1_free && identity_sc)) PROF(DWN_FAM_RESID_FWD, k_shortcut_stats(xin, gm, w.stsc, dt, s));
         TRY(k_bn_finalize_train2(fin_job(w.st4, a.Cout, (double)Mout, a.bn4, a.Cout),
@@ -636,11 +665,14 @@ static int pw_backward(int dt, const void* dh1, const void* a0, const float* w_p
 }
 
 int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
-    ENTER(device);
     const dwn_block_args& a = *ap;
     hipStream_t s = (hipStream_t)stream;
+    g_err[0] = 0;                    // the argument checks need no device: they answer the same on a host without one
     TRY(check_block(a));
-    if (!a.training) return dwn_set_error(-7, "block_backward: only training-mode (batch-statistics) backward is built");
+    if (a.training == DWN_BN_EVAL)
+        return dwn_set_error(-7, "block_backward: only training-mode (batch-statistics) and frozen-statistics backward are built");
+    ENTER(device);
+    const bool frozen = a.training == DWN_BN_FROZEN;   // BatchNorm backward triples (scale, 0, 0): every consumer below runs unchanged
     BlockWs w = carve_block(a, 1, a.ws, a.ws_bytes);
     if (w.bytes > a.ws_bytes) return dwn_set_error(-6, "block_backward: workspace too small");
     const int dt = a.dtype;
@@ -673,8 +705,8 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
     ResGeom gm = geom_of(a);
     // residual + the two linear BNs (bn4 = conv_pwl.1.bn, bnsc = bn_sc.bn)
     PROF(DWN_FAM_RESID_BWD, k_residual_bwd_reduce(xin, a.y4, a.dout, a.bn4.coef, a.bnsc.coef, a.drop_scale, gm, w.st4, w.stsc, dt, s));
-    TRY(k_bn_bwd_finalize2(bwd_job(w.st4, (double)Mout, a.bn4, w.abc4, a.Cout),
-                           bwd_job(w.stsc, (double)Mout, a.bnsc, w.abcsc, a.Cout), s));
+    TRY((frozen ? k_bn_bwd_finalize_frozen2 : k_bn_bwd_finalize2)(bwd_job(w.st4, (double)Mout, a.bn4, w.abc4, a.Cout),
+                                                                  bwd_job(w.stsc, (double)Mout, a.bnsc, w.abcsc, a.Cout), s));
     PROF(DWN_FAM_RESID_BWD, k_residual_bwd_dy4(a.y4, a.dout, w.abc4, a.drop_scale, gm, a.dy4, dt, s));
     // conv_pwl backward: du = dy4 @ W2 (+ SE gate gradient), dW2 = dy4^T @ u
     void* du = a.buf_a;
@@ -719,7 +751,8 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
     // ... and dh3 replaces du in place, so the temporal kernel reads (dh3, y3) with the plain BN-backward affine
     PROF(DWN_FAM_BN3_REDUCE, k_bn3_bwd_reduce(d3, a.bn3.coef, Mout, a.Cmid, w.st3, du, dt, s));
     }
-    TRY(k_bn_bwd_finalize(w.st3, (double)Mout, a.bn3.coef, a.bn3.dgamma, a.bn3.dbeta, w.abc3, a.Cmid, s));
+    if (frozen) TRY(k_bn_bwd_finalize_frozen(w.st3, a.bn3.coef, a.bn3.dgamma, a.bn3.dbeta, w.abc3, a.Cmid, s));
+    else TRY(k_bn_bwd_finalize(w.st3, (double)Mout, a.bn3.coef, a.bn3.dgamma, a.bn3.dbeta, w.abc3, a.Cmid, s));
     // temporal dw backward
     {
         DwTemporalBwd d; memset(&d, 0, sizeof(d));
@@ -730,7 +763,8 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
         d.kt = a.kt; d.stats = w.st2;
         PROF(DWN_FAM_DWT_BWD, launch_dw_temporal_bwd(d, dt, s));
     }
-    TRY(k_bn_bwd_finalize(w.st2, (double)Mout, a.bn2.coef, a.bn2.dgamma, a.bn2.dbeta, w.abc2, a.Cmid, s));
+    if (frozen) TRY(k_bn_bwd_finalize_frozen(w.st2, a.bn2.coef, a.bn2.dgamma, a.bn2.dbeta, w.abc2, a.Cmid, s));
+    else TRY(k_bn_bwd_finalize(w.st2, (double)Mout, a.bn2.coef, a.bn2.dgamma, a.bn2.dbeta, w.abc2, a.Cmid, s));
     // spatial dw backward (du is dead: reuse buf_a for dh1)
     void* dh1 = a.buf_a;
     {
@@ -742,7 +776,8 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
         d.Hout = a.Hout; d.Wout = a.Wout; d.C = a.Cmid; d.stride = a.stride; d.ks = a.ks; d.stats = w.st1;
         PROF(DWN_FAM_DWS_BWD, launch_dw_spatial_bwd(d, dt, s));
     }
-    TRY(k_bn_bwd_finalize(w.st1, (double)Min, a.bn1.coef, a.bn1.dgamma, a.bn1.dbeta, w.abc1, a.Cmid, s));
+    if (frozen) TRY(k_bn_bwd_finalize_frozen(w.st1, a.bn1.coef, a.bn1.dgamma, a.bn1.dbeta, w.abc1, a.Cmid, s));
+    else TRY(k_bn_bwd_finalize(w.st1, (double)Min, a.bn1.coef, a.bn1.dgamma, a.bn1.dbeta, w.abc1, a.Cmid, s));
     // conv_pw backward WITHOUT y1.  dy1 = A1*dh1 + A2*y1 + A3 is linear and y1 = a0.W1^T, so the y1 terms fold into Cin x Cin
     // matrices on either side:  da0 = [dh1 | a0] . [diag(A1) W1 ; G] + r3  (Bp, r3: k_pw_bwd_prep) and
     // dW1 = diag(A1) (dh1^T a0) + diag(A2) W1 (a0^T a0) + A3 (1^T a0)  (raw products in tacc, folded by k_pw_wgrad_fold)
@@ -823,33 +858,38 @@ int dwn_cortex_forward(const dwn_cortex_args* ap, int device, void* stream) {
     if (a.Cin % (8 * a.groups) || a.C % (8 * a.groups)) return dwn_set_error(-2, "cortex: channels per group must be multiples of 8");
     CortexWs w = carve_cortex(a, 0, a.ws, a.ws_bytes);
     if (w.bytes > a.ws_bytes) return dwn_set_error(-6, "cortex_forward: workspace too small");
-    const int M = a.B * a.T, Kg = a.Cin / a.groups, Ng = a.C / a.groups, dt = a.dtype, tr = a.training;
+    // tr: the training path's products (DWN_BN_TRAIN / _FROZEN); bs: batch statistics.  Frozen: coefficients in the prep launch
+    const int M = a.B * a.T, Kg = a.Cin / a.groups, Ng = a.C / a.groups, dt = a.dtype, tr = a.training != DWN_BN_EVAL;
+    const bool bs = a.training == DWN_BN_TRAIN;
     {
         PrepArgs pa;
         bool ok = pa.zero(w.zb, ((size_t)(w.ze - w.zb) + 15) & ~(size_t)15);
         ok = ok && pa.packw(a.w, w.wp, 1, a.C, Kg, 0, a.C, Kg);
+        if (tr && !bs) ok = ok && pa.bneval(a.bn, a.C, a.eps) && pa.bneval(a.bnsc, a.C, a.eps);
         if (!ok) return dwn_set_error(-2, "cortex_forward: workspace arena must be 16-byte aligned");
         TRY(k_prep(pa, dt, s));
     }
     GemmNN g = nn_base(ld_plain(a.x, a.Cin), LD_PLAIN, w.wp, Kg, a.y, a.C, M, Ng, Kg, a.groups);
     g.stats = tr ? w.st : nullptr; g.stat_nchan = a.C; g.f32_split = f32_split_of(a.f32_products, !tr);
     PROF(DWN_FAM_CORTEX_FWD, launch_gemm_nn(g, dt, s));
-    if (tr) {
+    if (bs) {
         TRY(k_colstats(ld_plain(a.x, a.Cin), LD_PLAIN, M, a.Cin, w.stsc, dt, s));
         TRY(k_bn_finalize_train2(fin_job(w.st, a.C, (double)M, a.bn, a.C), fin_job(w.stsc, a.Cin, (double)M, a.bnsc, a.C),
                                  a.momentum, a.eps, s));
-    } else {
-        TRY(bn_finalize(w.st, a.C, (double)M, a.bn, a.C, tr, a.momentum, a.eps, s));
-        TRY(bn_finalize(w.stsc, a.Cin, (double)M, a.bnsc, a.C, tr, a.momentum, a.eps, s));
+    } else if (!tr) {
+        TRY(bn_finalize(w.st, a.C, (double)M, a.bn, a.C, 0, a.momentum, a.eps, s));
+        TRY(bn_finalize(w.stsc, a.Cin, (double)M, a.bnsc, a.C, 0, a.momentum, a.eps, s));
     }
     return k_cortex_residual_fwd(a.y, a.x, a.bn.coef, a.bnsc.coef, a.drop_scale, M, a.T, a.Cin, a.C, a.groups, a.out,
                                  dt, s);
 }
 int dwn_cortex_backward(const dwn_cortex_args* ap, int device, void* stream) {
-    ENTER(device);
     const dwn_cortex_args& a = *ap;
     hipStream_t s = (hipStream_t)stream;
-    if (!a.training) return dwn_set_error(-7, "cortex_backward: only training-mode backward is built");
+    g_err[0] = 0;
+    if (a.training == DWN_BN_EVAL) return dwn_set_error(-7, "cortex_backward: only training-mode and frozen-statistics backward are built");
+    ENTER(device);
+    const bool frozen = a.training == DWN_BN_FROZEN;
     CortexWs w = carve_cortex(a, 1, a.ws, a.ws_bytes);
     if (w.bytes > a.ws_bytes) return dwn_set_error(-6, "cortex_backward: workspace too small");
     const int M = a.B * a.T, Kg = a.Cin / a.groups, Ng = a.C / a.groups, dt = a.dtype;
@@ -865,7 +905,8 @@ int dwn_cortex_backward(const dwn_cortex_args* ap, int device, void* stream) {
     }
     TRY(k_cortex_bwd_reduce(a.y, a.x, a.dout, a.dout_mask, a.dout_mask_ld, a.bn.coef, a.bnsc.coef, a.drop_scale, M, a.T,
                             a.Cin, a.C, a.groups, w.st, w.stsc, dt, s));
-    TRY(k_bn_bwd_finalize2(bwd_job(w.st, (double)M, a.bn, w.abc, a.C), bwd_job(w.stsc, (double)M, a.bnsc, w.abcsc, a.C), s));
+    TRY((frozen ? k_bn_bwd_finalize_frozen2 : k_bn_bwd_finalize2)(bwd_job(w.st, (double)M, a.bn, w.abc, a.C),
+                                                                  bwd_job(w.stsc, (double)M, a.bnsc, w.abcsc, a.C), s));
     TRY(k_cortex_bwd_dy(a.y, a.dout, a.dout_mask, a.dout_mask_ld, a.bn.coef, w.abc, a.drop_scale, M, a.T, a.C, a.groups,
                         w.dy, dt, s));
     {

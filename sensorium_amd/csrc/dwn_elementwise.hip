@@ -176,6 +176,45 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize2_kernel(BnBwdJob j0, BnBw
     bn_bwd_finalize_body(first ? blockIdx.x : blockIdx.x - j0.nblocks, j.stats, j.count, j.coef, j.dgamma, j.dbeta, j.abc, j.C);
 }
 
+// frozen statistics (dwn.h DWN_BN_FROZEN): the forward's BatchNorm was the fixed affine map scale * y + shift, so its backward is
+// dy = scale * dh — the triple (scale, 0, 0) for the same consumers — and dgamma = Σdh·ŷ, dbeta = Σdh come from the same two sums
+// (the producers took ŷ with coef's mean / invstd: the running statistics)
+__device__ __forceinline__ void bn_bwd_finalize_frozen_body(const int blk, const double* stats, const float* coef, float* dgamma,
+                                                            float* dbeta, float* abc, int C) {
+    const int r = threadIdx.x & 31;
+    const int c = blk * 8 + (threadIdx.x >> 5);
+    const bool ok = c < C;
+    double s1, s2;
+    rep_reduce(stats, C, ok ? c : 0, r, ok, s1, s2);
+    if (!ok || r != 0) return;
+    if (dgamma) dgamma[c] = (float)s2;
+    if (dbeta) dbeta[c] = (float)s1;
+    abc[c] = coef[c];
+    abc[C + c] = 0.f;
+    abc[2 * C + c] = 0.f;
+}
+__global__ __launch_bounds__(256) void bn_bwd_finalize_frozen_kernel(const double* stats, const float* coef, float* dgamma,
+                                                                     float* dbeta, float* abc, int C) {
+    bn_bwd_finalize_frozen_body(blockIdx.x, stats, coef, dgamma, dbeta, abc, C);
+}
+__global__ __launch_bounds__(256) void bn_bwd_finalize_frozen2_kernel(BnBwdJob j0, BnBwdJob j1) {
+    const bool first = (int)blockIdx.x < j0.nblocks;
+    const BnBwdJob& j = first ? j0 : j1;
+    bn_bwd_finalize_frozen_body(first ? blockIdx.x : blockIdx.x - j0.nblocks, j.stats, j.coef, j.dgamma, j.dbeta, j.abc, j.C);
+}
+int k_bn_bwd_finalize_frozen(const double* stats, const float* coef, float* dgamma, float* dbeta, float* abc, int C,
+                             hipStream_t s) {
+    hipLaunchKernelGGL(bn_bwd_finalize_frozen_kernel, dim3((C + 7) / 8), dim3(256), 0, s, stats, coef, dgamma, dbeta, abc, C);
+    DWN_CHECK_LAUNCH();
+    return 0;
+}
+int k_bn_bwd_finalize_frozen2(BnBwdJob j0, BnBwdJob j1, hipStream_t s) {
+    j0.nblocks = (j0.C + 7) / 8; j1.nblocks = (j1.C + 7) / 8;
+    hipLaunchKernelGGL(bn_bwd_finalize_frozen2_kernel, dim3(j0.nblocks + j1.nblocks), dim3(256), 0, s, j0, j1);
+    DWN_CHECK_LAUNCH();
+    return 0;
+}
+
 int k_bn_finalize_train(const double* stats, int stat_c, double count, const float* gamma, const float* beta,
                         float* rm, float* rv, long long* nbt, float momentum, float eps, float* coef, int C,
                         hipStream_t s) {
@@ -704,6 +743,162 @@ int k_stem_bwd_finalize(const double* acc, const double* xmom, const float* w, c
 }
 int stem_moment_count() { return STEM_NM; }
 int stem_acc_stride() { return STEM_MAXCIN + 1; }
+
+// frozen statistics: the accumulation ran with x̄ = 0 (zeroed moments), so acc holds Σ dout_c x_k and Σ dout_c; BatchNorm is the
+// fixed map scale * (w.x) + shift:  dbeta = Σ dout, dgamma = invstd (w . Σ dout x - mean Σ dout), dW[c][k] = scale Σ dout_c x_k
+__global__ __launch_bounds__(256) void stem_bwd_finalize_frozen_kernel(const double* acc, const float* w, const float* coef,
+                                                                       float* dgamma, float* dbeta, float* dw, int C0, int Cin) {
+    constexpr int NV = STEM_MAXCIN + 1;
+    const int part = threadIdx.x & 3;
+    for (int cb = 0; cb < C0; cb += blockDim.x / 4) {
+        const int c = cb + (threadIdx.x >> 2);
+        const bool ok = c < C0;
+        double dx[STEM_MAXCIN], s1 = 0.0;
+        for (int k = 0; k < STEM_MAXCIN; ++k) dx[k] = 0.0;
+        for (int r = part * (DWN_NREP / 4); r < (part + 1) * (DWN_NREP / 4); ++r) {
+            const double* p = acc + ((i64)r * C0 + (ok ? c : 0)) * NV;
+            for (int k = 0; k < Cin; ++k) dx[k] += p[k];
+            s1 += p[STEM_MAXCIN];
+        }
+        for (int o = 1; o < 4; o <<= 1) {
+            for (int k = 0; k < STEM_MAXCIN; ++k) dx[k] += __shfl_xor(dx[k], o);
+            s1 += __shfl_xor(s1, o);
+        }
+        if (!ok || part != 0) continue;
+        const double scale = coef[c], mean = coef[2 * C0 + c], invstd = coef[3 * C0 + c];
+        double dy = 0.0;                                    // Σ dout y0
+        for (int k = 0; k < Cin; ++k) dy += (double)w[c * Cin + k] * dx[k];
+        if (dgamma) dgamma[c] = (float)(invstd * (dy - mean * s1));
+        if (dbeta) dbeta[c] = (float)s1;
+        for (int k = 0; k < Cin; ++k) dw[c * Cin + k] = (float)(scale * dx[k]);
+    }
+}
+int k_stem_bwd_finalize_frozen(const double* acc, const float* w, const float* coef, float* dgamma, float* dbeta, float* dw,
+                               int C0, int Cin, hipStream_t s) {
+    hipLaunchKernelGGL(stem_bwd_finalize_frozen_kernel, dim3(1), dim3(256), 0, s, acc, w, coef, dgamma, dbeta, dw, C0, Cin);
+    DWN_CHECK_LAUNCH();
+    return 0;
+}
+
+// Input gradient of the stem with BatchNorm as a fixed affine map (dwn.h dwn_stem_input_grad): dx[b][k][s] = Σ_c w[c][k] scale_c
+// dout[b S + s][c].  C0 -> Cin <= 8 is too thin for the matrix cores: one streaming pass, 16-byte loads along the channels.  A wave
+// takes 64 consecutive rows: the 8 lanes of a row group (cv) read one row's channel vectors, row group pl takes rows pl*8 .. pl*8+7
+// in 8 loads; each lane then holds 8 rows x Cin partial sums over its channels, and a three-step transpose-reduce over the 8 lanes
+// (half of the values change hands at each step: 4 + 2 + 1 rows x Cin shuffles instead of 3 x 8 rows x Cin) leaves lane cv with the
+// full sums of row pl*8 + cv — lane l owns row l of the tile, so each of the Cin planes is written as one 256-byte run.
+// No atomics: the summation order is fixed.
+template <typename T, int CINT, int NJ>
+__global__ __launch_bounds__(256) void stem_input_grad_kernel(const T* dout, const float* w, const float* coef, int B, int Cin, i64 S,
+                                                              int C0, float* dx) {
+    constexpr int KC = TT<T>::KC;
+    const int tid = threadIdx.x, lane = tid & 63, cv = lane & 7, pl = lane >> 3;
+    float wa[NJ][CINT][KC];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int i = 0; i < KC; ++i) {
+            const int c = (cv + 8 * j) * KC + i;
+            const bool ok = c < C0;
+            const float sc = ok ? coef[c] : 0.f;
+#pragma unroll
+            for (int k = 0; k < CINT; ++k) wa[j][k][i] = (ok && k < Cin) ? w[c * Cin + k] * sc : 0.f;
+        }
+    const unsigned rows = (unsigned)((i64)B * S);
+    const unsigned ntiles = (rows + 63u) / 64u, nwaves = gridDim.x * 4u;
+    const UDiv32 dS((unsigned)S);
+    const bool b2 = (cv & 4) != 0, b1 = (cv & 2) != 0, b0 = (cv & 1) != 0;
+    for (unsigned tile = blockIdx.x * 4u + (tid >> 6); tile < ntiles; tile += nwaves) {
+        const unsigned base = tile * 64u;
+        float g[8][NJ][KC];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            unsigned row = base + pl * 8 + u;
+            row = row < rows ? row : rows - 1;               // tail rows: a valid address, the result is not stored
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int chan = (cv + 8 * j) * KC;
+                if (chan < C0) {
+                    ld_vec<T>(dout + (i64)row * C0 + chan, g[u][j]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < KC; ++i) g[u][j][i] = 0.f;
+                }
+            }
+        }
+        float v[8][CINT];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+            for (int k = 0; k < CINT; ++k) {
+                float a = 0.f;
+#pragma unroll
+                for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                    for (int i = 0; i < KC; ++i) a = fmaf(g[u][j][i], wa[j][k][i], a);
+                v[u][k] = a;
+            }
+        float r4[4][CINT], r2[2][CINT], r1[CINT];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int k = 0; k < CINT; ++k) {
+                const float keep = b2 ? v[u + 4][k] : v[u][k], send = b2 ? v[u][k] : v[u + 4][k];
+                r4[u][k] = keep + __shfl_xor(send, 4);
+            }
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int k = 0; k < CINT; ++k) {
+                const float keep = b1 ? r4[u + 2][k] : r4[u][k], send = b1 ? r4[u][k] : r4[u + 2][k];
+                r2[u][k] = keep + __shfl_xor(send, 2);
+            }
+#pragma unroll
+        for (int k = 0; k < CINT; ++k) {
+            const float keep = b0 ? r2[1][k] : r2[0][k], send = b0 ? r2[0][k] : r2[1][k];
+            r1[k] = keep + __shfl_xor(send, 1);
+        }
+        const unsigned row = base + lane;                   // = base + pl * 8 + cv
+        if (row < rows) {
+            const unsigned b = dS.div(row), sp = row - b * (unsigned)S;
+#pragma unroll
+            for (int k = 0; k < CINT; ++k)
+                if (k < Cin) dx[((i64)b * Cin + k) * S + sp] = r1[k];
+        }
+    }
+}
+template <typename T, int CINT, int NJ>
+static void stem_input_grad_launch(const void* dout, const float* w, const float* coef, int B, int Cin, i64 S, int C0, float* dx,
+                                   hipStream_t s) {
+    const i64 tiles = ((i64)B * S + 63) / 64;
+    i64 bx = (tiles + 3) / 4;
+    if (bx > 2048) bx = 2048;                               // 256 CUs x 8 workgroups of four waves; the tiles are walked grid-stride
+    hipLaunchKernelGGL((stem_input_grad_kernel<T, CINT, NJ>), dim3((unsigned)bx), dim3(256), 0, s, (const T*)dout, w, coef, B, Cin, S,
+                       C0, dx);
+}
+template <int CINT>
+static int stem_input_grad_dispatch(const void* dout, const float* w, const float* coef, int B, int Cin, i64 S, int C0, float* dx,
+                                    int dtype, hipStream_t s) {
+    const int per = 8 * (dtype == DWN_BF16 ? 8 : 4);        // channels one row group covers per 16-byte load
+    const int nj = (C0 + per - 1) / per;
+    if (nj == 1) {
+        DISPATCH_T(dtype, (stem_input_grad_launch<bf16_t, CINT, 1>(dout, w, coef, B, Cin, S, C0, dx, s)),
+                   (stem_input_grad_launch<float, CINT, 1>(dout, w, coef, B, Cin, S, C0, dx, s)));
+    } else if (nj == 2) {
+        DISPATCH_T(dtype, (stem_input_grad_launch<bf16_t, CINT, 2>(dout, w, coef, B, Cin, S, C0, dx, s)),
+                   (stem_input_grad_launch<float, CINT, 2>(dout, w, coef, B, Cin, S, C0, dx, s)));
+    } else {
+        return dwn_set_error(-4, "stem_input_grad: more than 128 (bf16) / 64 (fp32) stem channels not built");
+    }
+    DWN_CHECK_LAUNCH();
+    return 0;
+}
+int k_stem_input_grad(const void* dout, const float* w, const float* coef, int B, int Cin, i64 S, int C0, float* dx, int dtype,
+                      hipStream_t s) {
+    if (Cin > STEM_MAXCIN) return dwn_set_error(-4, "stem: in_channels > 8 not built");
+    if ((i64)B * S >= (1ll << 31) - 64) return dwn_set_error(-4, "stem: more than 2^31 rows");
+    if (Cin <= 5) return stem_input_grad_dispatch<5>(dout, w, coef, B, Cin, S, C0, dx, dtype, s);
+    return stem_input_grad_dispatch<8>(dout, w, coef, B, Cin, S, C0, dx, dtype, s);
+}
 
 
 // ------------------------------------------------------------------------------------------------

@@ -24,6 +24,9 @@ int k_bn_finalize_eval(const float* gamma, const float* beta, const float* rm, c
                        float* coef, int C, hipStream_t s);
 int k_bn_bwd_finalize(const double* stats, double count, const float* coef, float* dgamma, float* dbeta, float* abc,
                       int C, hipStream_t s);
+// frozen statistics (dwn.h DWN_BN_FROZEN): abc = (scale, 0, 0), dgamma / dbeta from the same sums; job.count is not read
+int k_bn_bwd_finalize_frozen(const double* stats, const float* coef, float* dgamma, float* dbeta, float* abc, int C, hipStream_t s);
+int k_bn_bwd_finalize_frozen2(BnBwdJob j0, BnBwdJob j1, hipStream_t s);
 // BatchNorm-1 statistics from the Gram matrix of the block input (y1 never materialised; dwn_elementwise.hip)
 int k_bn1_gram_finalize(const double* gram, const float* w1, int E, int Cin, double count, const float* gamma, const float* beta,
                         float* rm, float* rv, long long* nbt, float momentum, float eps, float* coef, double* sc_stats, int dtype,
@@ -41,6 +44,10 @@ int k_stem_bwd_acc(const void* dout, const float* x, const double* xmom, double 
                    double* acc, int dtype, hipStream_t s);
 int k_stem_bwd_finalize(const double* acc, const double* xmom, const float* w, const float* coef, double count, float* dgamma,
                         float* dbeta, float* dw, int C0, int Cin, hipStream_t s);
+int k_stem_bwd_finalize_frozen(const double* acc, const float* w, const float* coef, float* dgamma, float* dbeta, float* dw,
+                               int C0, int Cin, hipStream_t s);
+int k_stem_input_grad(const void* dout, const float* w, const float* coef, int B, int Cin, i64 S, int C0, float* dx, int dtype,
+                      hipStream_t s);
 int stem_moment_count();
 int stem_acc_stride();
 int k_shortcut_stats(const LoadDesc& xin, const ResGeom& gm, double* stats, int dtype, hipStream_t s);

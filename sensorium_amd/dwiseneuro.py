@@ -12,7 +12,8 @@ under ``torch.autocast`` (the reference trains under fp16 autocast, src/argus_mo
 autocast both select the bf16 path here) or when ``compute_dtype=torch.bfloat16`` is set explicitly.
 
 Constraints of the HIP path (raised loudly, no fallback): channel counts multiples of 8, spatial_kernel 3,
-temporal_kernel 3 or 5, CUDA/HIP tensors only, backward only in training mode.
+temporal_kernel 3 or 5, CUDA/HIP tensors only.  Backward: in training mode (batch statistics), and in eval mode with frozen
+BatchNorm statistics when the input requires a gradient or ``freeze_batchnorm()`` is on (input gradient at the stem: eval only).
 """
 from __future__ import annotations
 
@@ -179,7 +180,8 @@ class InvertedResidual3d(nn.Module):
         b, t, h, w, _ = x.shape
         geom = self.geometry(pe, t, h, w, x.device)
         drop = self.drop_path.sample(b, x.device)
-        return ops.BlockFn.apply(x, drop, self, geom, dtype, x_has_pe, out_pe, *self.parameters_in_kernel_order())
+        mode = ops.bn_mode(self.conv_pw[1].bn.training, x)
+        return ops.BlockFn.apply(x, drop, self, geom, dtype, x_has_pe, out_pe, mode, *self.parameters_in_kernel_order())
 
 
 class ShuffleLayer(nn.Module):
@@ -197,7 +199,8 @@ class ShuffleLayer(nn.Module):
 
     def forward(self, x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
         drop = self.drop_path.sample(x.shape[0], x.device)
-        return ops.CortexFn.apply(x, drop, self, dtype, self.conv.weight, self.bn.bn.weight, self.bn.bn.bias,
+        mode = ops.bn_mode(self.bn.bn.training, x)
+        return ops.CortexFn.apply(x, drop, self, dtype, mode, self.conv.weight, self.bn.bn.weight, self.bn.bn.bias,
                                   self.bn_sc.bn.weight, self.bn_sc.bn.bias)
 
 
@@ -283,7 +286,7 @@ class DepthwiseCore(nn.Module):
             s = blk.spatial_stride
             h, w = (h - 1) // s + 1, (w - 1) // s + 1
         tables = [blk.geometry(pe, t, hw[0], hw[1], x.device)[:3] for pe, blk, hw in zip(pes, blks, sizes)]
-        x = ops.StemFn.apply(x, self.stem[0].weight, bn.weight, bn.bias, self, dtype, tables[0])
+        x = ops.StemFn.apply(x, self.stem[0].weight, bn.weight, bn.bias, self, dtype, tables[0], ops.bn_mode(bn.training, x))
         for i, (pe, blk) in enumerate(zip(pes, blks)):
             x = blk(x, pe, dtype, True, tables[i + 1] if i + 1 < len(blks) else None)
         return x
@@ -310,6 +313,7 @@ class DwiseNeuro(nn.Module):
         super().__init__()
         self.compute_dtype = compute_dtype
         self.fp32_eval_products = "bf16x3"     # see set_fp32_eval_products
+        self.bn_frozen_finetune = False        # see freeze_batchnorm
         self.core = DepthwiseCore(in_channels=in_channels, features=core_features, spatial_strides=spatial_strides,
                                   spatial_kernel=spatial_kernel, temporal_kernel=temporal_kernel,
                                   expansion_ratio=expansion_ratio, se_reduce_ratio=se_reduce_ratio,
@@ -337,6 +341,16 @@ class DwiseNeuro(nn.Module):
                 m._dwn_fp32_native = mode == "native"
         return self
 
+    def freeze_batchnorm(self, flag: bool = True) -> "DwiseNeuro":
+        """Fine-tuning with frozen BatchNorm statistics.  An eval-mode forward (``model.eval()``) with autograd recording normally
+        keeps what a backward needs only when its *input* requires a gradient (receptive fields, most-exciting inputs); with this
+        switch on it does so for plain data too, and ``backward()`` leaves the parameter gradients in ``.grad`` (or the flat
+        all-reduce buckets) exactly as a training step does — BatchNorm normalises with the running statistics and does not
+        update them, DropPath / Dropout are the identity as in eval.  ``no_grad`` forwards are not affected.
+        (C-ABI: ``training = DWN_BN_FROZEN`` of dwn_stem_args / dwn_block_args / dwn_cortex_args.)"""
+        self.bn_frozen_finetune = bool(flag)
+        return self
+
     def _draw_drop_paths(self, batch: int, device) -> None:
         """One draw for every stochastic-depth layer of this forward pass (12 layers: 2 small launches instead of 24).  Same
         distribution as DropPath.sample: factor = Bernoulli(keep) / keep per sample (0 where keep == 0: no 0/0)."""
@@ -361,9 +375,14 @@ class DwiseNeuro(nn.Module):
         if self.training:
             self._draw_drop_paths(x.shape[0], x.device)
         dtype = _select_dtype(self.compute_dtype)
-        x = self.core(x, dtype)                                   # [B,T,h,w,C]
-        x = ops.PoolFn.apply(x)                                   # [B,T,C]
-        return self.cortex(x, dtype)
+        # eval: ONE BatchNorm mode for the whole forward, decided from the model's input (an inner activation requires grad whenever
+        # a parameter does): frozen statistics with a backward if the input needs a gradient or freeze_batchnorm() is on, else eval
+        mode = None if self.training else (
+            ops.L.BN_FROZEN if ops.wants_frozen(x, getattr(self, "bn_frozen_finetune", False)) else ops.L.BN_EVAL)
+        with ops.bn_mode_scope(mode):
+            x = self.core(x, dtype)                               # [B,T,h,w,C]
+            x = ops.PoolFn.apply(x)                               # [B,T,C]
+            return self.cortex(x, dtype)
 
     def forward(self, x: torch.Tensor, index: Optional[int] = None):
         feats = self.trunk(x)

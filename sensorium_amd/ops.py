@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import threading
 from typing import Optional
 
 import numpy as np
@@ -61,6 +62,53 @@ def _f32_products(mod, inference_readout: bool = False) -> int:
     if inference_readout:               # the readout's C struct has no training flag: the caller says what this forward is
         return L.F32_NATIVE if native else L.F32_SPLIT3
     return L.F32_NATIVE if native else L.F32_AUTO
+
+
+# ------------------------------------------------------------------------------------------------
+# BatchNorm mode of a forward (include/dwn.h DWN_BN_*)
+# ------------------------------------------------------------------------------------------------
+_EVAL_BACKWARD_ERROR = "sensorium_amd: backward through eval-mode BatchNorm is not built"
+
+
+class _BnModeState(threading.local):
+    override: Optional[int] = None      # set by DwiseNeuro.trunk for the modules it calls: the model decides once, from ITS input
+
+
+_BN_MODE = _BnModeState()
+
+
+class bn_mode_scope:
+    """``with bn_mode_scope(mode):`` — the eval-mode modules called inside take ``mode`` (L.BN_EVAL or L.BN_FROZEN) instead of
+    deciding from their own input.  DwiseNeuro uses it so that a whole forward runs in one mode: an inner activation requires
+    grad whenever a parameter does, which says nothing about what the caller wants."""
+
+    def __init__(self, mode: Optional[int]):
+        self.mode = mode
+
+    def __enter__(self):
+        self.prev, _BN_MODE.override = _BN_MODE.override, self.mode
+        return self
+
+    def __exit__(self, *exc):
+        _BN_MODE.override = self.prev
+        return False
+
+
+def wants_frozen(x: torch.Tensor, switch: bool = False) -> bool:
+    """Does an eval-mode forward of ``x`` keep what a backward needs?  Only when autograd is recording AND (the input itself needs
+    a gradient, or the caller asked for frozen-statistics fine-tuning).  Everything else — ``no_grad`` predictors, validation,
+    hipGraph capture, eval forwards of plain data — stays on the eval kernels."""
+    return torch.is_grad_enabled() and (bool(x.requires_grad) or switch)
+
+
+def bn_mode(training: bool, x: torch.Tensor) -> int:
+    """The BatchNorm mode of one module call; evaluated in the module's ``forward`` (inside an autograd Function grad mode is
+    off and says nothing)."""
+    if training:
+        return L.BN_TRAIN
+    if _BN_MODE.override is not None:
+        return _BN_MODE.override
+    return L.BN_FROZEN if wants_frozen(x) else L.BN_EVAL
 
 
 def _ddp_flush() -> None:
@@ -154,10 +202,12 @@ class StemFn(torch.autograd.Function):
     Returns the channels-last activation [B,T,H,W,C0] in the compute dtype."""
 
     @staticmethod
-    def forward(ctx, x, weight, gamma, beta, mod, dtype, pe=None):
+    def forward(ctx, x, weight, gamma, beta, mod, dtype, pe=None, mode=None):
         _require_gpu(x, "StemFn")
         conv, bn = mod.stem[0], mod.stem[1].bn
         _check_bn(bn)
+        if mode is None:             # direct callers: training -> batch statistics, eval -> running statistics, no backward
+            mode = int(bn.training)
         x = x.contiguous().float()
         B, Cin, T, H, W = x.shape
         C0 = weight.shape[0]
@@ -167,7 +217,7 @@ class StemFn(torch.autograd.Function):
         # the input moments (sum x, sum x x^T): what the backward needs instead of the raw conv output (never materialised)
         xmom = torch.empty(72, dtype=torch.float64, device=dev)
         a = L.StemArgs()
-        a.dtype = _DT[dtype]; a.training = int(bn.training); a.B = B; a.Cin = Cin; a.C0 = C0; a.S = T * H * W
+        a.dtype = _DT[dtype]; a.training = mode; a.B = B; a.Cin = Cin; a.C0 = C0; a.S = T * H * W
         a.eps = bn.eps; a.momentum = bn.momentum
         a.x = x.data_ptr(); a.w = weight.data_ptr(); a.bn = _bn_struct(bn, coef)
         a.out = out.data_ptr(); a.xmom = xmom.data_ptr()
@@ -177,32 +227,44 @@ class StemFn(torch.autograd.Function):
         ws = _ws(L.lib.dwn_stem_workspace_bytes(C.byref(a)), dev)
         a.ws = ws.data_ptr(); a.ws_bytes = ws.numel()
         L.check(L.lib.dwn_stem_forward(C.byref(a), dev.index, _stream(dev)), "dwn_stem_forward")
-        ctx.mod = mod; ctx.dtype = dtype; ctx.was_training = bn.training
+        ctx.mod = mod; ctx.dtype = dtype; ctx.mode = mode
         ctx.save_for_backward(x, weight, xmom, coef)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, weight, xmom, coef = ctx.saved_tensors
-        if not ctx.was_training:
-            raise RuntimeError("sensorium_amd: backward through eval-mode BatchNorm is not built")
+        if ctx.mode == L.BN_EVAL:
+            raise RuntimeError(_EVAL_BACKWARD_ERROR)
         bn = ctx.mod.stem[1].bn
         dev = x.device
         B, Cin, T, H, W = x.shape
         C0 = weight.shape[0]
         dout = dout.contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            if ctx.mode != L.BN_FROZEN:
+                raise RuntimeError("sensorium_amd: the gradient w.r.t. the model input is built for frozen BatchNorm statistics "
+                                   "(model.eval()) only, not through batch statistics")
+            dx = torch.empty_like(x)
+            g = L.StemInputGradArgs()
+            g.dtype = _DT[ctx.dtype]; g.training = ctx.mode; g.B = B; g.Cin = Cin; g.C0 = C0; g.S = T * H * W
+            g.w = weight.data_ptr(); g.coef = coef.data_ptr(); g.dout = dout.data_ptr(); g.dx = dx.data_ptr()
+            L.check(L.lib.dwn_stem_input_grad(C.byref(g), dev.index, _stream(dev)), "dwn_stem_input_grad")
+            if not any(ctx.needs_input_grad[1:4]):      # input gradient only (parameters frozen by the caller)
+                return dx, None, None, None, None, None, None, None
         dw = grad_out(ctx.mod.stem[0].weight)
         dgamma = grad_out(bn.weight)
         dbeta = grad_out(bn.bias)
         a = L.StemArgs()
-        a.dtype = _DT[ctx.dtype]; a.training = 1; a.B = B; a.Cin = Cin; a.C0 = C0; a.S = T * H * W
+        a.dtype = _DT[ctx.dtype]; a.training = ctx.mode; a.B = B; a.Cin = Cin; a.C0 = C0; a.S = T * H * W
         a.eps = bn.eps; a.momentum = bn.momentum
         a.x = x.data_ptr(); a.w = weight.data_ptr(); a.bn = _bn_struct(bn, coef, dgamma, dbeta)
         a.xmom = xmom.data_ptr(); a.dout = dout.data_ptr(); a.dw = dw.data_ptr()
         ws = _ws(L.lib.dwn_stem_workspace_bytes(C.byref(a)), dev)
         a.ws = ws.data_ptr(); a.ws_bytes = ws.numel()
         L.check(L.lib.dwn_stem_backward(C.byref(a), dev.index, _stream(dev)), "dwn_stem_backward")
-        return None, dw, dgamma, dbeta, None, None, None
+        return dx, dw, dgamma, dbeta, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------------------
@@ -249,7 +311,7 @@ class BlockFn(torch.autograd.Function):
     """x -> InvertedResidual3d(x + PositionalEncoding3d) (dwiseneuro.py:136-144, 184-192), channels-last."""
 
     @staticmethod
-    def forward(ctx, x, drop_scale, blk, geom, dtype, x_has_pe, out_pe, *params):
+    def forward(ctx, x, drop_scale, blk, geom, dtype, x_has_pe, out_pe, mode, *params):
         _require_gpu(x, "BlockFn")
         x = x.contiguous()
         dev = x.device
@@ -260,7 +322,8 @@ class BlockFn(torch.autograd.Function):
         bns = blk.bn_modules()
         for bn in bns:
             _check_bn(bn)
-        training = bns[0].training
+        # mode: include/dwn.h DWN_BN_*, decided by the module's forward (bn_mode: grad mode is not visible in here)
+        training = mode          # the C struct's `training` field
         f32 = dict(dtype=torch.float32, device=dev)
         y2 = torch.empty(B, T, Hout, Wout, Cmid, dtype=dtype, device=dev)
         z3 = torch.empty_like(y2)
@@ -286,12 +349,12 @@ class BlockFn(torch.autograd.Function):
         ws = _ws(L.lib.dwn_block_workspace_bytes(C.byref(a), 0), dev)
         a.ws = ws.data_ptr(); a.ws_bytes = ws.numel()
         L.check(L.lib.dwn_block_forward(C.byref(a), dev.index, _stream(dev)), "dwn_block_forward")
-        ctx.blk = blk; ctx.geom = geom; ctx.dtype = dtype; ctx.was_training = training
+        ctx.blk = blk; ctx.geom = geom; ctx.dtype = dtype; ctx.mode = mode
         if getattr(blk, "_capture", False):        # test hook: expose the raw intermediates
             blk._captured = dict(y1=y1, y2=y2, y3=y3, y4=y4, z3=z3, coefs=coefs, **saved)
         ctx.has_drop = drop_scale is not None
         # the block input *including* its positional encoding is what backward needs
-        if not training:              # no backward through eval-mode BatchNorm: nothing to keep
+        if mode == L.BN_EVAL:         # no backward through eval-mode BatchNorm: nothing to keep
             return out
         tensors = [x if x_has_pe else a0, y1, y2, y3, y4, *coefs, saved["pmean"], saved["hidpre"], saved["gate"], z3]
         if drop_scale is not None:
@@ -301,8 +364,8 @@ class BlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        if not ctx.was_training:
-            raise RuntimeError("sensorium_amd: backward through eval-mode BatchNorm is not built")
+        if ctx.mode == L.BN_EVAL:
+            raise RuntimeError(_EVAL_BACKWARD_ERROR)
         blk, dtype = ctx.blk, ctx.dtype
         t = ctx.saved_tensors
         x, y1, y2, y3, y4 = t[:5]
@@ -316,7 +379,7 @@ class BlockFn(torch.autograd.Function):
         Hout, Wout = y2.shape[2], y2.shape[3]
         Cmid, Cout = blk.mid_features, blk.out_features
         f32 = dict(dtype=torch.float32, device=dev)
-        a = _block_args(blk, ctx.geom, x, dtype, True, coefs, saved, drop_scale, True, None)
+        a = _block_args(blk, ctx.geom, x, dtype, ctx.mode, coefs, saved, drop_scale, True, None)
         a.y1 = _ptr(y1); a.y2 = y2.data_ptr(); a.y3 = y3.data_ptr(); a.y4 = y4.data_ptr()      # (y1 is None on a y1-free block)
         a.z3 = z3.data_ptr()
         bns = blk.bn_modules()
@@ -353,7 +416,7 @@ class BlockFn(torch.autograd.Function):
         _ddp_flush()            # this block's kernels are queued: a good moment for the host to start pending gradient exchanges
         grads = (dw_pw, dg[0], db[0], dw_dws, dg[1], db[1], dw_dwt, dg[2], db[2], dse_wr, dse_br, dse_we, dse_be,
                  dw_pwl, dg[3], db[3], dg[4], db[4])
-        return (dx, None, None, None, None, None, None) + grads
+        return (dx, None, None, None, None, None, None, None) + grads
 
 
 # ------------------------------------------------------------------------------------------------
@@ -392,7 +455,7 @@ class CortexFn(torch.autograd.Function):
     """ShuffleLayer.forward (dwiseneuro.py:228-234) on [B,T,C_in] -> [B,T,C]."""
 
     @staticmethod
-    def forward(ctx, x, drop_scale, layer, dtype, weight, g, b, gsc, bsc):
+    def forward(ctx, x, drop_scale, layer, dtype, mode, weight, g, b, gsc, bsc):
         _require_gpu(x, "CortexFn")
         x = x.contiguous()
         dev = x.device
@@ -400,13 +463,12 @@ class CortexFn(torch.autograd.Function):
         Cc = layer.out_features
         bn, bnsc = layer.bn.bn, layer.bn_sc.bn
         _check_bn(bn); _check_bn(bnsc)
-        training = bn.training
         y = torch.empty(B, T, Cc, dtype=dtype, device=dev)
         out = torch.empty_like(y)
         coef = torch.empty(4 * Cc, dtype=torch.float32, device=dev)
         coefsc = torch.empty(4 * Cc, dtype=torch.float32, device=dev)
         a = L.CortexArgs()
-        a.dtype = _DT[dtype]; a.training = int(training); a.B = B; a.T = T; a.Cin = Cin; a.C = Cc
+        a.dtype = _DT[dtype]; a.training = mode; a.B = B; a.T = T; a.Cin = Cin; a.C = Cc
         a.groups = layer.groups; a.eps = bn.eps; a.momentum = bn.momentum
         a.x = x.data_ptr(); a.out = out.data_ptr(); a.y = y.data_ptr(); a.w = weight.data_ptr()
         a.bn = _bn_struct(bn, coef); a.bnsc = _bn_struct(bnsc, coefsc); a.drop_scale = _ptr(drop_scale)
@@ -414,7 +476,7 @@ class CortexFn(torch.autograd.Function):
         ws = _ws(L.lib.dwn_cortex_workspace_bytes(C.byref(a), 0), dev)
         a.ws = ws.data_ptr(); a.ws_bytes = ws.numel()
         L.check(L.lib.dwn_cortex_forward(C.byref(a), dev.index, _stream(dev)), "dwn_cortex_forward")
-        ctx.layer = layer; ctx.dtype = dtype; ctx.was_training = training; ctx.has_drop = drop_scale is not None
+        ctx.layer = layer; ctx.dtype = dtype; ctx.mode = mode; ctx.has_drop = drop_scale is not None
         tensors = [x, y, coef, coefsc, weight]
         if drop_scale is not None:
             tensors.append(drop_scale)
@@ -423,8 +485,8 @@ class CortexFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        if not ctx.was_training:
-            raise RuntimeError("sensorium_amd: backward through eval-mode BatchNorm is not built")
+        if ctx.mode == L.BN_EVAL:
+            raise RuntimeError(_EVAL_BACKWARD_ERROR)
         layer, dtype = ctx.layer, ctx.dtype
         t = ctx.saved_tensors
         x, y, coef, coefsc, weight = t[:5]
@@ -439,7 +501,7 @@ class CortexFn(torch.autograd.Function):
         dw = grad_out(layer.conv.weight)             # cleared by dwn_cortex_backward's prep launch
         dx = torch.empty_like(x)
         a = L.CortexArgs()
-        a.dtype = _DT[dtype]; a.training = 1; a.B = B; a.T = T; a.Cin = Cin; a.C = Cc
+        a.dtype = _DT[dtype]; a.training = ctx.mode; a.B = B; a.T = T; a.Cin = Cin; a.C = Cc
         a.groups = layer.groups; a.eps = bn.eps; a.momentum = bn.momentum
         a.x = x.data_ptr(); a.y = y.data_ptr(); a.w = weight.data_ptr()
         a.bn = _bn_struct(bn, coef, dgm, dbm); a.bnsc = _bn_struct(bnsc, coefsc, dgs, dbs)
@@ -448,7 +510,7 @@ class CortexFn(torch.autograd.Function):
         ws = _ws(L.lib.dwn_cortex_workspace_bytes(C.byref(a), 1), dev)
         a.ws = ws.data_ptr(); a.ws_bytes = ws.numel()
         L.check(L.lib.dwn_cortex_backward(C.byref(a), dev.index, _stream(dev)), "dwn_cortex_backward")
-        return dx, None, None, None, dw, dgm, dbm, dgs, dbs
+        return dx, None, None, None, None, dw, dgm, dbm, dgs, dbs
 
 
 # ------------------------------------------------------------------------------------------------
