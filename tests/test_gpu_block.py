@@ -16,10 +16,10 @@ from oracle import dwiseneuro_oracle as orc  # noqa: E402
 from tests.gpu_helpers import dev, rel  # noqa: E402
 
 
-def make_block(cin, cout, stride, expansion, se_ratio, seed):
+def make_block(cin, cout, stride, expansion, se_ratio, seed, temporal_kernel=5):
     from sensorium_amd.dwiseneuro import InvertedResidual3d, PositionalEncoding3d
     torch.manual_seed(seed)
-    blk = InvertedResidual3d(cin, cout, spatial_kernel=3, temporal_kernel=5, spatial_stride=stride,
+    blk = InvertedResidual3d(cin, cout, spatial_kernel=3, temporal_kernel=temporal_kernel, spatial_stride=stride,
                              expansion_ratio=expansion, se_reduce_ratio=se_ratio)
     pe = PositionalEncoding3d(cin)
     g = torch.Generator().manual_seed(seed)
@@ -106,8 +106,13 @@ def _train_params():
 
 @pytest.mark.parametrize("case,dtype,drop,y1", _train_params())
 def test_block_train_forward_backward(case, dtype, drop, y1):
+    _train_forward_backward(case, dtype, drop, y1)
+
+
+def _train_forward_backward(case, dtype, drop, y1, temporal_kernel=5):
     cin, cout, stride, exp, ser, B, T, H, W = case
-    blk, pe = make_block(cin, cout, stride, exp, ser, seed=cin + stride)
+    blk, pe = make_block(cin, cout, stride, exp, ser, seed=cin + stride, temporal_kernel=temporal_kernel)
+    assert blk.state_dict()["temp_covn_dw.0.weight"].shape[2] == temporal_kernel
     sd = {"blk." + k: v.clone() for k, v in blk.state_dict().items()}
     torch.manual_seed(1)
     x = torch.randn(B, T, H, W, cin) * 1.5 + 0.3
@@ -178,8 +183,12 @@ def test_block_eval_forward(dtype, case_id):
     """Eval-mode forward.  The cases with 64 / 128 input channels take, in bf16, the y1-recomputing stencil
     (dwn_dw_spatial_fwd_rc: conv_pw never runs as its own pass) — except case 14, whose 130-pixel rows fit neither register
     geometry of that kernel and must fall back to conv_pw + stencil; case 1 and every fp32 run take the materialised path."""
-    cin, cout, stride, exp, ser, B, T, H, W = CASES[case_id]
-    blk, pe = make_block(cin, cout, stride, exp, ser, seed=3)
+    _eval_forward(CASES[case_id], dtype)
+
+
+def _eval_forward(case, dtype, temporal_kernel=5):
+    cin, cout, stride, exp, ser, B, T, H, W = case
+    blk, pe = make_block(cin, cout, stride, exp, ser, seed=3, temporal_kernel=temporal_kernel)
     sd = {"blk." + k: v.clone().double() if v.is_floating_point() else v.clone() for k, v in blk.state_dict().items()}
     x = torch.randn(B, T, H, W, cin, generator=torch.Generator().manual_seed(2))
     a0 = x.double() + orc.pe_table(cin, T, H, W, pe.inv_freq, torch.float64)
@@ -191,6 +200,24 @@ def test_block_eval_forward(dtype, case_id):
     assert rel(out.float(), ref) < (1e-3 if dtype == torch.float32 else 4e-2)
     for k, v in blk.state_dict().items():      # eval must not touch the BN buffers
         assert torch.equal(v, before[k]), k
+
+
+# temporal_kernel = 3: the second kernel size dwn_block_forward accepts (fwd<T,3>, bwd_rc<T,3> and the eval epilogue), through a whole
+# block against the oracle, with the bodies — assertions and bounds — of the tests above.  T = 1 .. 8: fewer frames than the kernel,
+# exactly one unrolled batch, several; ragged and whole channel slices; the y1-free bf16 path (cases 3, 4) and the 256-channel blocks
+KT3_CASES = [CASES[1], CASES[8], CASES[3], CASES[4], CASES[16], CASES[5], CASES[7]]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["float32", "bfloat16"])
+@pytest.mark.parametrize("case", KT3_CASES, ids=lambda c: "-".join(map(str, c)))
+def test_block_temporal_kernel_3_train_forward_backward(case, dtype):
+    _train_forward_backward(case, dtype, False, "auto", temporal_kernel=3)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["float32", "bfloat16"])
+@pytest.mark.parametrize("case", KT3_CASES, ids=lambda c: "-".join(map(str, c)))
+def test_block_temporal_kernel_3_eval_forward(case, dtype):
+    _eval_forward(case, dtype, temporal_kernel=3)
 
 
 @pytest.mark.parametrize("path", ["old", "new"])

@@ -1,8 +1,14 @@
-"""Row-walk spatial depth-wise backward kernels (sensorium_amd/csrc/dwn_dwbwd.hip; reference op: the backward of
-src/models/dwiseneuro.py:96-102) against the library's second implementation (dwn_dw_spatial_bwd_args.impl = 1: the pair /
-generic kernels), through the C-ABI entry dwn_dw_spatial_bwd.  Those kernels are pinned to the oracle by tests/test_gpu_block.py; here
-the two implementations must agree: dh1 BIT-identical (same dot2 order; stride 2 with bf16-representable stencil weights,
-which is what the dot2 kernels see anyway), dW and the BatchNorm-backward sums to summation order / bf16 rounding of z1."""
+"""Spatial depth-wise backward kernels of sensorium_amd/csrc/dwn_dwbwd.hip (reference op: the backward of
+src/models/dwiseneuro.py:90-102) through the C-ABI entry dwn_dw_spatial_bwd, in two parts:
+
+* the row-walk kernels on a stored y1 against the library's second implementation (dwn_dw_spatial_bwd_args.impl = 1: the pair /
+  generic kernels): dh1 BIT-identical at stride 1 (same dot2 order) and within an ulp on a per-mille share at stride 2, dW and the
+  BatchNorm-backward sums to summation order / bf16 rounding of z1 (kernel against kernel: what the two share is pinned to the
+  oracle by tests/test_gpu_block.py);
+* the rebuilt-y1 kernels (y1 recomputed from the block input on the matrix cores) against the float64 backward of
+  conv_pw -> BatchNorm-1 + SiLU -> 3x3 stencil (tests/dw_reference.py, pinned to the oracle by tests/test_dw_reference_cpu.py),
+  beside the stored-y1 form on the same data: dh1, the 9-tap weight gradient and the two sums, both strides, Cin 64 and 128, band
+  heights, 200 repeated launches, and the shapes the rebuilt form refuses."""
 import ctypes as C
 
 import pytest
@@ -26,7 +32,9 @@ def _desc(p, ld, **kw):
 
 
 def _both(planes, Hin, Win, Cc, stride, rows_band=0, seed=0):
-    """"new" = the product kernels (stride 1: chained rows with LDS-DMA y1; stride 2: banded row walk), "old" = impl 1."""
+    """One stored-y1 backward through both implementations on the same seeded bf16 operands (outputs pre-filled with NaN, dW and
+    the statistics zeroed): "new" = the product kernels (stride 1: chained rows with LDS-DMA y1; stride 2: banded row walk),
+    "old" = impl 1.  Returns ((dh1, dW, sums) old, (dh1, dW, sums) new)."""
     d = dev()
     s = torch.cuda.current_stream().cuda_stream
     g = torch.Generator(device=d); g.manual_seed(seed)

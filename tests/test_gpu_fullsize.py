@@ -6,7 +6,8 @@
 * the weight-gradient GEMM on small-integer data is exact;
 * eval forward is per-sample independent: a batch slice run alone equals the slice of the full-batch run;
 * the backward pass is linear in the loss scale: scaling the loss by 2 scales every gradient by 2 (a power-of-two
-  scale is exact in bf16/fp32, so only the atomic summation order may differ).
+  scale is exact in bf16/fp32, so only the atomic summation order may differ);
+* the depth-wise stencils (spatial and temporal, forward and backward) on small-integer data are exact.
 """
 import ctypes as C
 
@@ -246,3 +247,79 @@ def test_fullsize_depthwise_stencils_exact(L, geom):
 def test_depthwise_stencils_exact_other_plane_widths(L, geom):
     """The narrower plane widths (several planes side by side in one tile) with a ragged plane count."""
     _exact_stencil_case(L, 131, *geom)
+
+
+# ---- temp_covn_dw at the metric batch, exact-integer data ------------------------------------------------------------------------------
+# The temporal forward and the y3-recomputing backward (DWN_LD_PLAIN, what the block backward runs; src/models/dwiseneuro.py:105-111)
+# of blocks 0, 4 and 8 at B = 32, T = 32, on data built like the spatial cases above so that every intermediate is a small integer:
+#   y2 in 0 .. 3; BatchNorm-2 scale 1, shift 17  ->  z2 = h = y2 + 17 in 17 .. 20 and SiLU' = 1 (1 + exp(-h) rounds to 1.0f: see above)
+#   exactly three (kt = 5) / two (kt = 3) non-zero taps of +-1 per channel  ->  |y3| <= 60
+#   dh3 in {-1, 0, 1}, A1 = 1, A2 = 1, A3 = 0: dy3 = dh3 + y3, so the RECOMPUTED y3 matters  ->  |dy3| <= 61, |dh2| <= 183
+# bf16 holds all of them exactly, so y3 and dh2 must EQUAL float64 arithmetic on the same integers — what a tolerance cannot see: a wrong
+# frame at a boundary, an index that wraps at 2.6e8 elements, a lost atomic.
+def _exact_temporal_case(L, Bn, Tn, HW, E, kt, dtype):
+    from tests.dw_reference import _dwt
+    d = dev()
+    s = stream()
+    dt = L.DWN_BF16 if dtype == torch.bfloat16 else L.DWN_F32
+    g = torch.Generator(device="cuda").manual_seed(HW + E + kt)
+    M = Bn * Tn * HW
+    y2 = torch.randint(0, 4, (M, E), generator=g, device=d, dtype=torch.int8).to(dtype)
+    taps = torch.zeros(E, kt, device=d)
+    taps.scatter_(1, torch.rand(E, kt, generator=g, device=d).argsort(1)[:, :(3 if kt == 5 else 2)], 1.0)
+    taps = (taps * (torch.randint(0, 2, (E, kt), generator=g, device=d) * 2 - 1)).t().contiguous()        # [kt][E], +-1 / 0
+    dh3 = torch.randint(-1, 2, (M, E), generator=g, device=d, dtype=torch.int8).to(dtype)
+    ones, zeros = torch.ones(E, device=d), torch.zeros(E, device=d)
+    shift = torch.full((E,), 17.0, device=d)
+    # float64 reference on the integers (linear activation: z2 = h, SiLU' = 1)
+    h = (y2.double().view(Bn, Tn, HW, E) + 17.0).requires_grad_(True)
+    wd = taps.double().clone().requires_grad_(True)
+    y3_ref = _dwt(h, wd)
+    y3_ref.backward(dh3.double().view(Bn, Tn, HW, E) + y3_ref.detach())
+    y3_ref = y3_ref.detach().reshape(M, E)
+    dh2_ref = h.grad.reshape(M, E)
+    dw_ref = wd.grad.t().contiguous()                                                                   # [E][kt]
+    del h
+    assert float(y3_ref.abs().max()) <= 60 and float(dh2_ref.abs().max()) <= 183
+    # ---- forward
+    y3 = torch.full((M, E), float("nan"), dtype=dtype, device=d)
+    st = stats_buffer(E)
+    f = L.DwTemporalFwdArgs()
+    f.inp = load_desc(L, y2, E, v1=ones, v2=shift, act=1)
+    f.w = taps.data_ptr(); f.out = y3.data_ptr(); f.B = Bn; f.T = Tn; f.HW = HW; f.C = E; f.kt = kt; f.stats = st.data_ptr()
+    L.check(L.lib.dwn_dw_temporal_fwd(C.byref(f), dt, 0, s), "dwn_dw_temporal_fwd")
+    torch.cuda.synchronize()
+    assert torch.equal(y3.double(), y3_ref), "y3"
+    s0, s1 = read_stats(st, E)
+    # fp32 partial sums end at the workgroup (the replicas are doubles).  The persistent grid has at least 2 * 256 / slices workgroups per
+    # channel slice, so a workgroup sums at most 8192 elements of a channel (block 0: 16 rounds of 16 positions, 32 frames; fewer at the
+    # other widths).  sum y3: 8192 * 60 < 2^24: exact.  sum y3^2: 8192 * 3600 > 2^24: rounded
+    assert torch.equal(s0, y3_ref.sum(0)), "sum y3"
+    assert rel(s1, (y3_ref ** 2).sum(0)) < 1e-6, "sum y3^2"
+    del y3
+    # ---- backward, y3 recomputed
+    dh2 = torch.full((M, E), float("nan"), dtype=dtype, device=d)
+    dw = torch.zeros(E, kt, device=d)
+    st = stats_buffer(E)
+    b = L.DwTemporalBwdArgs()
+    b.dy = load_desc(L, dh3, E, v1=ones, v2=ones, v3=zeros); b.dy_kind = L.LD_PLAIN
+    b.y2 = load_desc(L, y2, E, v1=ones, v2=shift, v3=zeros, v4=ones)                    # mean 0, invstd 1: yhat2 = y2
+    b.w = taps.data_ptr(); b.dh2 = dh2.data_ptr(); b.dw = dw.data_ptr()
+    b.B = Bn; b.T = Tn; b.HW = HW; b.C = E; b.kt = kt; b.stats = st.data_ptr()
+    L.check(L.lib.dwn_dw_temporal_bwd(C.byref(b), dt, 0, s), "dwn_dw_temporal_bwd")
+    torch.cuda.synchronize()
+    assert torch.equal(dh2.double(), dh2_ref), "dh2"
+    s0, s1 = read_stats(st, E)
+    # sum dh2 (<= 183 per element) and sum dh2 * y2 (<= 549): 8192 * 549 < 2^24: exact
+    assert torch.equal(s0, dh2_ref.sum(0)), "sum dh2"
+    assert torch.equal(s1, (dh2_ref * y2.double()).sum(0)), "sum dh2 * y2"
+    # dW[k] = sum z2(t) dy3(t - k + P): terms up to 20 * 61, of one sign where the taps do not cancel; a workgroup's share is exact
+    # (8192 * 1220 < 2^24) but the workgroups add into one fp32 word per (channel, tap), |dW| up to 6e8 > 2^24: rounded
+    assert rel(dw, dw_ref) < 1e-6, "dW"
+
+
+@pytest.mark.parametrize("geom", [(576, 448, 5, torch.bfloat16), (144, 896, 5, torch.bfloat16), (40, 1792, 5, torch.bfloat16),
+                                  (576, 448, 3, torch.bfloat16), (40, 1792, 5, torch.float32)],
+                         ids=["block0", "block4", "block8", "block0-kt3", "block8-fp32"])
+def test_fullsize_temporal_depthwise_exact(L, geom):
+    _exact_temporal_case(L, B, T, *geom)
