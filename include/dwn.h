@@ -40,7 +40,8 @@ extern "C" {
 #define DWN_F32_SPLIT3 2
 /* BatchNorm mode: the `training` field of dwn_stem_args / dwn_block_args / dwn_cortex_args.
  * EVAL: normalise with the running statistics, keep nothing for a backward (dwn_*_backward returns -7).
- * TRAIN: batch statistics, running statistics and num_batches_tracked updated, intermediates saved, backward built.
+ * TRAIN: batch statistics, running statistics and num_batches_tracked updated, intermediates saved, backward built (the gradient
+ * w.r.t. the model input included: dwn_stem_backward_input).
  * FROZEN: normalise with the running statistics and do not touch them (as EVAL), take the training kernels and save the same
  * intermediates (as TRAIN), and run a backward in which BatchNorm is the fixed affine map it was in the forward:
  * dx = gamma * invstd_running * dy, dgamma = sum dy * xhat, dbeta = sum dy.  For input gradients (receptive fields, most-exciting
@@ -252,7 +253,8 @@ typedef struct dwn_stem_args {
 /* gradient of the stem's output w.r.t. its NCDHW fp32 input (dwn_stem_args has no dx): with BatchNorm as a fixed affine map,
  * dx[b][k][s] = sum_c w[c][k] * coef[c] * dout[b*S + s][c]   (coef[c] = gamma_c * invstd_c, the first row of dwn_bn.coef as the
  * forward wrote it).  One streaming pass over dout.  training must be DWN_BN_FROZEN: in DWN_BN_TRAIN the batch statistics add
- * terms in x (from xmom) that are not built — the call returns -7; DWN_BN_EVAL returns -7 like every backward.
+ * terms in x that need the finished sums of the parameter-gradient pass — this call returns -7 for it, and the training-mode
+ * input gradient comes from dwn_stem_backward_input (below); DWN_BN_EVAL returns -7 like every backward.
  * C0 a multiple of 8, at most 128 (bf16) / 64 (fp32); Cin <= 8. */
 typedef struct dwn_stem_input_grad_args {
     int dtype, training, B, Cin, C0; long long S;
@@ -425,6 +427,17 @@ size_t dwn_stem_workspace_bytes(const dwn_stem_args* a);
 int dwn_stem_forward(const dwn_stem_args* a, int device, void* stream);
 int dwn_stem_backward(const dwn_stem_args* a, int device, void* stream);
 int dwn_stem_input_grad(const dwn_stem_input_grad_args* a, int device, void* stream);
+/* dwn_stem_backward + the gradient w.r.t. the NCDHW fp32 input THROUGH the batch statistics, from one accumulation pass over
+ * dout (a->x, a->xmom, a->bn.coef as the training forward left them; a->ws sized by dwn_stem_workspace_bytes):
+ *   dx[b][k][s] = sum_c w[c][k] scale_c dout[b*S+s][c]  +  sum_j Q[k][j] (x[b][j][s] - xbar_j)  +  q0[k]
+ *   Q[k][j] = sum_c a2_c w[c][k] w[c][j],  a2_c = -scale_c invstd_c^2 (sum dout_c (z_c - mean_c)) / M,
+ *   q0[k]   = -(1/M) sum_c w[c][k] scale_c sum dout_c,                    M = B*S, z = W0 x.
+ * dgamma, dbeta, dw are what dwn_stem_backward writes (same launches, same bits under the deterministic build); then a
+ * one-workgroup finaliser forms Q, q0, xbar and one streaming pass over dout and x writes dx.
+ * training must be DWN_BN_TRAIN: DWN_BN_EVAL returns -7 like every backward, DWN_BN_FROZEN returns -7 too (its gradient is
+ * dwn_stem_backward + dwn_stem_input_grad).  dx: [B][Cin][S] fp32, written whole.  Null dx / x / xmom / dout / dw / ws: -1.
+ * The argument checks answer before the device is entered.  C0 and Cin as dwn_stem_input_grad. */
+int dwn_stem_backward_input(const dwn_stem_args* a, float* dx, int device, void* stream);
 size_t dwn_block_workspace_bytes(const dwn_block_args* a, int backward);
 int dwn_block_forward(const dwn_block_args* a, int device, void* stream);
 int dwn_block_backward(const dwn_block_args* a, int device, void* stream);

@@ -212,6 +212,7 @@ SYMBOLS = {
     "dwn_stem_forward": (c_i, [_P(StemArgs), c_i, c_p]),
     "dwn_stem_backward": (c_i, [_P(StemArgs), c_i, c_p]),
     "dwn_stem_input_grad": (c_i, [_P(StemInputGradArgs), c_i, c_p]),
+    "dwn_stem_backward_input": (c_i, [_P(StemArgs), c_p, c_i, c_p]),
     "dwn_block_workspace_bytes": (c_sz, [_P(BlockArgs), c_i]),
     "dwn_block_forward": (c_i, [_P(BlockArgs), c_i, c_p]),
     "dwn_block_backward": (c_i, [_P(BlockArgs), c_i, c_p]),
@@ -269,8 +270,8 @@ def _load():
     lib = C.CDLL(str(LIB_PATH), mode=getattr(os, "RTLD_NOW", 2))
     ab = bool(os.environ.get("DWN_LIB_PATH"))      # an explicitly chosen other build: a same-box A/B run of an older library
     for name, (restype, argtypes) in SYMBOLS.items():
-        if ab and name == "dwn_stem_input_grad" and not hasattr(lib, name):
-            continue                     # (A/B: a library from before the frozen-statistics mode; the training step does not call it)
+        if ab and name in ("dwn_stem_input_grad", "dwn_stem_backward_input") and not hasattr(lib, name):
+            continue                     # (A/B: a library from before the input gradients; the training step does not call them)
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

@@ -455,6 +455,37 @@ int dwn_stem_backward(const dwn_stem_args* a, int device, void* stream) {
     return k_stem_bwd_finalize(acc, a->xmom, a->w, a->bn.coef, (double)M, a->bn.dgamma, a->bn.dbeta, a->dw, a->C0, a->Cin, s);
 }
 
+// dwn_stem_backward in training mode + dx through the batch statistics (dwn.h).  The first three launches are dwn_stem_backward's,
+// argument for argument; Q, q0, x̄ (80 floats) go to the workspace's moment slot, which only the forward and the frozen backward
+// use — dwn_stem_workspace_bytes does not grow.
+int dwn_stem_backward_input(const dwn_stem_args* a, float* dx, int device, void* stream) {
+    g_err[0] = 0;                    // the argument checks need no device
+    if (!a || !dx) return dwn_set_error(-1, "stem_backward_input: null pointer (args, dx)");
+    if (a->training != DWN_BN_TRAIN)
+        return dwn_set_error(-7, "stem_backward_input: built for batch statistics (DWN_BN_TRAIN) only; the frozen-statistics input "
+                                 "gradient is dwn_stem_backward + dwn_stem_input_grad");
+    if (!a->x || !a->w || !a->bn.coef || !a->dout || !a->dw || !a->xmom || !a->ws)
+        return dwn_set_error(-1, "stem_backward_input: null pointer (x, w, bn.coef, dout, dw, xmom, ws)");
+    if (a->C0 <= 0 || a->C0 % 8 || a->Cin <= 0 || a->B <= 0 || a->S <= 0)
+        return dwn_set_error(-2, "stem_backward_input: C0 must be a positive multiple of 8; B, Cin, S positive");
+    if (a->dtype != DWN_F32 && a->dtype != DWN_BF16) return dwn_set_error(-2, "stem_backward_input: dtype");
+    if (a->C0 > (a->dtype == DWN_BF16 ? 128 : 64) || a->Cin > 8)
+        return dwn_set_error(-4, "stem_backward_input: more than 128 (bf16) / 64 (fp32) stem channels or 8 input channels not built");
+    ENTER(device);
+    hipStream_t s = (hipStream_t)stream;
+    Carver c(a->ws, a->ws_bytes);
+    double* mom = c.take<double>((size_t)DWN_NREP * stem_moment_count());
+    double* acc = c.take<double>((size_t)DWN_NREP * a->C0 * stem_acc_stride());
+    if (!c.ok()) return dwn_set_error(-6, "stem: workspace too small");
+    float* qx = reinterpret_cast<float*>(mom);
+    const i64 M = (i64)a->B * a->S;
+    TRY(k_zero(acc, (size_t)DWN_NREP * a->C0 * stem_acc_stride() * sizeof(double), s));
+    TRY(k_stem_bwd_acc(a->dout, a->x, a->xmom, (double)M, a->B, a->Cin, a->S, a->C0, acc, a->dtype, s));
+    TRY(k_stem_bwd_finalize(acc, a->xmom, a->w, a->bn.coef, (double)M, a->bn.dgamma, a->bn.dbeta, a->dw, a->C0, a->Cin, s));
+    TRY(k_stem_bwd_finalize_dx(acc, a->xmom, a->w, a->bn.coef, (double)M, qx, a->C0, a->Cin, s));
+    return k_stem_input_grad_train(a->dout, a->w, a->bn.coef, a->x, qx, a->B, a->Cin, a->S, a->C0, dx, a->dtype, s);
+}
+
 // dx of the stem with BatchNorm as a fixed affine map (dwn.h): one streaming pass over dout
 int dwn_stem_input_grad(const dwn_stem_input_grad_args* a, int device, void* stream) {
     g_err[0] = 0;
@@ -463,7 +494,8 @@ int dwn_stem_input_grad(const dwn_stem_input_grad_args* a, int device, void* str
         return dwn_set_error(-2, "stem_input_grad: C0 must be a positive multiple of 8; B, Cin, S positive");
     if (a->dtype != DWN_F32 && a->dtype != DWN_BF16) return dwn_set_error(-2, "stem_input_grad: dtype");
     if (a->training != DWN_BN_FROZEN)
-        return dwn_set_error(-7, "stem_input_grad: only the frozen-statistics (DWN_BN_FROZEN) input gradient is built");
+        return dwn_set_error(-7, "stem_input_grad: this entry is the frozen-statistics (DWN_BN_FROZEN) input gradient; through batch "
+                                 "statistics (DWN_BN_TRAIN) it is dwn_stem_backward_input");
     ENTER(device);
     return k_stem_input_grad(a->dout, a->w, a->coef, a->B, a->Cin, a->S, a->C0, a->dx, a->dtype, (hipStream_t)stream);
 }

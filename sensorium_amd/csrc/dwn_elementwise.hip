@@ -741,6 +741,63 @@ int k_stem_bwd_finalize(const double* acc, const double* xmom, const float* w, c
     DWN_CHECK_LAUNCH();
     return 0;
 }
+// one workgroup, launched only when dx is asked for: Q[k][j] = Σ_c a2_c w[c][k] w[c][j], q0[k] = -(1/n) Σ_c w[c][k] scale_c Σ dout_c
+// and x̄ as floats, formed in double from the replica sums and the input moments.  The per-channel sums are taken as in
+// stem_bwd_finalize_kernel; the sums over the channels run serially in channel order (fixed order, C0 <= 128 terms).
+constexpr int STEM_DX_MAXC0 = 128;
+__global__ __launch_bounds__(256) void stem_bwd_finalize_dx_kernel(const double* acc, const double* xmom, const float* w,
+                                                                   const float* coef, double count, float* qx, int C0, int Cin) {
+    constexpr int NV = STEM_MAXCIN + 1;
+    __shared__ double la2[STEM_DX_MAXC0], lb[STEM_DX_MAXC0];
+    const int part = threadIdx.x & 3;
+    for (int cb = 0; cb < C0; cb += blockDim.x / 4) {
+        const int c = cb + (threadIdx.x >> 2);
+        const bool ok = c < C0;
+        double dx[STEM_MAXCIN], s1 = 0.0;
+        for (int k = 0; k < STEM_MAXCIN; ++k) dx[k] = 0.0;
+        for (int r = part * (DWN_NREP / 4); r < (part + 1) * (DWN_NREP / 4); ++r) {
+            const double* p = acc + ((i64)r * C0 + (ok ? c : 0)) * NV;
+            for (int k = 0; k < Cin; ++k) dx[k] += p[k];
+            s1 += p[STEM_MAXCIN];
+        }
+        for (int o = 1; o < 4; o <<= 1) {
+            for (int k = 0; k < STEM_MAXCIN; ++k) dx[k] += __shfl_xor(dx[k], o);
+            s1 += __shfl_xor(s1, o);
+        }
+        if (!ok || part != 0) continue;
+        const double scale = coef[c], invstd = coef[3 * C0 + c];
+        double dyc = 0.0;                                   // Σ dout (y0 - mean)
+        for (int k = 0; k < Cin; ++k) dyc += (double)w[c * Cin + k] * dx[k];
+        la2[c] = -scale * invstd * (invstd * dyc / count);
+        lb[c] = -scale * s1 / count;
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < STEM_MAXCIN * STEM_MAXCIN) {
+        const int k = t / STEM_MAXCIN, j = t % STEM_MAXCIN;
+        double v = 0.0;
+        if (k < Cin && j < Cin)
+            for (int c = 0; c < C0; ++c) v += la2[c] * (double)w[c * Cin + k] * (double)w[c * Cin + j];
+        qx[t] = (float)v;
+    } else if (t < STEM_MAXCIN * STEM_MAXCIN + STEM_MAXCIN) {
+        const int k = t - STEM_MAXCIN * STEM_MAXCIN;
+        double v = 0.0;
+        if (k < Cin)
+            for (int c = 0; c < C0; ++c) v += lb[c] * (double)w[c * Cin + k];
+        qx[t] = (float)v;
+    } else if (t < STEM_MAXCIN * STEM_MAXCIN + 2 * STEM_MAXCIN) {
+        const int k = t - STEM_MAXCIN * STEM_MAXCIN - STEM_MAXCIN;
+        qx[t] = k < Cin ? (float)(xmom[k] / count) : 0.f;
+    }
+}
+int k_stem_bwd_finalize_dx(const double* acc, const double* xmom, const float* w, const float* coef, double count, float* qx,
+                           int C0, int Cin, hipStream_t s) {
+    if (C0 > STEM_DX_MAXC0) return dwn_set_error(-4, "stem_backward_input: more than 128 stem channels not built");
+    if (Cin > STEM_MAXCIN) return dwn_set_error(-4, "stem: in_channels > 8 not built");
+    hipLaunchKernelGGL(stem_bwd_finalize_dx_kernel, dim3(1), dim3(256), 0, s, acc, xmom, w, coef, count, qx, C0, Cin);
+    DWN_CHECK_LAUNCH();
+    return 0;
+}
 int stem_moment_count() { return STEM_NM; }
 int stem_acc_stride() { return STEM_MAXCIN + 1; }
 
@@ -787,11 +844,26 @@ int k_stem_bwd_finalize_frozen(const double* acc, const float* w, const float* c
 // (half of the values change hands at each step: 4 + 2 + 1 rows x Cin shuffles instead of 3 x 8 rows x Cin) leaves lane cv with the
 // full sums of row pl*8 + cv — lane l owns row l of the tile, so each of the Cin planes is written as one 256-byte run.
 // No atomics: the summation order is fixed.
-template <typename T, int CINT, int NJ>
-__global__ __launch_bounds__(256) void stem_input_grad_kernel(const T* dout, const float* w, const float* coef, int B, int Cin, i64 S,
-                                                              int C0, float* dx) {
+// BS (batch statistics, dwn.h dwn_stem_backward_input): the statistics are functions of x, which adds an affine map of the row's
+// own input, dx[k] += q0[k] + Σ_j Q[k][j] (x_j - x̄_j), with qx = Q [8][8], q0 [8], x̄ [8] from stem_bwd_finalize_dx_kernel
+// (wave-uniform loads).  Lane l owns row l after the transpose-reduce, so it loads that row's Cin values from the NCDHW planes
+// (one 256-byte run per plane and wave, the pattern of the stores) before the dout loads: they are in flight under the reduce.
+template <typename T, int CINT, int NJ, bool BS>
+__global__ __launch_bounds__(256) void stem_input_grad_kernel(const T* dout, const float* w, const float* coef, const float* x,
+                                                              const float* qx, int B, int Cin, i64 S, int C0, float* dx) {
     constexpr int KC = TT<T>::KC;
     const int tid = threadIdx.x, lane = tid & 63, cv = lane & 7, pl = lane >> 3;
+    float Q[BS ? CINT : 1][BS ? CINT : 1], q0[BS ? CINT : 1], xbar[BS ? CINT : 1];
+    if constexpr (BS) {
+#pragma unroll
+        for (int k = 0; k < CINT; ++k) {
+            const bool ok = k < Cin;
+            q0[k] = ok ? qx[STEM_MAXCIN * STEM_MAXCIN + k] : 0.f;
+            xbar[k] = ok ? qx[STEM_MAXCIN * STEM_MAXCIN + STEM_MAXCIN + k] : 0.f;
+#pragma unroll
+            for (int j = 0; j < CINT; ++j) Q[k][j] = (ok && j < Cin) ? qx[k * STEM_MAXCIN + j] : 0.f;
+        }
+    }
     float wa[NJ][CINT][KC];
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
@@ -809,16 +881,25 @@ __global__ __launch_bounds__(256) void stem_input_grad_kernel(const T* dout, con
     const bool b2 = (cv & 4) != 0, b1 = (cv & 2) != 0, b0 = (cv & 1) != 0;
     for (unsigned tile = blockIdx.x * 4u + (tid >> 6); tile < ntiles; tile += nwaves) {
         const unsigned base = tile * 64u;
+        const unsigned row = base + lane;                   // = base + pl * 8 + cv: the row this lane stores
+        unsigned b = 0, sp = 0;
+        float xc[BS ? CINT : 1];
+        if constexpr (BS) {
+            const unsigned rowc = row < rows ? row : rows - 1;      // tail rows: a valid address, the result is not stored
+            b = dS.div(rowc); sp = rowc - b * (unsigned)S;
+#pragma unroll
+            for (int k = 0; k < CINT; ++k) xc[k] = k < Cin ? x[((i64)b * Cin + k) * S + sp] : 0.f;
+        }
         float g[8][NJ][KC];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-            unsigned row = base + pl * 8 + u;
-            row = row < rows ? row : rows - 1;               // tail rows: a valid address, the result is not stored
+            unsigned r = base + pl * 8 + u;
+            r = r < rows ? r : rows - 1;                     // tail rows: a valid address, the result is not stored
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 const int chan = (cv + 8 * j) * KC;
                 if (chan < C0) {
-                    ld_vec<T>(dout + (i64)row * C0 + chan, g[u][j]);
+                    ld_vec<T>(dout + (i64)r * C0 + chan, g[u][j]);
                 } else {
 #pragma unroll
                     for (int i = 0; i < KC; ++i) g[u][j][i] = 0.f;
@@ -857,35 +938,45 @@ __global__ __launch_bounds__(256) void stem_input_grad_kernel(const T* dout, con
             const float keep = b0 ? r2[1][k] : r2[0][k], send = b0 ? r2[0][k] : r2[1][k];
             r1[k] = keep + __shfl_xor(send, 1);
         }
-        const unsigned row = base + lane;                   // = base + pl * 8 + cv
+        if constexpr (BS) {
+#pragma unroll
+            for (int k = 0; k < CINT; ++k) xc[k] -= xbar[k];
+#pragma unroll
+            for (int k = 0; k < CINT; ++k) {
+                float t = q0[k];
+#pragma unroll
+                for (int j = 0; j < CINT; ++j) t = fmaf(Q[k][j], xc[j], t);
+                r1[k] += t;
+            }
+        }
         if (row < rows) {
-            const unsigned b = dS.div(row), sp = row - b * (unsigned)S;
+            if constexpr (!BS) { b = dS.div(row); sp = row - b * (unsigned)S; }
 #pragma unroll
             for (int k = 0; k < CINT; ++k)
                 if (k < Cin) dx[((i64)b * Cin + k) * S + sp] = r1[k];
         }
     }
 }
-template <typename T, int CINT, int NJ>
-static void stem_input_grad_launch(const void* dout, const float* w, const float* coef, int B, int Cin, i64 S, int C0, float* dx,
-                                   hipStream_t s) {
+template <typename T, int CINT, int NJ, bool BS>
+static void stem_input_grad_launch(const void* dout, const float* w, const float* coef, const float* x, const float* qx, int B, int Cin,
+                                   i64 S, int C0, float* dx, hipStream_t s) {
     const i64 tiles = ((i64)B * S + 63) / 64;
     i64 bx = (tiles + 3) / 4;
     if (bx > 2048) bx = 2048;                               // 256 CUs x 8 workgroups of four waves; the tiles are walked grid-stride
-    hipLaunchKernelGGL((stem_input_grad_kernel<T, CINT, NJ>), dim3((unsigned)bx), dim3(256), 0, s, (const T*)dout, w, coef, B, Cin, S,
-                       C0, dx);
+    hipLaunchKernelGGL((stem_input_grad_kernel<T, CINT, NJ, BS>), dim3((unsigned)bx), dim3(256), 0, s, (const T*)dout, w, coef, x, qx, B,
+                       Cin, S, C0, dx);
 }
-template <int CINT>
-static int stem_input_grad_dispatch(const void* dout, const float* w, const float* coef, int B, int Cin, i64 S, int C0, float* dx,
-                                    int dtype, hipStream_t s) {
+template <int CINT, bool BS>
+static int stem_input_grad_dispatch(const void* dout, const float* w, const float* coef, const float* x, const float* qx, int B, int Cin,
+                                    i64 S, int C0, float* dx, int dtype, hipStream_t s) {
     const int per = 8 * (dtype == DWN_BF16 ? 8 : 4);        // channels one row group covers per 16-byte load
     const int nj = (C0 + per - 1) / per;
     if (nj == 1) {
-        DISPATCH_T(dtype, (stem_input_grad_launch<bf16_t, CINT, 1>(dout, w, coef, B, Cin, S, C0, dx, s)),
-                   (stem_input_grad_launch<float, CINT, 1>(dout, w, coef, B, Cin, S, C0, dx, s)));
+        DISPATCH_T(dtype, (stem_input_grad_launch<bf16_t, CINT, 1, BS>(dout, w, coef, x, qx, B, Cin, S, C0, dx, s)),
+                   (stem_input_grad_launch<float, CINT, 1, BS>(dout, w, coef, x, qx, B, Cin, S, C0, dx, s)));
     } else if (nj == 2) {
-        DISPATCH_T(dtype, (stem_input_grad_launch<bf16_t, CINT, 2>(dout, w, coef, B, Cin, S, C0, dx, s)),
-                   (stem_input_grad_launch<float, CINT, 2>(dout, w, coef, B, Cin, S, C0, dx, s)));
+        DISPATCH_T(dtype, (stem_input_grad_launch<bf16_t, CINT, 2, BS>(dout, w, coef, x, qx, B, Cin, S, C0, dx, s)),
+                   (stem_input_grad_launch<float, CINT, 2, BS>(dout, w, coef, x, qx, B, Cin, S, C0, dx, s)));
     } else {
         return dwn_set_error(-4, "stem_input_grad: more than 128 (bf16) / 64 (fp32) stem channels not built");
     }
@@ -896,8 +987,15 @@ int k_stem_input_grad(const void* dout, const float* w, const float* coef, int B
                       hipStream_t s) {
     if (Cin > STEM_MAXCIN) return dwn_set_error(-4, "stem: in_channels > 8 not built");
     if ((i64)B * S >= (1ll << 31) - 64) return dwn_set_error(-4, "stem: more than 2^31 rows");
-    if (Cin <= 5) return stem_input_grad_dispatch<5>(dout, w, coef, B, Cin, S, C0, dx, dtype, s);
-    return stem_input_grad_dispatch<8>(dout, w, coef, B, Cin, S, C0, dx, dtype, s);
+    if (Cin <= 5) return stem_input_grad_dispatch<5, false>(dout, w, coef, nullptr, nullptr, B, Cin, S, C0, dx, dtype, s);
+    return stem_input_grad_dispatch<8, false>(dout, w, coef, nullptr, nullptr, B, Cin, S, C0, dx, dtype, s);
+}
+int k_stem_input_grad_train(const void* dout, const float* w, const float* coef, const float* x, const float* qx, int B, int Cin,
+                            i64 S, int C0, float* dx, int dtype, hipStream_t s) {
+    if (Cin > STEM_MAXCIN) return dwn_set_error(-4, "stem: in_channels > 8 not built");
+    if ((i64)B * S >= (1ll << 31) - 64) return dwn_set_error(-4, "stem: more than 2^31 rows");
+    if (Cin <= 5) return stem_input_grad_dispatch<5, true>(dout, w, coef, x, qx, B, Cin, S, C0, dx, dtype, s);
+    return stem_input_grad_dispatch<8, true>(dout, w, coef, x, qx, B, Cin, S, C0, dx, dtype, s);
 }
 
 

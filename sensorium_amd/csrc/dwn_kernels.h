@@ -48,6 +48,11 @@ int k_stem_bwd_finalize_frozen(const double* acc, const float* w, const float* c
                                int C0, int Cin, hipStream_t s);
 int k_stem_input_grad(const void* dout, const float* w, const float* coef, int B, int Cin, i64 S, int C0, float* dx, int dtype,
                       hipStream_t s);
+// batch statistics: qx = Q [8][8], q0 [8], x̄ [8] (floats) from the finished sums; dx = frozen term + Q (x - x̄) + q0
+int k_stem_bwd_finalize_dx(const double* acc, const double* xmom, const float* w, const float* coef, double count, float* qx,
+                           int C0, int Cin, hipStream_t s);
+int k_stem_input_grad_train(const void* dout, const float* w, const float* coef, const float* x, const float* qx, int B, int Cin,
+                            i64 S, int C0, float* dx, int dtype, hipStream_t s);
 int stem_moment_count();
 int stem_acc_stride();
 int k_shortcut_stats(const LoadDesc& xin, const ResGeom& gm, double* stats, int dtype, hipStream_t s);

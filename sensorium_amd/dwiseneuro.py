@@ -13,7 +13,8 @@ autocast both select the bf16 path here) or when ``compute_dtype=torch.bfloat16`
 
 Constraints of the HIP path (raised loudly, no fallback): channel counts multiples of 8, spatial_kernel 3,
 temporal_kernel 3 or 5, CUDA/HIP tensors only.  Backward: in training mode (batch statistics), and in eval mode with frozen
-BatchNorm statistics when the input requires a gradient or ``freeze_batchnorm()`` is on (input gradient at the stem: eval only).
+BatchNorm statistics when the input requires a gradient or ``freeze_batchnorm()`` is on.  The gradient w.r.t. the model input
+exists in both: through the batch statistics in training mode, through the fixed affine map in eval mode.
 """
 from __future__ import annotations
 

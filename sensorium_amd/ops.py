@@ -242,10 +242,7 @@ class StemFn(torch.autograd.Function):
         C0 = weight.shape[0]
         dout = dout.contiguous()
         dx = None
-        if ctx.needs_input_grad[0]:
-            if ctx.mode != L.BN_FROZEN:
-                raise RuntimeError("sensorium_amd: the gradient w.r.t. the model input is built for frozen BatchNorm statistics "
-                                   "(model.eval()) only, not through batch statistics")
+        if ctx.needs_input_grad[0] and ctx.mode == L.BN_FROZEN:
             dx = torch.empty_like(x)
             g = L.StemInputGradArgs()
             g.dtype = _DT[ctx.dtype]; g.training = ctx.mode; g.B = B; g.Cin = Cin; g.C0 = C0; g.S = T * H * W
@@ -263,7 +260,13 @@ class StemFn(torch.autograd.Function):
         a.xmom = xmom.data_ptr(); a.dout = dout.data_ptr(); a.dw = dw.data_ptr()
         ws = _ws(L.lib.dwn_stem_workspace_bytes(C.byref(a)), dev)
         a.ws = ws.data_ptr(); a.ws_bytes = ws.numel()
-        L.check(L.lib.dwn_stem_backward(C.byref(a), dev.index, _stream(dev)), "dwn_stem_backward")
+        if ctx.needs_input_grad[0] and ctx.mode == L.BN_TRAIN:
+            # through the batch statistics: parameter gradients and dx from one accumulation pass over dout (with the stem's
+            # parameters frozen by the caller, dw / dgamma / dbeta above are temporaries that autograd drops)
+            dx = torch.empty_like(x)
+            L.check(L.lib.dwn_stem_backward_input(C.byref(a), dx.data_ptr(), dev.index, _stream(dev)), "dwn_stem_backward_input")
+        else:
+            L.check(L.lib.dwn_stem_backward(C.byref(a), dev.index, _stream(dev)), "dwn_stem_backward")
         return dx, dw, dgamma, dbeta, None, None, None, None
 
 
