@@ -851,6 +851,7 @@ int dwn_pool_forward(const dwn_pool_args* a, int device, void* stream) {
 }
 int dwn_pool_backward(const dwn_pool_args* a, int device, void* stream) {
     ENTER(device);
+    if (a->C % 8) return dwn_set_error(-2, "pool: C must be a multiple of 8");      // (the kernel stores whole 16-byte channel vectors)
     return k_pool_bwd(a->dout, a->dx, a->BT, a->HW, a->C, a->dtype, (hipStream_t)stream);
 }
 
@@ -902,10 +903,11 @@ int dwn_cortex_forward(const dwn_cortex_args* ap, int device, void* stream) {
         TRY(k_prep(pa, dt, s));
     }
     GemmNN g = nn_base(ld_plain(a.x, a.Cin), LD_PLAIN, w.wp, Kg, a.y, a.C, M, Ng, Kg, a.groups);
-    g.stats = tr ? w.st : nullptr; g.stat_nchan = a.C; g.f32_split = f32_split_of(a.f32_products, !tr);
+    g.f32_split = f32_split_of(a.f32_products, !tr);
+    // (no statistics epilogue: the batch statistics are summed in double by k_cortex_stats below, frozen statistics need none)
     PROF(DWN_FAM_CORTEX_FWD, launch_gemm_nn(g, dt, s));
     if (bs) {
-        TRY(k_colstats(ld_plain(a.x, a.Cin), LD_PLAIN, M, a.Cin, w.stsc, dt, s));
+        TRY(k_cortex_stats(a.y, a.x, M, a.Cin, a.C, w.st, w.stsc, dt, s));
         TRY(k_bn_finalize_train2(fin_job(w.st, a.C, (double)M, a.bn, a.C), fin_job(w.stsc, a.Cin, (double)M, a.bnsc, a.C),
                                  a.momentum, a.eps, s));
     } else if (!tr) {

@@ -338,26 +338,6 @@ __global__ __launch_bounds__(256) void ew_apply_kernel(LoadDesc d, T* out, i64 l
     }
 }
 
-template <typename T, int KIND>
-__global__ __launch_bounds__(256) void colstats_kernel(LoadDesc d, i64 rows, int C, double* stats) {
-    SLICE_SETUP(C)
-    __shared__ float lstat[2 * NCV * KC];
-    if (tid < 2 * NCV * KC) lstat[tid] = 0.f;
-    __syncthreads();
-    float s0[KC], s1[KC];
-#pragma unroll
-    for (int i = 0; i < KC; ++i) { s0[i] = 0.f; s1[i] = 0.f; }
-    if (chan_ok)
-        for (i64 row = (i64)blockIdx.x * 32 + pl; row < rows; row += (i64)gridDim.x * 32) {
-            float v[KC];
-            load_op<KIND, T>(d, row, chan, v);
-#pragma unroll
-            for (int i = 0; i < KC; ++i) { s0[i] += v[i]; s1[i] += v[i] * v[i]; }
-        }
-    slice_stats_flush<KC>(lstat, s0, s1, cv, c0, C, stats, blockIdx.x % DWN_NREP);
-    DET_EXIT();
-}
-
 template <typename T>
 static int ew_apply_t(const LoadDesc& d, int kind, void* out, i64 ldo, i64 rows, int C, hipStream_t s) {
     dim3 grid = slice_grid(rows, C, TT<T>::KC);
@@ -377,21 +357,6 @@ static int ew_apply_t(const LoadDesc& d, int kind, void* out, i64 ldo, i64 rows,
 int k_ew_apply(const LoadDesc& d, int kind, void* out, i64 ldo, i64 rows, int C, int dtype, hipStream_t s) {
     return dtype == DWN_BF16 ? ew_apply_t<bf16_t>(d, kind, out, ldo, rows, C, s)
                              : ew_apply_t<float>(d, kind, out, ldo, rows, C, s);
-}
-template <typename T>
-static int colstats_t(const LoadDesc& d, int kind, i64 rows, int C, double* stats, hipStream_t s) {
-    dim3 grid = slice_grid(rows, C, TT<T>::KC, 1024);
-    switch (kind) {
-        case LD_PLAIN: hipLaunchKernelGGL((colstats_kernel<T, LD_PLAIN>), grid, dim3(256), 0, s, d, rows, C, stats); break;
-        case LD_PE: hipLaunchKernelGGL((colstats_kernel<T, LD_PE>), grid, dim3(256), 0, s, d, rows, C, stats); break;
-        case LD_BNACT: hipLaunchKernelGGL((colstats_kernel<T, LD_BNACT>), grid, dim3(256), 0, s, d, rows, C, stats); break;
-        default: return dwn_set_error(-3, "colstats: bad loader kind");
-    }
-    DWN_CHECK_LAUNCH();
-    return 0;
-}
-int k_colstats(const LoadDesc& d, int kind, i64 rows, int C, double* stats, int dtype, hipStream_t s) {
-    return dtype == DWN_BF16 ? colstats_t<bf16_t>(d, kind, rows, C, stats, s) : colstats_t<float>(d, kind, rows, C, stats, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1958,6 +1923,40 @@ __global__ void cortex_residual_fwd_kernel(const T* y, const T* x, const float* 
     out[idx] = from_f<T>(d * z + sc);
 }
 
+// training-mode BatchNorm sums of the layer: sum y, sum y^2 per channel of the conv output [M][C] and sum x, sum x^2 per channel of
+// the input [M][Cin] (the shortcut BatchNorm sees x tiled), accumulated in DOUBLE from the stored values.  Float partial sums (the
+// GEMM statistics epilogue and a column-sum pass, which this kernel replaced here) carry 1e-7 of sum y^2, which the variance
+// E[y^2] - mean^2 magnifies by mean^2 / var: 1.6e-4 in the variance of a channel whose mean is 100 standard deviations, and
+// 1.5e-3 in dw = dy^T x, which multiplies the then non-zero batch sum of dy by the input mean.  The
+// tensors are tiny ([B*T][<= 4096]): one thread per channel and 16-row chunk, as the backward sums below.
+template <typename T>
+__global__ void cortex_stats_kernel(const T* y, const T* x, int M, int Cin, int C, int rows_per_chunk, double* stats,
+                                    double* statssc) {
+    const int ch = blockIdx.x * blockDim.x + threadIdx.x;
+    const int m_beg = blockIdx.y * rows_per_chunk;
+    const int m_end = m_beg + rows_per_chunk < M ? m_beg + rows_per_chunk : M;
+    const int rep = blockIdx.y % DWN_NREP;
+    double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;
+    if (ch < C) {
+#pragma unroll 8
+        for (int m = m_beg; m < m_end; ++m) { const double v = (double)to_f<T>(y[(i64)m * C + ch]); a0 += v; a1 = fma(v, v, a1); }
+    }
+    if (ch < Cin) {
+#pragma unroll 8
+        for (int m = m_beg; m < m_end; ++m) { const double v = (double)to_f<T>(x[(i64)m * Cin + ch]); b0 += v; b1 = fma(v, v, b1); }
+    }
+    DET_ENTER();
+    if (ch < C) {
+        atomicAdd(stats + ((i64)rep * 2 + 0) * C + ch, a0);
+        atomicAdd(stats + ((i64)rep * 2 + 1) * C + ch, a1);
+    }
+    if (ch < Cin) {
+        atomicAdd(statssc + ((i64)rep * 2 + 0) * Cin + ch, b0);
+        atomicAdd(statssc + ((i64)rep * 2 + 1) * Cin + ch, b1);
+    }
+    DET_EXIT();
+}
+
 // per-channel backward sums: main BN (indexed by o): Σdh, Σdh·ŷ ; shortcut BN (indexed by j): Σdout, Σdout·ŝ
 // one thread per channel, looping over rows (M = B*T is ~1k)
 template <typename T>
@@ -2045,6 +2044,15 @@ int k_cortex_residual_fwd(const void* y, const void* x, const float* coef, const
     DISPATCH_T(dtype,
         hipLaunchKernelGGL((cortex_residual_fwd_kernel<bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)y, (const bf16_t*)x, coef, coefsc, dscale, M, Tn, Cin, C, groups, (bf16_t*)out),
         hipLaunchKernelGGL((cortex_residual_fwd_kernel<float>), grid, dim3(256), 0, s, (const float*)y, (const float*)x, coef, coefsc, dscale, M, Tn, Cin, C, groups, (float*)out));
+    DWN_CHECK_LAUNCH();
+    return 0;
+}
+int k_cortex_stats(const void* y, const void* x, int M, int Cin, int C, double* stats, double* statssc, int dtype, hipStream_t s) {
+    const int rows_per_chunk = 16, cmax = C > Cin ? C : Cin;
+    dim3 grid((cmax + 127) / 128, (M + rows_per_chunk - 1) / rows_per_chunk);
+    DISPATCH_T(dtype,
+        hipLaunchKernelGGL((cortex_stats_kernel<bf16_t>), grid, dim3(128), 0, s, (const bf16_t*)y, (const bf16_t*)x, M, Cin, C, rows_per_chunk, stats, statssc),
+        hipLaunchKernelGGL((cortex_stats_kernel<float>), grid, dim3(128), 0, s, (const float*)y, (const float*)x, M, Cin, C, rows_per_chunk, stats, statssc));
     DWN_CHECK_LAUNCH();
     return 0;
 }
@@ -2208,6 +2216,9 @@ int k_pack_dw(const float* src, float* dst, int C, int taps, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // dz[m][g*Rp + r] = dout[b][n][t] * (1 - exp(-beta*out[b][n][t])),  n = g*Rg + r  (zero in the padding),
 // db[n] += sum_m dz.  One workgroup per (b, 64-neuron tile): LDS transpose (t-contiguous -> n-contiguous).
+// The derivative sigmoid(beta*z) is formed as -expm1(-beta*out): for a quiet neuron (beta*z << 0) beta*out = log1p(exp(beta*z))
+// is tiny and 1 - exp(-beta*out) would cancel to steps of 6e-8 (17 % off at beta*z = -15, exactly 0 from -17 down), while
+// the Poisson gradient 1 - y/(out + eps) on such an element is of order 1/out, so dL/dz stays O(y).
 template <typename T>
 __global__ __launch_bounds__(256) void readout_dz_kernel(const float* dout, const float* out, float beta, int Tn,
                                                          int n_valid, int Rg, int Rp, int groups, T* dz, float* db) {
@@ -2222,7 +2233,7 @@ __global__ __launch_bounds__(256) void readout_dz_kernel(const float* dout, cons
         float v = 0.f;
         if (np < npad_total && r < Rg && n < n_valid) {
             i64 off = ((i64)b * n_valid + n) * Tn + t;
-            v = dout[off] * (1.0f - __expf(-beta * out[off]));
+            v = dout[off] * -expm1f(-beta * out[off]);
         }
         tile[nl * (Tn + 1) + t] = v;
     }
@@ -2394,6 +2405,15 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(const TensorListEntry* l
         if (ema) ema[i] = ema_decay * ema[i] + ema_omd * pi;
     }
 }
+// decay * e + omd * m as torch forms it on float32 tensors: two rounded products and a rounded sum.  Contraction is switched off
+// for this expression (HIP's __fmul_rn / __fadd_rn are plain operators and contract like them): a v_fmac_f32 skips one rounding,
+// and the truncation to int64 then lands on another integer
+__device__ __forceinline__ float ema_lerp_rounded(float decay, float e, float omd, float m) {
+#pragma clang fp contract(off)
+    const float a = decay * e;
+    const float b = omd * m;
+    return a + b;
+}
 // EMA of float buffers (running stats) and int64 counters (num_batches_tracked: float result truncated, ema.py:52)
 __global__ __launch_bounds__(256) void ema_lerp_kernel(const TensorListEntry* list, int ntensors, float decay, float omd) {
     const TensorListEntry e = list[blockIdx.y];
@@ -2401,7 +2421,7 @@ __global__ __launch_bounds__(256) void ema_lerp_kernel(const TensorListEntry* li
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             long long* d = reinterpret_cast<long long*>(e.ema);
             const long long* sp = reinterpret_cast<const long long*>(e.param);
-            for (i64 i = 0; i < e.numel; ++i) d[i] = (long long)(decay * (float)d[i] + omd * (float)sp[i]);
+            for (i64 i = 0; i < e.numel; ++i) d[i] = (long long)ema_lerp_rounded(decay, (float)d[i], omd, (float)sp[i]);
         }
         return;
     }

@@ -32,7 +32,6 @@ int k_bn1_gram_finalize(const double* gram, const float* w1, int E, int Cin, dou
                         float* rm, float* rv, long long* nbt, float momentum, float eps, float* coef, double* sc_stats, int dtype,
                         hipStream_t s);
 int k_ew_apply(const LoadDesc& d, int kind, void* out, i64 ldo, i64 rows, int C, int dtype, hipStream_t s);
-int k_colstats(const LoadDesc& d, int kind, i64 rows, int C, double* stats, int dtype, hipStream_t s);
 // stem through the input moments (no y0 round trip; dwn_elementwise.hip)
 int k_stem_xmom(const float* x, int B, int Cin, i64 S, double* mom, hipStream_t s);
 int k_stem_bn_finalize(const double* mom, double count, const float* w, const float* gamma, const float* beta, float* rm,
@@ -78,6 +77,7 @@ int k_pool_fwd(const void* x, void* out, i64 BT, int HW, int C, int dtype, hipSt
 int k_pool_bwd(const void* dpool, void* dx, i64 BT, int HW, int C, int dtype, hipStream_t s);
 int k_cortex_residual_fwd(const void* y, const void* x, const float* coef, const float* coefsc, const float* dscale,
                           int M, int Tn, int Cin, int C, int groups, void* out, int dtype, hipStream_t s);
+int k_cortex_stats(const void* y, const void* x, int M, int Cin, int C, double* stats, double* statssc, int dtype, hipStream_t s);
 int k_cortex_bwd_reduce(const void* y, const void* x, const void* dout, const float* gmask, int gmask_ld,
                         const float* coef, const float* coefsc, const float* dscale, int M, int Tn, int Cin, int C,
                         int groups, double* stats, double* statssc, int dtype, hipStream_t s);
