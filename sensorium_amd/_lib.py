@@ -251,7 +251,8 @@ class DwnError(RuntimeError):
 
 # csrc/Makefile HASH_SRCS, in its order
 HASH_SRCS = ("dwn_api.hip", "dwn_gemm.hip", "dwn_gemm_xl.hip", "dwn_gemm_kd.hip", "dwn_dwconv.hip", "dwn_dwrc.hip", "dwn_dwbwd.hip", "dwn_dwfwd.hip",
-             "dwn_elementwise.hip", "dwn_data.hip", "dwn_common.h", "dwn_internal.h", "dwn_kernels.h", "../../include/dwn.h")
+             "dwn_elementwise.hip", "dwn_data.hip", "dwn_common.h", "dwn_internal.h", "dwn_kernels.h", "dwn_launch.h",
+             "../../include/dwn.h")
 
 
 def source_hash() -> str:

@@ -131,24 +131,23 @@ LoadDesc ld_ycoef(const void* y, i64 ld, const float* coef, int C) {
     return d;
 }
 
-int bn_finalize(const double* stats, int stat_c, double count, const dwn_bn& bn, int C, int training, float momentum,
-                float eps, hipStream_t s) {
-    if (training)
-        return k_bn_finalize_train(stats, stat_c, count, bn.gamma, bn.beta, bn.running_mean, bn.running_var,
-                                   bn.num_batches_tracked, momentum, eps, bn.coef, C, s);
-    return k_bn_finalize_eval(bn.gamma, bn.beta, bn.running_mean, bn.running_var, eps, bn.coef, C, s);
-}
-
 BnFinJob fin_job(const double* stats, int stat_c, double count, const dwn_bn& bn, int C) {
     BnFinJob j; memset(&j, 0, sizeof(j));
     j.stats = stats; j.stat_c = stat_c; j.count = count; j.gamma = bn.gamma; j.beta = bn.beta;
     j.running_mean = bn.running_mean; j.running_var = bn.running_var; j.nbt = bn.num_batches_tracked; j.coef = bn.coef; j.C = C;
     return j;
 }
-BnBwdJob bwd_job(const double* stats, double count, const dwn_bn& bn, float* abc, int C) {
+BnBwdJob bwd_job(const double* stats, double count, const dwn_bn& bn, float* abc, int C, bool frozen) {
     BnBwdJob j; memset(&j, 0, sizeof(j));
     j.stats = stats; j.count = count; j.coef = bn.coef; j.dgamma = bn.dgamma; j.dbeta = bn.dbeta; j.abc = abc; j.C = C;
+    j.frozen = frozen ? 1 : 0;
     return j;
+}
+
+int bn_finalize(const double* stats, int stat_c, double count, const dwn_bn& bn, int C, int training, float momentum,
+                float eps, hipStream_t s) {
+    if (training) return k_bn_finalize_train(fin_job(stats, stat_c, count, bn, C), BnFinJob{}, momentum, eps, s);
+    return k_bn_finalize_eval(bn.gamma, bn.beta, bn.running_mean, bn.running_var, eps, bn.coef, C, s);
 }
 
 GemmNN nn_base(const LoadDesc& a, int a_kind, const void* b, i64 ldb, void* c, i64 ldc, int M, int N, int K, int groups) {
@@ -377,7 +376,7 @@ int dwn_bn_finalize(const double* stats, int stat_c, double count, const dwn_bn*
 int dwn_bn_bwd_finalize(const double* stats, double count, const dwn_bn* bn, float* abc, int C, int device,
                         void* stream) {
     ENTER(device);
-    return k_bn_bwd_finalize(stats, count, bn->coef, bn->dgamma, bn->dbeta, abc, C, (hipStream_t)stream);
+    return k_bn_bwd_finalize(bwd_job(stats, count, *bn, abc, C, false), BnBwdJob{}, (hipStream_t)stream);
 }
 // BatchNorm-1 of conv_pw WITHOUT conv_pw's output (dwn.h): raw products [a0 | 1]^T a0 by one gemm_tn pass, then k_bn1_gram_finalize
 size_t dwn_conv_pw_bn_stats_workspace_bytes(int Cin) { return (size_t)(Cin + 8) * Cin * sizeof(double) + 256; }
@@ -651,7 +650,7 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
     if (bs) {
         // (y1-free on an identity-map block: the shortcut's sums came out of the Gram pass, k_bn1_gram_finalize)
         if (!(y1_free && identity_sc)) PROF(DWN_FAM_RESID_FWD, k_shortcut_stats(xin, gm, w.stsc, dt, s));
-        TRY(k_bn_finalize_train2(fin_job(w.st4, a.Cout, (double)Mout, a.bn4, a.Cout),
+        TRY(k_bn_finalize_train(fin_job(w.st4, a.Cout, (double)Mout, a.bn4, a.Cout),
                                  fin_job(w.stsc, a.Cin, (double)Mout, a.bnsc, a.Cout), a.momentum, a.eps, s));
     }
     PROF(DWN_FAM_RESID_FWD, k_residual_fwd(xin, a.y4, a.bn4.coef, a.bnsc.coef, a.drop_scale, gm, a.out_pe_t, a.out_pe_h,
@@ -737,8 +736,8 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
     ResGeom gm = geom_of(a);
     // residual + the two linear BNs (bn4 = conv_pwl.1.bn, bnsc = bn_sc.bn)
     PROF(DWN_FAM_RESID_BWD, k_residual_bwd_reduce(xin, a.y4, a.dout, a.bn4.coef, a.bnsc.coef, a.drop_scale, gm, w.st4, w.stsc, dt, s));
-    TRY((frozen ? k_bn_bwd_finalize_frozen2 : k_bn_bwd_finalize2)(bwd_job(w.st4, (double)Mout, a.bn4, w.abc4, a.Cout),
-                                                                  bwd_job(w.stsc, (double)Mout, a.bnsc, w.abcsc, a.Cout), s));
+    TRY(k_bn_bwd_finalize(bwd_job(w.st4, (double)Mout, a.bn4, w.abc4, a.Cout, frozen),
+                          bwd_job(w.stsc, (double)Mout, a.bnsc, w.abcsc, a.Cout, frozen), s));
     PROF(DWN_FAM_RESID_BWD, k_residual_bwd_dy4(a.y4, a.dout, w.abc4, a.drop_scale, gm, a.dy4, dt, s));
     // conv_pwl backward: du = dy4 @ W2 (+ SE gate gradient), dW2 = dy4^T @ u
     void* du = a.buf_a;
@@ -783,8 +782,7 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
     // ... and dh3 replaces du in place, so the temporal kernel reads (dh3, y3) with the plain BN-backward affine
     PROF(DWN_FAM_BN3_REDUCE, k_bn3_bwd_reduce(d3, a.bn3.coef, Mout, a.Cmid, w.st3, du, dt, s));
     }
-    if (frozen) TRY(k_bn_bwd_finalize_frozen(w.st3, a.bn3.coef, a.bn3.dgamma, a.bn3.dbeta, w.abc3, a.Cmid, s));
-    else TRY(k_bn_bwd_finalize(w.st3, (double)Mout, a.bn3.coef, a.bn3.dgamma, a.bn3.dbeta, w.abc3, a.Cmid, s));
+    TRY(k_bn_bwd_finalize(bwd_job(w.st3, (double)Mout, a.bn3, w.abc3, a.Cmid, frozen), BnBwdJob{}, s));
     // temporal dw backward
     {
         DwTemporalBwd d; memset(&d, 0, sizeof(d));
@@ -795,8 +793,7 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
         d.kt = a.kt; d.stats = w.st2;
         PROF(DWN_FAM_DWT_BWD, launch_dw_temporal_bwd(d, dt, s));
     }
-    if (frozen) TRY(k_bn_bwd_finalize_frozen(w.st2, a.bn2.coef, a.bn2.dgamma, a.bn2.dbeta, w.abc2, a.Cmid, s));
-    else TRY(k_bn_bwd_finalize(w.st2, (double)Mout, a.bn2.coef, a.bn2.dgamma, a.bn2.dbeta, w.abc2, a.Cmid, s));
+    TRY(k_bn_bwd_finalize(bwd_job(w.st2, (double)Mout, a.bn2, w.abc2, a.Cmid, frozen), BnBwdJob{}, s));
     // spatial dw backward (du is dead: reuse buf_a for dh1)
     void* dh1 = a.buf_a;
     {
@@ -808,8 +805,7 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
         d.Hout = a.Hout; d.Wout = a.Wout; d.C = a.Cmid; d.stride = a.stride; d.ks = a.ks; d.stats = w.st1;
         PROF(DWN_FAM_DWS_BWD, launch_dw_spatial_bwd(d, dt, s));
     }
-    if (frozen) TRY(k_bn_bwd_finalize_frozen(w.st1, a.bn1.coef, a.bn1.dgamma, a.bn1.dbeta, w.abc1, a.Cmid, s));
-    else TRY(k_bn_bwd_finalize(w.st1, (double)Min, a.bn1.coef, a.bn1.dgamma, a.bn1.dbeta, w.abc1, a.Cmid, s));
+    TRY(k_bn_bwd_finalize(bwd_job(w.st1, (double)Min, a.bn1, w.abc1, a.Cmid, frozen), BnBwdJob{}, s));
     // conv_pw backward WITHOUT y1.  dy1 = A1*dh1 + A2*y1 + A3 is linear and y1 = a0.W1^T, so the y1 terms fold into Cin x Cin
     // matrices on either side:  da0 = [dh1 | a0] . [diag(A1) W1 ; G] + r3  (Bp, r3: k_pw_bwd_prep) and
     // dW1 = diag(A1) (dh1^T a0) + diag(A2) W1 (a0^T a0) + A3 (1^T a0)  (raw products in tacc, folded by k_pw_wgrad_fold)
@@ -908,7 +904,7 @@ int dwn_cortex_forward(const dwn_cortex_args* ap, int device, void* stream) {
     PROF(DWN_FAM_CORTEX_FWD, launch_gemm_nn(g, dt, s));
     if (bs) {
         TRY(k_cortex_stats(a.y, a.x, M, a.Cin, a.C, w.st, w.stsc, dt, s));
-        TRY(k_bn_finalize_train2(fin_job(w.st, a.C, (double)M, a.bn, a.C), fin_job(w.stsc, a.Cin, (double)M, a.bnsc, a.C),
+        TRY(k_bn_finalize_train(fin_job(w.st, a.C, (double)M, a.bn, a.C), fin_job(w.stsc, a.Cin, (double)M, a.bnsc, a.C),
                                  a.momentum, a.eps, s));
     } else if (!tr) {
         TRY(bn_finalize(w.st, a.C, (double)M, a.bn, a.C, 0, a.momentum, a.eps, s));
@@ -939,8 +935,7 @@ int dwn_cortex_backward(const dwn_cortex_args* ap, int device, void* stream) {
     }
     TRY(k_cortex_bwd_reduce(a.y, a.x, a.dout, a.dout_mask, a.dout_mask_ld, a.bn.coef, a.bnsc.coef, a.drop_scale, M, a.T,
                             a.Cin, a.C, a.groups, w.st, w.stsc, dt, s));
-    TRY((frozen ? k_bn_bwd_finalize_frozen2 : k_bn_bwd_finalize2)(bwd_job(w.st, (double)M, a.bn, w.abc, a.C),
-                                                                  bwd_job(w.stsc, (double)M, a.bnsc, w.abcsc, a.C), s));
+    TRY(k_bn_bwd_finalize(bwd_job(w.st, (double)M, a.bn, w.abc, a.C, frozen), bwd_job(w.stsc, (double)M, a.bnsc, w.abcsc, a.C, frozen), s));
     TRY(k_cortex_bwd_dy(a.y, a.dout, a.dout_mask, a.dout_mask_ld, a.bn.coef, w.abc, a.drop_scale, M, a.T, a.C, a.groups,
                         w.dy, dt, s));
     {

@@ -16,6 +16,7 @@
 //     (slow) LDS float atomics.
 // dh1 is bit-identical to the pair kernel's (same dot2 order); dW and the BatchNorm sums differ in summation order only.
 #include "dwn_internal.h"
+#include "dwn_launch.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -217,13 +218,31 @@ __device__ __forceinline__ WkBlk wk_block() {
 // Gram-matrix statistics describe them).  A wave fetches its a0 fragments one chunk ahead (each tile's registers are refilled as
 // soon as its MFMAs are issued) and keeps its W1 fragments in registers for the whole launch.  The slices of a plane group run on
 // one XCD (wk_block), so a0 crosses the fabric once and the other slices find it in that L2.
+// The kernel's dynamic LDS, indexed by the kernel and sized by its launcher (launch_s1c) from this one description:
+// ring [NG][RQ][Wqp][64] dwords, then (stored form) the chunk's y1 rows by LDS-DMA, 1 KB per wave and row, or (rebuilt form) the
+// swizzled W1 slice of the workgroup's 64 channels.  The end-of-kernel dW reduction ([9][64] floats) reuses the dead ring.
+template <int LPW, int RB, int CIN>
+struct S1cLds {
+    static constexpr int CS = 64, NG = 16 / LPW, Wqp = LPW + 1, RQ = RB + 2;
+    static constexpr int rowdw = Wqp * CS;                                  // dwords between ring rows of one plane
+    static constexpr unsigned RING_BYTES = (unsigned)NG * RQ * Wqp * CS * 4u;
+    // PF (rebuilt form): the NEXT chunk's gradient rows are loaded before the current chunk's walk and stay in registers under it —
+    // the kernel runs two workgroups per CU and was latency-bound (vector ALUs 52 % busy, a third of the wave cycles waiting): with
+    // the loads a chunk ahead a workgroup never waits for HBM at the top of a chunk.  The 36 registers come from the W1 fragments,
+    // which then live in LDS for 64 input channels too
+    static constexpr bool PF = (CIN > 64 && WK_S1C_PF >= 1) || (CIN > 0 && WK_S1C_PF >= 2);
+    static constexpr bool W1_LDS = CIN > 64 || PF;
+    static constexpr unsigned Y1_OFF = RING_BYTES, Y1_BYTES = CIN > 0 ? 0u : (unsigned)RB * 4096u;
+    static constexpr unsigned W1_OFF = Y1_OFF + Y1_BYTES, W1_BYTES = W1_LDS ? 64u * CIN * 2u : 0u;
+    static constexpr unsigned TOTAL = W1_OFF + W1_BYTES;
+};
 template <int LPW, int RB, int CIN>
 __global__ __launch_bounds__(256, CIN > 0 ? WK_MINW_RC : WK_MINW) void dw_spatial_bwd_s1c_kernel(const DwSpatialBwd a) {
     typedef bf16_t T;
-    constexpr int NT = 256, CS = 64, NG = 16 / LPW, Wqp = LPW + 1, RQ = RB + 2, W = 2 * LPW;
+    typedef S1cLds<LPW, RB, CIN> L;
+    constexpr int NT = 256, CS = L::CS, NG = L::NG, Wqp = L::Wqp, RQ = L::RQ, W = 2 * LPW;
     constexpr int KB = CIN > 0 ? CIN / 32 : 1;
-    constexpr int rowdw = Wqp * CS;                                         // dwords between ring rows of one plane
-    constexpr unsigned RING_BYTES = (unsigned)NG * RQ * Wqp * CS * 4u;
+    constexpr int rowdw = L::rowdw;
     constexpr int NEX = (RB + LPW - 1) / LPW;                              // halo-column rows a thread stages per chunk
     __shared__ float lstat[2 * CS];
     __shared__ __attribute__((aligned(16))) unsigned lwp[3 * 4 * CS];        // packed weights [dy][combo][channel]
@@ -275,23 +294,18 @@ __global__ __launch_bounds__(256, CIN > 0 ? WK_MINW_RC : WK_MINW) void dw_spatia
     const int dp = wave * 8 + dq;                                              // pixel of the 32-pixel group row
     const int dgrp = dp / W, dx = dp % W;
     const int dce = (c0 + c16 * 8 < a.C) ? c0 + c16 * 8 : c0;                   // channel tail: any valid address (never read back)
-    const unsigned lds_y1 = (unsigned)(size_t)wk_smem + RING_BYTES + (unsigned)wave * 1024u;
+    const unsigned lds_y1 = (unsigned)(size_t)wk_smem + L::Y1_OFF + (unsigned)wave * 1024u;
     // ... and where this thread finds its two pixels (2jj, 2jj+1) of a row in that block: slots s0 and s0 + 2
     const int jq = pl & 3;
-    const unsigned char* yld = wk_smem + RING_BYTES + wave * 1024 + (((jq & 1) + ((jq >> 1) << 2)) * 128) + cv * 8;
+    const unsigned char* yld = wk_smem + L::Y1_OFF + wave * 1024 + (((jq & 1) + ((jq >> 1) << 2)) * 128) + cv * 8;
     // ---- rebuilt y1 (CIN > 0): lane (lr, lg): A-operand row lr = (pixel pair lr >> 2 of this wave, row parity (lr >> 1) & 1, x parity
     // lr & 1), k group lg; B-operand column lr = W1 row c0 + 4 lr + n of channel tile n
     const int lr = lane & 15, lg = lane >> 4;
     // W1 fragments: registers for CIN = 64; for CIN = 128 a swizzled copy of the 64-row slice in LDS behind the ring
     // (16-byte chunk c of row r at chunk c ^ ((r >> 2) & (chunks per row - 1)): conflict-free ds_read_b128 of a fragment at 128
     // input channels, two-way at 64 — eight reads per two walk rows)
-    // PF (rebuilt form): the NEXT chunk's gradient rows are loaded before the current chunk's walk and stay in registers under it —
-    // the kernel runs two workgroups per CU and was latency-bound (vector ALUs 52 % busy, a third of the wave cycles waiting): with
-    // the loads a chunk ahead a workgroup never waits for HBM at the top of a chunk.  The 36 registers come from the W1 fragments,
-    // which then live in LDS for 64 input channels too
-    constexpr bool PF = (CIN > 64 && WK_S1C_PF >= 1) || (CIN > 0 && WK_S1C_PF >= 2);
-    constexpr bool W1_LDS = CIN > 64 || PF;
-    constexpr unsigned W1_OFF = CIN > 0 ? RING_BYTES : RING_BYTES + (unsigned)RB * 4096u;
+    constexpr bool PF = L::PF, W1_LDS = L::W1_LDS;        // gradient rows fetched a chunk ahead; W1 fragments in LDS (S1cLds)
+    constexpr unsigned W1_OFF = L::W1_OFF;
     uint4 wfr[W1_LDS ? 1 : 4][KB];
     const T* a0src0 = nullptr;
     if constexpr (CIN > 0) {
@@ -644,10 +658,26 @@ __global__ __launch_bounds__(256, CIN > 0 ? WK_MINW_RC : WK_MINW) void dw_spatia
 // CIN > 0: y1 is rebuilt from a0 (see the stride-1 kernel).  Here the MFMA runs with the PIXELS as its A operand (the wave's 16
 // pixels of the input row: four quads) and W1 rows as B in the order 4 cv + n, so that accumulator register j of channel tile n
 // in lane (cv, quad) IS y1[pixel j of the thread's quad][channel 4 cv + n]: the thread's own 4 x 4 values, no LDS round trip.
+// The kernel's dynamic LDS, indexed by the kernel and sized by its launcher (launch_s2) from this one description: the gradient tile
+// [NG][rows_qmax][Wqp][64] dwords (rows_qmax staged output rows: a run-time band height), then (128 input channels) the swizzled
+// W1 slice.  The end-of-kernel dW reduction ([9][64] floats) reuses the dead tile: the floor of the total.
+template <int LPW, int CIN>
+struct S2Lds {
+    static constexpr int NG = 16 / LPW, Wqp = LPW + 1;
+    static constexpr bool W1_LDS = CIN > 64;             // W1 fragments: registers at 64 input channels, LDS behind the tile at 128
+    static constexpr unsigned ROW_BYTES = (unsigned)(NG * Wqp * 256);       // one staged row of every plane of the group
+    static constexpr unsigned W1_BYTES = W1_LDS ? 64u * CIN * 2u : 0u;
+    static constexpr unsigned w1_off(int rows_qmax) { return (unsigned)rows_qmax * ROW_BYTES; }
+    static constexpr size_t total(int rows_qmax) {
+        const size_t b = (size_t)rows_qmax * ROW_BYTES + W1_BYTES;
+        return b < 9 * 64 * sizeof(float) ? 9 * 64 * sizeof(float) : b;
+    }
+};
 template <int LPW, int CIN>
 __global__ __launch_bounds__(256, CIN > 0 ? WK_MINW2_RC : WK_MINW2) void dw_spatial_bwd_s2_kernel(const DwSpatialBwd a, const int R, const int rows_qmax) {
     typedef bf16_t T;
-    constexpr int NT = 256, CS = 64, NG = 16 / LPW, Wqp = LPW + 1;
+    typedef S2Lds<LPW, CIN> L;
+    constexpr int NT = 256, CS = 64, NG = L::NG, Wqp = L::Wqp;
     constexpr int KB = CIN > 0 ? CIN / 32 : 1;
     __shared__ float lstat[2 * CS];
     __shared__ __attribute__((aligned(16))) unsigned lwp[3 * 3 * CS];        // packed weights [dy][combo][channel]
@@ -677,8 +707,8 @@ __global__ __launch_bounds__(256, CIN > 0 ? WK_MINW2_RC : WK_MINW2) void dw_spat
 
         // B operand: column cv of channel tile n = W1 row c0 + 4 cv + n, k group lane >> 4.  Registers for CIN = 64; for CIN = 128 a
     // swizzled LDS copy of the slice behind the gradient tile (chunk c of row r at c ^ ((r >> 2) & 15))
-    constexpr bool W1_LDS = CIN > 64;
-    const unsigned W1_OFF = (unsigned)rows_qmax * (unsigned)(NG * Wqp * 256);
+    constexpr bool W1_LDS = L::W1_LDS;
+    const unsigned W1_OFF = L::w1_off(rows_qmax);
     uint4 wfr[W1_LDS ? 1 : 4][KB];
     if constexpr (CIN > 0) {
         const T* w1 = reinterpret_cast<const T*>(a.w1);
@@ -967,63 +997,37 @@ bool dw_spatial_bwd_rc_supported(const DwSpatialBwd& a, int dtype) {
     return true;
 }
 
+// both launchers: fallback 2 workgroups per CU when the occupancy query fails (historical).  CIN > 0: wk_block<true> maps the slices of
+// a tile to one XCD
 template <int LPW, int CIN>
 static int launch_s2(const DwSpatialBwd& a, hipStream_t s) {
-    constexpr int NG = 16 / LPW, Wqp = LPW + 1;
-    const size_t rowb = (size_t)NG * Wqp * 256;
+    typedef S2Lds<LPW, CIN> L;
     // rebuilt-y1 form: two workgroups per CU (registers), so the tile may be larger
     const size_t budget = CIN > 0 ? (size_t)(WK_LDS_BUDGET * 3 / 2) : (size_t)WK_LDS_BUDGET;
     int R = a.rows_band;                              // input rows per band, even
     if (R <= 0) {
         R = 2;
-        while (R < a.Hin && (size_t)((R + 2) / 2 + 1) * rowb <= budget) R += 2;
+        while (R < a.Hin && (size_t)((R + 2) / 2 + 1) * L::ROW_BYTES <= budget) R += 2;
         const int nb = (a.Hin + R - 1) / R;
         R = (a.Hin + nb - 1) / nb;                    // even split
     }
     R = (R + 1) & ~1;
     if (R > a.Hin) R = (a.Hin + 1) & ~1;
     const int rows_qmax = R / 2 + 1;
-    size_t lds = (size_t)rows_qmax * rowb + (CIN > 64 ? (size_t)64 * CIN * 2 : 0);
-    if (lds < 9 * 64 * sizeof(float)) lds = 9 * 64 * sizeof(float);
+    const size_t lds = L::total(rows_qmax);
     if (lds > 150 * 1024) return dwn_set_error(-5, "dw_spatial_bwd: rows_band too large for the LDS tile");
-    auto kern = dw_spatial_bwd_s2_kernel<LPW, CIN>;
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        (void)hipGetLastError();
-    int bpc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kern, 256, lds) != hipSuccess || bpc < 1) { (void)hipGetLastError(); bpc = 2; }
-    const int slices = (a.C + 63) / 64;
     const int nbands = (a.Hin + R - 1) / R;
-    const i64 work = (i64)((a.planes + NG - 1) / NG) * nbands;
-    i64 gx = (256 * bpc) / slices;
-    if (gx < 1) gx = 1;
-    if (gx > work) gx = work;
-    if (CIN > 0) gx = gx >= 8 ? (gx & ~(i64)7) : 8;   // wk_block<true>: the slices of a tile share an XCD (a workgroup past the work just exits)
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, slices), dim3(256), lds, s, a, R, rows_qmax);
-    DWN_CHECK_LAUNCH();
-    return 0;
+    return launch_resident(dw_spatial_bwd_s2_kernel<LPW, CIN>, 256, lds, 2, (a.C + 63) / 64,
+                           (i64)((a.planes + L::NG - 1) / L::NG) * nbands, CIN > 0, s, a, R, rows_qmax);
 }
 
 template <int LPW, int RB, int CIN>
 static int launch_s1c(const DwSpatialBwd& a, hipStream_t s) {
-    constexpr int NG = 16 / LPW, Wqp = LPW + 1;
-    // ring + (stored form) the chunk's y1 rows by LDS-DMA / (rebuilt form, 128 input channels) the W1 slice
-    const size_t lds = (size_t)NG * (RB + 2) * Wqp * 256 + (CIN > 0 ? ((CIN > 64 || WK_S1C_PF >= 2) ? (size_t)64 * CIN * 2 : 0) : (size_t)RB * 4096);
-    auto kern = dw_spatial_bwd_s1c_kernel<LPW, RB, CIN>;
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        (void)hipGetLastError();
-    int bpc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kern, 256, lds) != hipSuccess || bpc < 1) { (void)hipGetLastError(); bpc = 2; }
-    const int slices = (a.C + 63) / 64;
-    const i64 work = (a.planes + NG - 1) / NG;
-    i64 gx = (256 * bpc) / slices;
-    if (gx < 1) gx = 1;
-    if (gx > work) gx = work;
-    if (CIN > 0) gx = gx >= 8 ? (gx & ~(i64)7) : 8;
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, slices), dim3(256), lds, s, a);
-    DWN_CHECK_LAUNCH();
-    return 0;
+    typedef S1cLds<LPW, RB, CIN> L;
+    return launch_resident(dw_spatial_bwd_s1c_kernel<LPW, RB, CIN>, 256, L::TOTAL, 2, (a.C + 63) / 64,
+                           (a.planes + L::NG - 1) / L::NG, CIN > 0, s, a);
 }
-// chained stride-1 kernel: rows per chunk = a.rows_band, or the measured best at the metric shapes (tools/bwd_chain_check.py):
+// chained stride-1 kernel: rows per chunk = a.rows_band, or the measured best at the metric shapes (figures: docs/HISTORY.md section 6c):
 // 4 rows per chunk at 18x32 planes (three workgroups per CU), 2 at 9x16 and 5x8
 template <int LPW, int CIN>
 static int launch_s1c_rb(const DwSpatialBwd& a, hipStream_t s) {

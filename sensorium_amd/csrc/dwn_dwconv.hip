@@ -20,6 +20,7 @@
 // Integer index math is kept off the per-tap path (FastDiv / 24-bit multiplies / per-pixel tile index): on gfx950 an
 // integer VALU op costs ~1.5 FMAs and a bf16->fp32 unpack is such an op (profiles/r1c_valu_rates.txt).
 #include "dwn_internal.h"
+#include "dwn_launch.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -1036,21 +1037,11 @@ __global__ __launch_bounds__(256, TB >= 8 ? 2 : 3) void dw_temporal_bwd_kernel(c
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-static inline int grid_cap(i64 work, int cap) { return (int)(work < cap ? (work > 0 ? work : 1) : cap); }
-// persistent grids: one full resident wave of workgroups (256 CUs x blocks/CU from the occupancy query), so no
-// ragged second wave; `slices` workgroups share each x index
-template <typename K>
-static int resident_grid_x(K kernel, size_t dyn_lds, int slices, i64 work, int threads = 256) {
-    if (dyn_lds > 48 * 1024) {     // opt in to > default dynamic LDS (160 KiB per CU on gfx950, minus the static part)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)dyn_lds) != hipSuccess)
-            (void)hipGetLastError();   // clear: the launch itself reports a too-large tile
-    }
-    int bpc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kernel, threads, dyn_lds) != hipSuccess || bpc < 1) bpc = 2;
-    int gx = (256 * bpc) / slices;     // 256 CUs
-    if (gx < 1) gx = 1;
-    return grid_cap(work, gx);
+// persistent grids (dwn_launch.h): one full resident round of workgroups, `slices` of them per x index.  Fallback 2 workgroups per
+// CU when the occupancy query fails: historical
+template <typename K, typename A>
+static int launch_dw(K kernel, int threads, size_t dyn_lds, int slices, i64 work, hipStream_t s, const A& a) {
+    return launch_resident(kernel, threads, dyn_lds, 2, slices, work, false, s, a);
 }
 
 template <typename T>
@@ -1079,27 +1070,19 @@ static int spatial_fwd_t(DwSpatialFwd a, hipStream_t s) {
     const i64 work = (i64)a.planes * nbands;
     // 512-thread workgroups (twice the waves per LDS tile) pay off on large planes; tiny planes prefer 256
     const bool big = a.Hin * a.Win >= 512;
-#define DWS_FWD_LAUNCH(ST_, NT_) do { \
-        dim3 grid(resident_grid_x(dw_spatial_fwd_kernel<T, 3, ST_, NT_>, lds, slices, work, NT_), slices); \
-        hipLaunchKernelGGL((dw_spatial_fwd_kernel<T, 3, ST_, NT_>), grid, dim3(NT_), lds, s, a); } while (0)
     if constexpr (TT<T>::IS_BF16) {
         if (pair) {
-#define DWS_PAIR_LAUNCH(ST_, NT_) do { \
-        dim3 grid(resident_grid_x(dw_spatial_fwd_pair_kernel<ST_, NT_>, lds, slices, work, NT_), slices); \
-        hipLaunchKernelGGL((dw_spatial_fwd_pair_kernel<ST_, NT_>), grid, dim3(NT_), lds, s, a); } while (0)
-            if (a.stride == 1) { if (big) DWS_PAIR_LAUNCH(1, 512); else DWS_PAIR_LAUNCH(1, 256); }
-            else { if (big) DWS_PAIR_LAUNCH(2, 512); else DWS_PAIR_LAUNCH(2, 256); }
-#undef DWS_PAIR_LAUNCH
-            DWN_CHECK_LAUNCH();
-            return 0;
+            if (a.stride == 1) return big ? launch_dw(dw_spatial_fwd_pair_kernel<1, 512>, 512, lds, slices, work, s, a)
+                                          : launch_dw(dw_spatial_fwd_pair_kernel<1, 256>, 256, lds, slices, work, s, a);
+            return big ? launch_dw(dw_spatial_fwd_pair_kernel<2, 512>, 512, lds, slices, work, s, a)
+                       : launch_dw(dw_spatial_fwd_pair_kernel<2, 256>, 256, lds, slices, work, s, a);
         }
     }
-    if (a.stride == 1) { if (big) DWS_FWD_LAUNCH(1, 512); else DWS_FWD_LAUNCH(1, 256); }
-    else if (a.stride == 2) { if (big) DWS_FWD_LAUNCH(2, 512); else DWS_FWD_LAUNCH(2, 256); }
-    else DWS_FWD_LAUNCH(0, 256);
-#undef DWS_FWD_LAUNCH
-    DWN_CHECK_LAUNCH();
-    return 0;
+    if (a.stride == 1) return big ? launch_dw(dw_spatial_fwd_kernel<T, 3, 1, 512>, 512, lds, slices, work, s, a)
+                                  : launch_dw(dw_spatial_fwd_kernel<T, 3, 1, 256>, 256, lds, slices, work, s, a);
+    if (a.stride == 2) return big ? launch_dw(dw_spatial_fwd_kernel<T, 3, 2, 512>, 512, lds, slices, work, s, a)
+                                  : launch_dw(dw_spatial_fwd_kernel<T, 3, 2, 256>, 256, lds, slices, work, s, a);
+    return launch_dw(dw_spatial_fwd_kernel<T, 3, 0, 256>, 256, lds, slices, work, s, a);
 }
 bool dw_spatial_fwd_walk_supported(const DwSpatialFwd& a, int dtype);
 int launch_dw_spatial_fwd_walk(const DwSpatialFwd& a, hipStream_t s);
@@ -1353,12 +1336,10 @@ static int spatial_bwd_t(DwSpatialBwd a, hipStream_t s) {
     const int nbands = (a.Hin + a.rows_band - 1) / a.rows_band;
     const int slices = (a.C + CS - 1) / CS;
     const i64 work = (i64)a.planes * nbands;
-    if (pair) { dim3 grid(resident_grid_x(dw_spatial_bwd_pair_kernel, lds, slices, work, DWS_BWD_THREADS), slices); hipLaunchKernelGGL(dw_spatial_bwd_pair_kernel, grid, dim3(DWS_BWD_THREADS), lds, s, a); }
-    else if (a.stride == 1) { dim3 grid(resident_grid_x(dw_spatial_bwd_kernel<T, 3, 1>, lds, slices, work, DWS_BWD_THREADS), slices); hipLaunchKernelGGL((dw_spatial_bwd_kernel<T, 3, 1>), grid, dim3(DWS_BWD_THREADS), lds, s, a); }
-    else if (a.stride == 2) { dim3 grid(resident_grid_x(dw_spatial_bwd_kernel<T, 3, 2>, lds, slices, work, DWS_BWD_THREADS), slices); hipLaunchKernelGGL((dw_spatial_bwd_kernel<T, 3, 2>), grid, dim3(DWS_BWD_THREADS), lds, s, a); }
-    else { dim3 grid(resident_grid_x(dw_spatial_bwd_kernel<T, 3, 0>, lds, slices, work, DWS_BWD_THREADS), slices); hipLaunchKernelGGL((dw_spatial_bwd_kernel<T, 3, 0>), grid, dim3(DWS_BWD_THREADS), lds, s, a); }
-    DWN_CHECK_LAUNCH();
-    return 0;
+    if (pair) return launch_dw(dw_spatial_bwd_pair_kernel, DWS_BWD_THREADS, lds, slices, work, s, a);
+    if (a.stride == 1) return launch_dw(dw_spatial_bwd_kernel<T, 3, 1>, DWS_BWD_THREADS, lds, slices, work, s, a);
+    if (a.stride == 2) return launch_dw(dw_spatial_bwd_kernel<T, 3, 2>, DWS_BWD_THREADS, lds, slices, work, s, a);
+    return launch_dw(dw_spatial_bwd_kernel<T, 3, 0>, DWS_BWD_THREADS, lds, slices, work, s, a);
 }
 bool dw_spatial_bwd_walk_supported(const DwSpatialBwd& a, int dtype);
 int launch_dw_spatial_bwd_walk(const DwSpatialBwd& a, hipStream_t s);
@@ -1378,17 +1359,13 @@ static int temporal_fwd_t(const DwTemporalFwd& a, hipStream_t s) {
     const i64 work = (npos + LP - 1) / LP;
     if (a.z_scale) {
         if (!a.z_shift || a.stats) return dwn_set_error(-2, "dw_temporal: the z3 epilogue needs z_shift and no statistics (eval mode)");
-        if (a.kt == 5) { dim3 grid(resident_grid_x(dw_temporal_fwd_kernel<T, 5, true>, 0, slices, work), slices); hipLaunchKernelGGL((dw_temporal_fwd_kernel<T, 5, true>), grid, dim3(256), 0, s, a); }
-        else if (a.kt == 3) { dim3 grid(resident_grid_x(dw_temporal_fwd_kernel<T, 3, true>, 0, slices, work), slices); hipLaunchKernelGGL((dw_temporal_fwd_kernel<T, 3, true>), grid, dim3(256), 0, s, a); }
-        else return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
-        DWN_CHECK_LAUNCH();
-        return 0;
+        if (a.kt == 5) return launch_dw(dw_temporal_fwd_kernel<T, 5, true>, 256, 0, slices, work, s, a);
+        if (a.kt == 3) return launch_dw(dw_temporal_fwd_kernel<T, 3, true>, 256, 0, slices, work, s, a);
+        return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
     }
-    if (a.kt == 5) { dim3 grid(resident_grid_x(dw_temporal_fwd_kernel<T, 5>, 0, slices, work), slices); hipLaunchKernelGGL((dw_temporal_fwd_kernel<T, 5>), grid, dim3(256), 0, s, a); }
-    else if (a.kt == 3) { dim3 grid(resident_grid_x(dw_temporal_fwd_kernel<T, 3>, 0, slices, work), slices); hipLaunchKernelGGL((dw_temporal_fwd_kernel<T, 3>), grid, dim3(256), 0, s, a); }
-    else return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
-    DWN_CHECK_LAUNCH();
-    return 0;
+    if (a.kt == 5) return launch_dw(dw_temporal_fwd_kernel<T, 5>, 256, 0, slices, work, s, a);
+    if (a.kt == 3) return launch_dw(dw_temporal_fwd_kernel<T, 3>, 256, 0, slices, work, s, a);
+    return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
 }
 int launch_dw_temporal_fwd(const DwTemporalFwd& a, int dtype, hipStream_t s) {
     return dtype == DWN_BF16 ? temporal_fwd_t<bf16_t>(a, s) : temporal_fwd_t<float>(a, s);
@@ -1553,29 +1530,22 @@ static int temporal_bwd_t(const DwTemporalBwd& a, hipStream_t s) {
     const i64 work = (npos + LP - 1) / LP;
     const bool dy3 = a.dy_kind == LD_DY3;
     if (a.dy_kind == LD_PLAIN) {       // dy.p = dh3 only: y3 is recomputed from y2 (three passes instead of four)
-        if (a.kt == 5) {
-            dim3 grid(resident_grid_x(dw_temporal_bwd_rc_kernel<T, 5>, 0, slices, work), slices);
-            hipLaunchKernelGGL((dw_temporal_bwd_rc_kernel<T, 5>), grid, dim3(256), 0, s, a);
-        } else if (a.kt == 3) {
-            dim3 grid(resident_grid_x(dw_temporal_bwd_rc_kernel<T, 3>, 0, slices, work), slices);
-            hipLaunchKernelGGL((dw_temporal_bwd_rc_kernel<T, 3>), grid, dim3(256), 0, s, a);
-        } else return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
-        DWN_CHECK_LAUNCH();
-        return 0;
+        if (a.kt == 5) return launch_dw(dw_temporal_bwd_rc_kernel<T, 5>, 256, 0, slices, work, s, a);
+        if (a.kt == 3) return launch_dw(dw_temporal_bwd_rc_kernel<T, 3>, 256, 0, slices, work, s, a);
+        return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
     }
-    dim3 grid(resident_grid_x(dw_temporal_bwd_kernel<T, 5, LD_AFFINE2, 4>, 0, slices, work), slices);
     if (!dy3 && a.dy_kind != LD_AFFINE2) return dwn_set_error(-3, "dw_temporal_bwd: unsupported dy loader");
-    constexpr bool tb8 = DWT_BWD_TB == 8;
+    const bool tb8 = DWT_BWD_TB == 8;
     if (a.kt == 5) {
-        if (dy3) hipLaunchKernelGGL((dw_temporal_bwd_kernel<T, 5, LD_DY3, 4>), grid, dim3(256), 0, s, a);
-        else if (tb8) hipLaunchKernelGGL((dw_temporal_bwd_kernel<T, 5, LD_AFFINE2, 8>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((dw_temporal_bwd_kernel<T, 5, LD_AFFINE2, 4>), grid, dim3(256), 0, s, a);
-    } else if (a.kt == 3) {
-        if (dy3) hipLaunchKernelGGL((dw_temporal_bwd_kernel<T, 3, LD_DY3, 4>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((dw_temporal_bwd_kernel<T, 3, LD_AFFINE2, 4>), grid, dim3(256), 0, s, a);
-    } else return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
-    DWN_CHECK_LAUNCH();
-    return 0;
+        if (dy3) return launch_dw(dw_temporal_bwd_kernel<T, 5, LD_DY3, 4>, 256, 0, slices, work, s, a);
+        if (tb8) return launch_dw(dw_temporal_bwd_kernel<T, 5, LD_AFFINE2, 8>, 256, 0, slices, work, s, a);
+        return launch_dw(dw_temporal_bwd_kernel<T, 5, LD_AFFINE2, 4>, 256, 0, slices, work, s, a);
+    }
+    if (a.kt == 3) {
+        if (dy3) return launch_dw(dw_temporal_bwd_kernel<T, 3, LD_DY3, 4>, 256, 0, slices, work, s, a);
+        return launch_dw(dw_temporal_bwd_kernel<T, 3, LD_AFFINE2, 4>, 256, 0, slices, work, s, a);
+    }
+    return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
 }
 int launch_dw_temporal_bwd(const DwTemporalBwd& a, int dtype, hipStream_t s) {
     return dtype == DWN_BF16 ? temporal_bwd_t<bf16_t>(a, s) : temporal_bwd_t<float>(a, s);

@@ -9,6 +9,7 @@
 // sit side by side in one tile.  The stencils are VALU-issue-bound, and a quarter of the pair kernel's instructions were
 // flat-index decodes.  y2 is bit-identical to the pair kernel's.
 #include "dwn_internal.h"
+#include "dwn_launch.h"
 #include <stdlib.h>
 
 extern __shared__ __attribute__((aligned(16))) unsigned char wf_smem[];
@@ -98,16 +99,28 @@ __device__ __forceinline__ void wf_lds_barrier() {
 // three pair columns per row (stride 1: Q_{jj-1}, Q_jj, Q_{jj+1}; stride 2: Q_{2jj-1}, Q_{2jj}, Q_{2jj+1}), four dot products per
 // tap row and channel as before.  Pair columns are 64 dwords apart: a ds_write_b128 group (8 lanes x 16 B) and a ds_read_b128
 // group (16 lanes: 4 + 4 + 8 of two pair columns) each cover distinct banks.
+// The kernel's dynamic LDS, indexed by the kernel and sized by its launcher (launch_fc) from this one description:
+// ring [NG][RQ][NPC][PS] dwords, then (128 input channels) the swizzled W1 slice of the workgroup's 64 channels
+template <int ST, int LPW, int RB, int CIN>
+struct FcLds {
+    static constexpr bool QL = CIN > 0;                  // even-aligned pairs Q_k = (2k, 2k+1) + a zero column on either side
+    static constexpr int NG = 16 / LPW, NPC = ST * LPW + (QL ? 2 : 1);
+    static constexpr int PS = 64;                        // dwords between consecutive pairs of a ring row
+    static constexpr int RQ = ST == 1 ? RB + 2 : 2 * RB + 1;
+    static constexpr int rowdw = NPC * PS;
+    static constexpr bool W1_LDS = CIN > 64;             // W1 fragments: registers at 64 input channels, LDS behind the ring at 128
+    static constexpr unsigned RING_BYTES = (unsigned)NG * RQ * rowdw * 4u;
+    static constexpr unsigned W1_OFF = RING_BYTES, W1_BYTES = W1_LDS ? 64u * CIN * 2u : 0u;
+    static constexpr unsigned TOTAL = W1_OFF + W1_BYTES;
+};
 template <int ST, int LPW, int RB, int CIN>
 __global__ __launch_bounds__(256, CIN > 0 ? (ST * RB <= 4 && CIN <= 64 ? WF_MINW_RC4 : WF_MINW_RC) : WF_MINW) void dw_spatial_fwd_chain_kernel(const DwSpatialFwd a) {
     typedef bf16_t T;
-    constexpr bool QL = CIN > 0;                         // even-aligned pairs Q_k = (2k, 2k+1) + a zero column on either side
-    constexpr int NT = 256, CS = 64, NG = 16 / LPW, NPC = ST * LPW + (QL ? 2 : 1);
-    constexpr int PS = 64;                               // dwords between consecutive pairs of a ring row
+    typedef FcLds<ST, LPW, RB, CIN> L;
+    constexpr bool QL = L::QL;
+    constexpr int NT = 256, CS = 64, NG = L::NG, NPC = L::NPC, PS = L::PS, RQ = L::RQ, rowdw = L::rowdw;
     constexpr int NWC = ST == 1 ? 4 : 2;
     constexpr int NR = ST * RB;                          // input rows staged per chunk
-    constexpr int RQ = ST == 1 ? RB + 2 : 2 * RB + 1;
-    constexpr int rowdw = NPC * PS;
     constexpr int KB = CIN > 0 ? CIN / 32 : 1;
     __shared__ float lstat[2 * CS];
     __shared__ __attribute__((aligned(16))) float lcoef[2 * CS];             // BatchNorm-1 scale, shift (re-read per phase: registers)
@@ -196,8 +209,8 @@ __global__ __launch_bounds__(256, CIN > 0 ? (ST * RB <= 4 && CIN <= 64 ? WF_MINW
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // W1 fragments of this workgroup's 64 channels: registers for CIN = 64 (32 VGPRs); for CIN = 128 a copy of the slice in LDS behind
     // the ring (16 KB, 16-byte chunk c of row r at chunk c ^ ((r >> 2) & 15): conflict-free ds_read_b128 of a fragment)
-    constexpr bool W1_LDS = CIN > 64;
-    constexpr unsigned RING_BYTES = (unsigned)NG * RQ * rowdw * 4u;
+    constexpr bool W1_LDS = L::W1_LDS;
+    constexpr unsigned W1_OFF = L::W1_OFF;
     uint4 wfr[W1_LDS ? 1 : 4][KB];
     if constexpr (CIN > 0) {
         const T* w1 = reinterpret_cast<const T*>(a.w1);
@@ -206,7 +219,7 @@ __global__ __launch_bounds__(256, CIN > 0 ? (ST * RB <= 4 && CIN <= 64 ? WF_MINW
             for (int i = tid; i < 64 * CH; i += NT) {
                 const int r = i / CH, c = i % CH;
                 const int ch = c0 + r;
-                *reinterpret_cast<uint4*>(wf_smem + RING_BYTES + (r * CH + (c ^ ((r >> 2) & 15))) * 16) =
+                *reinterpret_cast<uint4*>(wf_smem + W1_OFF + (r * CH + (c ^ ((r >> 2) & 15))) * 16) =
                     *reinterpret_cast<const uint4*>(w1 + (i64)(ch < a.C ? ch : c0) * CIN + 8 * c);
             }
             __syncthreads();
@@ -228,7 +241,7 @@ __global__ __launch_bounds__(256, CIN > 0 ? (ST * RB <= 4 && CIN <= 64 ? WF_MINW
     auto w1frag = [&](const int n, const int kb) -> uint4 {
         if constexpr (W1_LDS) {
             const int r = 4 * lr + n;
-            return *reinterpret_cast<const uint4*>(wf_smem + RING_BYTES + (r * (CIN / 8) + ((lg + 4 * kb) ^ lr)) * 16);
+            return *reinterpret_cast<const uint4*>(wf_smem + W1_OFF + (r * (CIN / 8) + ((lg + 4 * kb) ^ lr)) * 16);
         } else {
             return wfr[n][kb];
         }
@@ -640,25 +653,13 @@ bool dw_spatial_fwd_rc_walk_supported(const DwSpatialFwd& a, int dtype) {
 
 template <int ST, int LPW, int RB, int CIN>
 static int launch_fc(const DwSpatialFwd& a, hipStream_t s) {
-    constexpr int NG = 16 / LPW, NPC = ST * LPW + (CIN > 0 ? 2 : 1), RQ = ST == 1 ? RB + 2 : 2 * RB + 1;
-    const size_t lds = (size_t)NG * RQ * NPC * 256 + (CIN > 64 ? (size_t)64 * CIN * 2 : 0);
-    auto kern = dw_spatial_fwd_chain_kernel<ST, LPW, RB, CIN>;
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        (void)hipGetLastError();
-    int bpc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kern, 256, lds) != hipSuccess || bpc < 1) { (void)hipGetLastError(); bpc = 2; }
-    const int slices = (a.C + 63) / 64;
-    const i64 work = (a.planes + NG - 1) / NG;
-    i64 gx = (256 * bpc) / slices;
-    if (gx < 1) gx = 1;
-    if (gx > work) gx = work;
-    if (CIN > 0) gx = gx >= 8 ? (gx & ~(i64)7) : 8;   // wf_block<true>: the slices of a plane group share an XCD
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, slices), dim3(256), lds, s, a);
-    DWN_CHECK_LAUNCH();
-    return 0;
+    typedef FcLds<ST, LPW, RB, CIN> L;
+    // fallback 2 workgroups per CU: historical.  CIN > 0: wf_block<true> maps the slices of a plane group to one XCD
+    return launch_resident(dw_spatial_fwd_chain_kernel<ST, LPW, RB, CIN>, 256, L::TOTAL, 2, (a.C + 63) / 64,
+                           (a.planes + L::NG - 1) / L::NG, CIN > 0, s, a);
 }
-// output rows per chunk: a.rows_band, or the measured best at the metric shapes (tools/fwd_chain_check.py).  The rebuilt-input
-// form stages whole input rows per wave: chunks of 4 or 8 input rows
+// output rows per chunk: a.rows_band, or the measured best at the metric shapes (figures: docs/HISTORY.md section 6c).  The
+// rebuilt-input form stages whole input rows per wave: chunks of 4 or 8 input rows
 template <int ST, int LPW, int CIN>
 static int launch_fc_rb(const DwSpatialFwd& a, hipStream_t s) {
     if constexpr (CIN > 0) {

@@ -17,6 +17,7 @@
 //
 // HBM traffic: a0 once per tile (+ band halo rows) and y2 once — instead of (M_in + M_out) E-wide rows.
 #include "dwn_internal.h"
+#include "dwn_launch.h"
 #include <stdlib.h>
 
 extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
@@ -494,15 +495,10 @@ int dwn_dw_spatial_fwd_rc(const dwn_dw_spatial_rc_fwd_args* ap, int device, void
     const int nbands = (x.Hout + R - 1) / R;
     const i64 ntiles = (i64)x.planes * nbands;
     if (ntiles <= 0) return 0;
-#define RC_FWD_LAUNCH4(CIN_, ST_, RND_, MU_, MI_) do { \
-        auto kern = dw_spatial_fwd_rc_kernel<CIN_, ST_, RC_NT, RND_, MU_, MI_>; \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            (void)hipGetLastError(); \
-        int bpc = 0; \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kern, RC_NT, lds) != hipSuccess || bpc < 1) { (void)hipGetLastError(); bpc = 1; } \
-        const i64 cap = (i64)256 * bpc; \
-        dim3 grid((unsigned)(ntiles < cap ? ntiles : cap)); \
-        hipLaunchKernelGGL(kern, grid, dim3(RC_NT), lds, s, k); } while (0)
+    // one workgroup per tile up to one resident round; fallback 1 workgroup per CU when the occupancy query fails (the safe
+    // minimum: such a grid never exceeds the resident slots)
+#define RC_FWD_LAUNCH4(CIN_, ST_, RND_, MU_, MI_) \
+        return launch_resident(dw_spatial_fwd_rc_kernel<CIN_, ST_, RC_NT, RND_, MU_, MI_>, RC_NT, lds, 1, 1, ntiles, false, s, k)
 #define RC_FWD_LAUNCH3(CIN_, ST_, MU_, MI_) do { if (x.round_y1) RC_FWD_LAUNCH4(CIN_, ST_, true, MU_, MI_); else RC_FWD_LAUNCH4(CIN_, ST_, false, MU_, MI_); } while (0)
 #define RC_FWD_LAUNCH(CIN_, ST_) do { if (few_items) RC_FWD_LAUNCH3(CIN_, ST_, RC_MU_A, RC_MI_A); else RC_FWD_LAUNCH3(CIN_, ST_, RC_MU_B, RC_MI_B(CIN_)); } while (0)
     if (x.Cin == 64) { if (x.stride == 1) RC_FWD_LAUNCH(64, 1); else RC_FWD_LAUNCH(64, 2); }
@@ -510,8 +506,6 @@ int dwn_dw_spatial_fwd_rc(const dwn_dw_spatial_rc_fwd_args* ap, int device, void
 #undef RC_FWD_LAUNCH4
 #undef RC_FWD_LAUNCH3
 #undef RC_FWD_LAUNCH
-    DWN_CHECK_LAUNCH();
-    return 0;
 }
 
 }  // extern "C"

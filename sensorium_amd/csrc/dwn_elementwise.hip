@@ -4,6 +4,7 @@
 // Reference call sites are cited per kernel (paths relative to lRomul/sensorium).
 #include "dwn_internal.h"
 #include "dwn_kernels.h"
+#include "dwn_launch.h"
 
 #define NCV 8
 #define DISPATCH_T(dtype, CALL_BF, CALL_F) do { if ((dtype) == DWN_BF16) { CALL_BF; } else { CALL_F; } } while (0)
@@ -50,14 +51,9 @@ __device__ __forceinline__ void slice_stats_flush(float* lstat, const float* s0,
 template <typename K>
 static dim3 resident_slice_grid(K kernel, i64 rows, int C, int KC, int max_bpc = 1 << 20) {
     int slices = (C + NCV * KC - 1) / (NCV * KC);
-    int bpc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kernel, 256, 0) != hipSuccess || bpc < 1) { (void)hipGetLastError(); bpc = 4; }
+    int bpc = resident_bpc(kernel, 256, 0, 4);      // fallback 4: historical (light streaming kernels, capped by max_bpc below)
     if (bpc > max_bpc) bpc = max_bpc;
-    i64 bx = (256 * (i64)bpc) / slices;
-    i64 need = (rows + 31) / 32;
-    if (bx > need) bx = need;
-    if (bx < 1) bx = 1;
-    return dim3((unsigned)bx, (unsigned)slices);
+    return dim3((unsigned)resident_grid_x(bpc, slices, (rows + 31) / 32), (unsigned)slices);
 }
 
 static inline dim3 slice_grid(i64 rows, int C, int KC, int cap = 2048) {
@@ -122,15 +118,9 @@ __device__ __forceinline__ void bn_finalize_train_body(const int blk, const doub
         running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
     }
 }
-__global__ __launch_bounds__(256) void bn_finalize_train_kernel(const double* stats, int stat_c, double count,
-                                                                const float* gamma, const float* beta,
-                                                                float* running_mean, float* running_var, long long* nbt,
-                                                                float momentum, float eps, float* coef, int C) {
-    bn_finalize_train_body(blockIdx.x, stats, stat_c, count, gamma, beta, running_mean, running_var, nbt, momentum, eps, coef, C);
-}
-// two independent BatchNorms in one launch (conv_pwl.1.bn + bn_sc.bn; the cortex pair): every tiny launch costs ~4.5 us
-// of GPU timeline on this part whatever its size
-__global__ __launch_bounds__(256) void bn_finalize_train2_kernel(BnFinJob j0, BnFinJob j1, float momentum, float eps) {
+// Up to two independent BatchNorms per launch (conv_pwl.1.bn + bn_sc.bn; the cortex pair): every tiny launch costs ~4.5 us of GPU
+// timeline on this part whatever its size.  Job 0 owns the first j0.nblocks workgroups, job 1 the rest (nblocks = 0: no second job).
+__global__ __launch_bounds__(256) void bn_finalize_train_kernel(BnFinJob j0, BnFinJob j1, float momentum, float eps) {
     const bool first = (int)blockIdx.x < j0.nblocks;
     const BnFinJob& j = first ? j0 : j1;
     bn_finalize_train_body(first ? blockIdx.x : blockIdx.x - j0.nblocks, j.stats, j.stat_c, j.count, j.gamma, j.beta,
@@ -149,9 +139,12 @@ __global__ void bn_finalize_eval_kernel(const float* gamma, const float* beta, c
     coef[3 * C + c] = invstd;
 }
 
-// backward: stats = [NREP][2][C] with Σdh and Σdh·ŷ.  dy = A1*dh + A2*y + A3 (y raw), dgamma = Σdh·ŷ, dbeta = Σdh
+// backward: stats = [NREP][2][C] with Σdh and Σdh·ŷ.  dy = A1*dh + A2*y + A3 (y raw), dgamma = Σdh·ŷ, dbeta = Σdh.
+// frozen statistics (dwn.h DWN_BN_FROZEN): the forward's BatchNorm was the fixed affine map scale * y + shift, so its backward is
+// dy = scale * dh — the triple (scale, 0, 0) for the same consumers — and dgamma, dbeta come from the same two sums (the producers
+// took ŷ with coef's mean / invstd: the running statistics); count is not read
 __device__ __forceinline__ void bn_bwd_finalize_body(const int blk, const double* stats, double count, const float* coef,
-                                                     float* dgamma, float* dbeta, float* abc, int C) {
+                                                     float* dgamma, float* dbeta, float* abc, int C, const bool frozen) {
     const int r = threadIdx.x & 31;
     const int c = blk * 8 + (threadIdx.x >> 5);
     const bool ok = c < C;
@@ -163,75 +156,26 @@ __device__ __forceinline__ void bn_bwd_finalize_body(const int blk, const double
     if (dbeta) dbeta[c] = (float)s1;
     double m1 = s1 / count, m2 = s2 / count;
     abc[c] = scale;
-    abc[C + c] = (float)(-(double)scale * invstd * m2);
-    abc[2 * C + c] = (float)((double)scale * (-m1 + (double)mean * invstd * m2));
+    abc[C + c] = frozen ? 0.f : (float)(-(double)scale * invstd * m2);
+    abc[2 * C + c] = frozen ? 0.f : (float)((double)scale * (-m1 + (double)mean * invstd * m2));
 }
-__global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const double* stats, double count, const float* coef,
-                                                              float* dgamma, float* dbeta, float* abc, int C) {
-    bn_bwd_finalize_body(blockIdx.x, stats, count, coef, dgamma, dbeta, abc, C);
-}
-__global__ __launch_bounds__(256) void bn_bwd_finalize2_kernel(BnBwdJob j0, BnBwdJob j1) {
+__global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(BnBwdJob j0, BnBwdJob j1) {
     const bool first = (int)blockIdx.x < j0.nblocks;
     const BnBwdJob& j = first ? j0 : j1;
-    bn_bwd_finalize_body(first ? blockIdx.x : blockIdx.x - j0.nblocks, j.stats, j.count, j.coef, j.dgamma, j.dbeta, j.abc, j.C);
+    bn_bwd_finalize_body(first ? blockIdx.x : blockIdx.x - j0.nblocks, j.stats, j.count, j.coef, j.dgamma, j.dbeta, j.abc, j.C,
+                         j.frozen != 0);
 }
 
-// frozen statistics (dwn.h DWN_BN_FROZEN): the forward's BatchNorm was the fixed affine map scale * y + shift, so its backward is
-// dy = scale * dh — the triple (scale, 0, 0) for the same consumers — and dgamma = Σdh·ŷ, dbeta = Σdh come from the same two sums
-// (the producers took ŷ with coef's mean / invstd: the running statistics)
-__device__ __forceinline__ void bn_bwd_finalize_frozen_body(const int blk, const double* stats, const float* coef, float* dgamma,
-                                                            float* dbeta, float* abc, int C) {
-    const int r = threadIdx.x & 31;
-    const int c = blk * 8 + (threadIdx.x >> 5);
-    const bool ok = c < C;
-    double s1, s2;
-    rep_reduce(stats, C, ok ? c : 0, r, ok, s1, s2);
-    if (!ok || r != 0) return;
-    if (dgamma) dgamma[c] = (float)s2;
-    if (dbeta) dbeta[c] = (float)s1;
-    abc[c] = coef[c];
-    abc[C + c] = 0.f;
-    abc[2 * C + c] = 0.f;
-}
-__global__ __launch_bounds__(256) void bn_bwd_finalize_frozen_kernel(const double* stats, const float* coef, float* dgamma,
-                                                                     float* dbeta, float* abc, int C) {
-    bn_bwd_finalize_frozen_body(blockIdx.x, stats, coef, dgamma, dbeta, abc, C);
-}
-__global__ __launch_bounds__(256) void bn_bwd_finalize_frozen2_kernel(BnBwdJob j0, BnBwdJob j1) {
-    const bool first = (int)blockIdx.x < j0.nblocks;
-    const BnBwdJob& j = first ? j0 : j1;
-    bn_bwd_finalize_frozen_body(first ? blockIdx.x : blockIdx.x - j0.nblocks, j.stats, j.coef, j.dgamma, j.dbeta, j.abc, j.C);
-}
-int k_bn_bwd_finalize_frozen(const double* stats, const float* coef, float* dgamma, float* dbeta, float* abc, int C,
-                             hipStream_t s) {
-    hipLaunchKernelGGL(bn_bwd_finalize_frozen_kernel, dim3((C + 7) / 8), dim3(256), 0, s, stats, coef, dgamma, dbeta, abc, C);
-    DWN_CHECK_LAUNCH();
-    return 0;
-}
-int k_bn_bwd_finalize_frozen2(BnBwdJob j0, BnBwdJob j1, hipStream_t s) {
+// a job with C = 0 (BnFinJob{} / BnBwdJob{}) is no job
+int k_bn_finalize_train(BnFinJob j0, BnFinJob j1, float momentum, float eps, hipStream_t s) {
     j0.nblocks = (j0.C + 7) / 8; j1.nblocks = (j1.C + 7) / 8;
-    hipLaunchKernelGGL(bn_bwd_finalize_frozen2_kernel, dim3(j0.nblocks + j1.nblocks), dim3(256), 0, s, j0, j1);
+    hipLaunchKernelGGL(bn_finalize_train_kernel, dim3(j0.nblocks + j1.nblocks), dim3(256), 0, s, j0, j1, momentum, eps);
     DWN_CHECK_LAUNCH();
     return 0;
 }
-
-int k_bn_finalize_train(const double* stats, int stat_c, double count, const float* gamma, const float* beta,
-                        float* rm, float* rv, long long* nbt, float momentum, float eps, float* coef, int C,
-                        hipStream_t s) {
-    hipLaunchKernelGGL(bn_finalize_train_kernel, dim3((C + 7) / 8), dim3(256), 0, s, stats, stat_c, count,
-                       gamma, beta, rm, rv, nbt, momentum, eps, coef, C);
-    DWN_CHECK_LAUNCH();
-    return 0;
-}
-int k_bn_finalize_train2(BnFinJob j0, BnFinJob j1, float momentum, float eps, hipStream_t s) {
+int k_bn_bwd_finalize(BnBwdJob j0, BnBwdJob j1, hipStream_t s) {
     j0.nblocks = (j0.C + 7) / 8; j1.nblocks = (j1.C + 7) / 8;
-    hipLaunchKernelGGL(bn_finalize_train2_kernel, dim3(j0.nblocks + j1.nblocks), dim3(256), 0, s, j0, j1, momentum, eps);
-    DWN_CHECK_LAUNCH();
-    return 0;
-}
-int k_bn_bwd_finalize2(BnBwdJob j0, BnBwdJob j1, hipStream_t s) {
-    j0.nblocks = (j0.C + 7) / 8; j1.nblocks = (j1.C + 7) / 8;
-    hipLaunchKernelGGL(bn_bwd_finalize2_kernel, dim3(j0.nblocks + j1.nblocks), dim3(256), 0, s, j0, j1);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(j0.nblocks + j1.nblocks), dim3(256), 0, s, j0, j1);
     DWN_CHECK_LAUNCH();
     return 0;
 }
@@ -239,13 +183,6 @@ int k_bn_finalize_eval(const float* gamma, const float* beta, const float* rm, c
                        float* coef, int C, hipStream_t s) {
     hipLaunchKernelGGL(bn_finalize_eval_kernel, dim3((C + 255) / 256), dim3(256), 0, s, gamma, beta, rm, rv, eps,
                        coef, C);
-    DWN_CHECK_LAUNCH();
-    return 0;
-}
-int k_bn_bwd_finalize(const double* stats, double count, const float* coef, float* dgamma, float* dbeta,
-                      float* abc, int C, hipStream_t s) {
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 7) / 8), dim3(256), 0, s, stats, count, coef, dgamma,
-                       dbeta, abc, C);
     DWN_CHECK_LAUNCH();
     return 0;
 }
@@ -2195,18 +2132,6 @@ int k_gate_weights(const float* w, const float* gate, void* dst, int B, int N, i
     DISPATCH_T(dtype,
         hipLaunchKernelGGL((gate_weights_kernel<bf16_t>), grid, dim3(256), 0, s, w, gate, (bf16_t*)dst, N, K),
         hipLaunchKernelGGL((gate_weights_kernel<float>), grid, dim3(256), 0, s, w, gate, (float*)dst, N, K));
-    DWN_CHECK_LAUNCH();
-    return 0;
-}
-// depth-wise weights: reference layout [C][taps] -> tap-major [taps][C] fp32
-__global__ void pack_dw_kernel(const float* src, float* dst, int C, int taps) {
-    int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= C * taps) return;
-    int k = idx / C, c = idx % C;
-    dst[idx] = src[c * taps + k];
-}
-int k_pack_dw(const float* src, float* dst, int C, int taps, hipStream_t s) {
-    hipLaunchKernelGGL(pack_dw_kernel, dim3((C * taps + 255) / 256), dim3(256), 0, s, src, dst, C, taps);
     DWN_CHECK_LAUNCH();
     return 0;
 }

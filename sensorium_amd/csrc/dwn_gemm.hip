@@ -18,6 +18,7 @@
 // mode, bit-exact fp32 FMA chain).  Operand maps (cdna_hip_programming.md §3): lane l holds
 // A[row l&15][k = 8*(l>>4)+j], B[k = 8*(l>>4)+j][col l&15]; C/D: col = l&15, row = 4*(l>>4)+reg.
 #include "dwn_internal.h"
+#include "dwn_launch.h"
 #include <type_traits>
 int k_zero(void* p, size_t nbytes, hipStream_t s);        // dwn_elementwise.hip
 
@@ -771,9 +772,8 @@ static int launch_nn_k(const GemmNN& g, hipStream_t s) {
     const int ntn = (g.N + BNv - 1) / BNv;
     // persistent grid = exactly the resident workgroups (256 CUs x blocks/CU from the occupancy query: the unified
     // VGPR+AGPR budget decides, not the arch-VGPR count); every workgroup gets a contiguous range of M-tiles
-    int bpc = 0;
-    hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, gemm_nn_kernel<T, ALD, EPI, BNv, SINGLE>, 256, 0);
-    if (oe != hipSuccess || bpc < 1) { (void)hipGetLastError(); bpc = 1; }
+    // (fallback 1, here and in launch_tn_t: the safe minimum — such a grid never exceeds the resident slots)
+    const int bpc = resident_bpc(gemm_nn_kernel<T, ALD, EPI, BNv, SINGLE>, 256, 0, 1);
     // never more workgroups than resident slots (a second partial wave of persistent workgroups doubles the
     // kernel time); nranges * ntn must be a multiple of 8 for the XCD-major logical id
     int nranges = (256 * bpc) / (ntn * g.groups);
@@ -1123,11 +1123,7 @@ static int launch_tn_t(const GemmTN& g_in, hipStream_t s) {
     GemmTN g = g_in;
     if (g.rows_per_sample > 0) {
         if (g.groups != 1 || g.M % g.rows_per_sample) return dwn_set_error(-2, "gemm_tn: per-sample mode needs groups == 1 and M % rows_per_sample == 0");
-        int bpc = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, gemm_tn_kernel<T, PLD, QLD>, 256, 0) != hipSuccess || bpc < 1) {
-            (void)hipGetLastError();
-            bpc = 1;
-        }
+        int bpc = resident_bpc(gemm_tn_kernel<T, PLD, QLD>, 256, 0, 1);
         const int nb = g.M / g.rows_per_sample;
         const int tiles = ((g.R + 127) / 128) * ((g.Cc + 127) / 128);
         if (bpc > TN_SLOTS) bpc = TN_SLOTS;
@@ -1143,11 +1139,7 @@ static int launch_tn_t(const GemmTN& g_in, hipStream_t s) {
     } else if (g.nsplit <= 0) {
         // one resident round: tiles x splits = the workgroups the chip holds at once (a partial second round costs a
         // whole workgroup duration, and every split adds 64 KB of fp32 atomics per tile)
-        int bpc = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, gemm_tn_kernel<T, PLD, QLD>, 256, 0) != hipSuccess || bpc < 1) {
-            (void)hipGetLastError();
-            bpc = 1;
-        }
+        int bpc = resident_bpc(gemm_tn_kernel<T, PLD, QLD>, 256, 0, 1);
         if (bpc > TN_SLOTS) bpc = TN_SLOTS;
         if (g.dw_f64 && bpc > TN_F64_SLOTS) bpc = TN_F64_SLOTS;      // every split adds one fp64 atomic per output element, all to the same addresses
         const int tiles = ((g.R + 127) / 128) * ((g.Cc + 127) / 128) * g.groups;
@@ -1488,7 +1480,7 @@ static int launch_pw_bwd_fused_t(const void* dh1, const void* a0, const void* bp
                                  long long M, const void* res, const float* res_coef, int res_n, const PwbGather& gq, hipStream_t s) {
     auto kern = pw_bwd_fused_kernel<NKC>;
     {   // > 64 KB of dynamic LDS needs the opt-in; per device, so it is (cheaply) repeated on every call
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, pwb::Cfg<NKC>::LDS_BYTES);
+        hipError_t e = lds_opt_in(kern, pwb::Cfg<NKC>::LDS_BYTES);
         if (e != hipSuccess) return dwn_set_error((int)e, hipGetErrorString(e));
     }
     int grid = 256;

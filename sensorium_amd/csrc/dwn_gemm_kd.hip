@@ -20,6 +20,7 @@
 // accumulates the next BatchNorm's sums from the rounded values (one flush per workgroup: LDS atomics, then fp64 atomics into
 // the DWN_NREP replicas).  Results equal gemm_nn_kernel's to the bit (same k order, same roundings): tests/test_gpu_gemm.py.
 #include "dwn_internal.h"
+#include "dwn_launch.h"
 #include <type_traits>
 
 #ifndef KD_FRG
@@ -297,8 +298,8 @@ static int launch_kd_t(const KdArgs& a, hipStream_t s) {
     const size_t smem = 2 * (size_t)BN * 64 + 64 * ((size_t)BN * 2 + 16) + 2 * (size_t)BN * 4 + (GATE ? (size_t)a.K * 4 : 0);
     // per launch: the attribute belongs to the (function, device) pair and the API takes a device argument (a process-wide flag left
     // a second device without it); the call is a host-side table write
-    if (smem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kd_kernel<BN, RT, GATE, CAT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    {
+        hipError_t e = lds_opt_in(gemm_kd_kernel<BN, RT, GATE, CAT>, smem);
         if (e != hipSuccess) return dwn_set_error((int)e, hipGetErrorString(e));
     }
     const unsigned tiles = (unsigned)a.ntm * (unsigned)a.ntn;

@@ -21,6 +21,7 @@
 // a tile that does not fit the LDS; the next lever is keeping the weight operand in registers across k-steps.
 // MFMA operand roles as in dwn_gemm.hip (weights = A operand): acc[i][j][r] = C[m = i*16 + lr][n = j*16 + 4*lg + r].
 #include "dwn_internal.h"
+#include "dwn_launch.h"
 #include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(8))) short xl_bf16x8_t;
@@ -310,14 +311,12 @@ int launch_gemm_nn_xl(const GemmNN& g, hipStream_t s) {
     if (wide) {
         constexpr size_t lds = 2 * (256 * 128 + 256 * 128) + 2 * 256 * sizeof(float);
         auto kern = gemm_nn_xl_kernel<256>;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            (void)hipGetLastError();
+        if (lds_opt_in(kern, lds) != hipSuccess) (void)hipGetLastError();     // the launch reports it
         hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a);
     } else {
         constexpr size_t lds = 2 * (256 * 128 + 128 * 128) + 2 * 128 * sizeof(float);
         auto kern = gemm_nn_xl_kernel<128>;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            (void)hipGetLastError();
+        if (lds_opt_in(kern, lds) != hipSuccess) (void)hipGetLastError();     // the launch reports it
         hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a);
     }
     DWN_CHECK_LAUNCH();

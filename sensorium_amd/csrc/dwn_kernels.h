@@ -14,19 +14,13 @@ struct BnFinJob {
     const double* stats; int stat_c; double count; const float* gamma; const float* beta;
     float* running_mean; float* running_var; long long* nbt; float* coef; int C; int nblocks;
 };
-struct BnBwdJob { const double* stats; double count; const float* coef; float* dgamma; float* dbeta; float* abc; int C; int nblocks; };
-int k_bn_finalize_train2(BnFinJob j0, BnFinJob j1, float momentum, float eps, hipStream_t s);
-int k_bn_bwd_finalize2(BnBwdJob j0, BnBwdJob j1, hipStream_t s);
-int k_bn_finalize_train(const double* stats, int stat_c, double count, const float* gamma, const float* beta,
-                        float* rm, float* rv, long long* nbt, float momentum, float eps, float* coef, int C,
-                        hipStream_t s);
+// frozen (dwn.h DWN_BN_FROZEN): abc = (scale, 0, 0), dgamma / dbeta from the same sums; count is not read
+struct BnBwdJob { const double* stats; double count; const float* coef; float* dgamma; float* dbeta; float* abc; int C; int nblocks; int frozen; };
+// one or two BatchNorms per launch: a job with C = 0 (BnFinJob{} / BnBwdJob{}) is no job; nblocks is the launcher's
+int k_bn_finalize_train(BnFinJob j0, BnFinJob j1, float momentum, float eps, hipStream_t s);
+int k_bn_bwd_finalize(BnBwdJob j0, BnBwdJob j1, hipStream_t s);
 int k_bn_finalize_eval(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
                        float* coef, int C, hipStream_t s);
-int k_bn_bwd_finalize(const double* stats, double count, const float* coef, float* dgamma, float* dbeta, float* abc,
-                      int C, hipStream_t s);
-// frozen statistics (dwn.h DWN_BN_FROZEN): abc = (scale, 0, 0), dgamma / dbeta from the same sums; job.count is not read
-int k_bn_bwd_finalize_frozen(const double* stats, const float* coef, float* dgamma, float* dbeta, float* abc, int C, hipStream_t s);
-int k_bn_bwd_finalize_frozen2(BnBwdJob j0, BnBwdJob j1, hipStream_t s);
 // BatchNorm-1 statistics from the Gram matrix of the block input (y1 never materialised; dwn_elementwise.hip)
 int k_bn1_gram_finalize(const double* gram, const float* w1, int E, int Cin, double count, const float* gamma, const float* beta,
                         float* rm, float* rv, long long* nbt, float momentum, float eps, float* coef, double* sc_stats, int dtype,
@@ -88,7 +82,6 @@ int k_cortex_bwd_dx(const void* dxmain, const void* x, const void* dout, const f
                     const float* abcsc, int M, int Tn, int Cin, int C, void* dx, int dtype, hipStream_t s);
 int k_pack_weight(const float* src, void* dst, int groups, int R, int C, int transpose, int Rd, int Cd, int dtype,
                   hipStream_t s);
-int k_pack_dw(const float* src, float* dst, int C, int taps, hipStream_t s);
 int k_gate_weights(const float* w, const float* gate, void* dst, int B, int N, int K, int dtype, hipStream_t s);
 int k_readout_dz(const float* dout, const float* out, float beta, int B, int Tn, int n_valid, int Rg, int Rp,
                  int groups, void* dz, float* db, int dtype, hipStream_t s);
