@@ -344,6 +344,26 @@ typedef struct dwn_tensor_entry {
     long long numel; int is_int64; int pad_;
 } dwn_tensor_entry;
 
+/* ---- guarded optimizer step: global gradient-norm clipping and the skip of a step with a non-finite gradient,
+ * both decided on the device — no host read-back, capturable in a hipGraph.
+ * dwn_guarded_entry = the fields of dwn_tensor_entry + the parameter's own step count in DEVICE memory (as torch's fused AdamW
+ * keeps it under found_inf): the host cannot know whether a step was skipped, so it cannot count. */
+typedef struct dwn_guarded_entry {
+    float* param; const float* grad; float* exp_avg; float* exp_avg_sq; float* ema;
+    long long numel; int is_int64; int pad_;
+    long long* step;                        /* one int64 per parameter (distinct words within a call); may be null for
+                                             * dwn_grad_sumsq_multi, which reads grad and numel only */
+} dwn_guarded_entry;
+/* device-resident; zeroed once by the caller, then written by dwn_step_guard_finalize alone */
+typedef struct dwn_step_guard {
+    double norm;                            /* sqrt of the summed squares of grad_scale * g over all finite elements */
+    float coef;                             /* min(1, max_norm / (norm + 1e-6)) (torch clip_grad_norm_), 1 when clipping is off */
+    int skip;                               /* 1 iff skip_nonfinite and nonfinite > 0 */
+    long long nonfinite;                    /* Inf / NaN elements among the gradients of this step */
+    long long good_steps, skipped_steps;    /* running totals over the calls of dwn_step_guard_finalize */
+} dwn_step_guard;
+#define DWN_GS_SEG 1024                     /* tensors per sum-of-squares launch (a longer table takes several, one fold) */
+
 /* ---- batch assembly on the device --------------------------------------------------------
  * A trial stays resident in HBM in the reference's on-disk layout (src/datasets.py:37-51, src/data.py:59-70):
  * video [H0][W0][L] (uint8 or float32), behavior [2][L], pupil_center [2][L], responses [N][L] (float32).
@@ -470,6 +490,32 @@ int dwn_adamw_ema_multi(const dwn_tensor_entry* list, int ntensors, int max_bloc
                         double grad_scale, int device, void* stream);
 int dwn_ema_lerp_multi(const dwn_tensor_entry* list, int ntensors, int max_blocks, double decay, int device,
                        void* stream);
+
+/* Guarded step, three calls on one stream (all tables, pairs, the workspace and the guard are DEVICE memory; argument errors are
+ * answered with a negative code before anything touches a device):
+ *
+ * dwn_grad_sumsq_multi: pair[0] = sum over all entries of (grad_scale * g)^2, accumulated in float64 (the square of a float32 is
+ *   exact in double: gradients of 3e25 give a finite sum); pair[1] = the number of elements that are not finite, as a double.
+ *   Non-finite elements are counted and left out of the sum.  Entries with a null grad or numel <= 0 contribute nothing; grad may
+ *   start at any 4-byte boundary (float4 loads behind a scalar head, scalar tail).  Two stages in a fixed order — max_blocks
+ *   workgroups write one partial each into `ws` by a plain store, a one-workgroup launch folds them — without atomics: the same
+ *   table and max_blocks give the same bits on every launch, in the deterministic build as well.  `ws` holds
+ *   dwn_grad_guard_workspace_bytes(ntensors, max_blocks) bytes, 16-byte aligned.  1 <= max_blocks <= 65536.
+ * dwn_step_guard_finalize: adds pair_a and the optional pair_b (the sharded slices' sum after its all-reduce; null otherwise),
+ *   writes *guard (see dwn_step_guard; max_norm <= 0 = no clipping) and, unless the step is skipped, adds 1 to the step counter of
+ *   each of the ntensors entries of `list` (null list with ntensors = 0: no counters).
+ * dwn_adamw_ema_multi_guarded: dwn_adamw_ema_multi with the gradient factor grad_scale * guard->coef and each entry's step count
+ *   read from the device (already advanced; 1 - beta^t, lr / bc1 and sqrt(bc2) formed in double and cast to float as there;
+ *   entries of different counts ride in one launch).  With guard->skip set, param, exp_avg, exp_avg_sq are not written and the
+ *   EMA leg still runs on the unchanged parameter (the reference's GradScaler skips optimizer.step, ModelEma.update runs anyway). */
+size_t dwn_grad_guard_workspace_bytes(int ntensors, int max_blocks);
+int dwn_grad_sumsq_multi(const dwn_guarded_entry* list, int ntensors, int max_blocks, double grad_scale, void* ws,
+                         size_t ws_bytes, double* pair, int device, void* stream);
+int dwn_step_guard_finalize(const double* pair_a, const double* pair_b, double max_norm, int skip_nonfinite,
+                            const dwn_guarded_entry* list, int ntensors, dwn_step_guard* guard, int device, void* stream);
+int dwn_adamw_ema_multi_guarded(const dwn_guarded_entry* list, int ntensors, int max_blocks, double lr, double beta1,
+                                double beta2, double eps, double weight_decay, double ema_decay, double grad_scale,
+                                const dwn_step_guard* guard, int device, void* stream);
 
 
 /* conv_pw backward (dwiseneuro.py:90-93 backward) WITHOUT reading y1.  With the BatchNorm-1 backward affine

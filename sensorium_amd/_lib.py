@@ -152,6 +152,16 @@ class TensorEntry(C.Structure):
                 ("numel", c_ll), ("is_int64", c_i), ("pad_", c_i)]
 
 
+class GuardedEntry(C.Structure):           # TensorEntry + the parameter's device-resident step count (guarded step)
+    _fields_ = [("param", c_p), ("grad", c_p), ("exp_avg", c_p), ("exp_avg_sq", c_p), ("ema", c_p),
+                ("numel", c_ll), ("is_int64", c_i), ("pad_", c_i), ("step", c_p)]
+
+
+class StepGuard(C.Structure):
+    _fields_ = [("norm", c_d), ("coef", c_f), ("skip", c_i), ("nonfinite", c_ll), ("good_steps", c_ll),
+                ("skipped_steps", c_ll)]
+
+
 class ClipSrc(C.Structure):
     _fields_ = [("video", c_p), ("behavior", c_p), ("pupil_center", c_p), ("responses", c_p), ("length", c_ll),
                 ("video_dtype", c_i), ("frame_start", c_i), ("frame_step", c_i), ("valid", c_i)]
@@ -186,6 +196,7 @@ _STRUCTS = {
     "dwn_cortex_args": CortexArgs, "dwn_readout_args": ReadoutArgs, "dwn_tensor_entry": TensorEntry,
     "dwn_clip_src": ClipSrc, "dwn_clip_desc": ClipDesc, "dwn_pw_bwd_args": PwBwdArgs,
     "dwn_dw_spatial_rc_fwd_args": DwSpatialRcFwdArgs, "dwn_stem_input_grad_args": StemInputGradArgs,
+    "dwn_guarded_entry": GuardedEntry, "dwn_step_guard": StepGuard,
 }
 
 # every symbol include/dwn.h declares: (restype, argtypes)
@@ -231,6 +242,10 @@ SYMBOLS = {
     "dwn_f64_to_f32": (c_i, [c_p, c_p, c_i, c_i, c_p]),
     "dwn_adamw_ema_multi": (c_i, [c_p, c_i, c_i, c_d, c_d, c_d, c_d, c_d, c_ll, c_d, c_d, c_i, c_p]),
     "dwn_ema_lerp_multi": (c_i, [c_p, c_i, c_i, c_d, c_i, c_p]),
+    "dwn_grad_guard_workspace_bytes": (c_sz, [c_i, c_i]),
+    "dwn_grad_sumsq_multi": (c_i, [c_p, c_i, c_i, c_d, c_p, c_sz, c_p, c_i, c_p]),
+    "dwn_step_guard_finalize": (c_i, [c_p, c_p, c_d, c_i, c_p, c_i, c_p, c_i, c_p]),
+    "dwn_adamw_ema_multi_guarded": (c_i, [c_p, c_i, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_d, c_p, c_i, c_p]),
     "dwn_conv_pw_bn_stats_workspace_bytes": (c_sz, [c_i]),
     "dwn_conv_pw_bn_stats": (c_i, [c_p, c_ll, c_ll, c_p, c_i, c_i, _P(BN), c_f, c_f, c_p, c_p, c_sz, c_i, c_i, c_p]),
     "dwn_pw_bwd_fused_supported": (c_i, [c_i, c_ll, c_i, c_i]),
@@ -271,8 +286,9 @@ def _load():
     lib = C.CDLL(str(LIB_PATH), mode=getattr(os, "RTLD_NOW", 2))
     ab = bool(os.environ.get("DWN_LIB_PATH"))      # an explicitly chosen other build: a same-box A/B run of an older library
     for name, (restype, argtypes) in SYMBOLS.items():
-        if ab and name in ("dwn_stem_input_grad", "dwn_stem_backward_input") and not hasattr(lib, name):
-            continue                     # (A/B: a library from before the input gradients; the training step does not call them)
+        if ab and name in ("dwn_stem_input_grad", "dwn_stem_backward_input", "dwn_grad_guard_workspace_bytes", "dwn_grad_sumsq_multi",
+                           "dwn_step_guard_finalize", "dwn_adamw_ema_multi_guarded") and not hasattr(lib, name):
+            continue                     # (A/B: a library from before the input gradients / the guarded step; the plain training step calls neither)
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -284,7 +300,7 @@ def _load():
                           f"`make -C {LIB_PATH.parent}` — binaries are not in git, so what runs must be what is committed")
     for cname, struct in _STRUCTS.items():
         n = lib.dwn_sizeof(cname.encode())
-        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname == "dwn_stem_input_grad_args")):      # (A/B: ABI 7 only appended)
+        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard"))):      # (A/B: ABI 7 only appended)
             raise ImportError(f"struct layout mismatch for {cname}: C {n} bytes vs ctypes {C.sizeof(struct)}")
     return lib
 

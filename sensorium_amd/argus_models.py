@@ -165,6 +165,7 @@ class MouseModel(Model):
         self.optimizer = MouseModel.optimizer[oname](params, **okwargs)
         if self.buckets is not None and self.buckets.shard:
             self.optimizer.set_shard_map(self.buckets.owned_range)
+            self.optimizer.set_guard_group(self.buckets.pg)    # guarded step: the owned slices' part of the norm is summed over it
         if self._model_ema is not None:
             self._bind_ema_to_optimizer()
         pending = getattr(self, "_pending_optimizer_state", None)

@@ -307,7 +307,7 @@ int dwn_sizeof(const char* name) {
     SZ(dwn_dw_spatial_bwd_args); SZ(dwn_dw_temporal_fwd_args); SZ(dwn_dw_temporal_bwd_args); SZ(dwn_bn);
     SZ(dwn_stem_args); SZ(dwn_block_args); SZ(dwn_pool_args); SZ(dwn_cortex_args); SZ(dwn_readout_args);
     SZ(dwn_tensor_entry); SZ(dwn_clip_src); SZ(dwn_clip_desc); SZ(dwn_pw_bwd_args); SZ(dwn_dw_spatial_rc_fwd_args);
-    SZ(dwn_stem_input_grad_args);
+    SZ(dwn_stem_input_grad_args); SZ(dwn_guarded_entry); SZ(dwn_step_guard);
 #undef SZ
     return -1;
 }
@@ -1070,6 +1070,49 @@ int dwn_ema_lerp_multi(const dwn_tensor_entry* list, int ntensors, int max_block
                        void* stream) {
     ENTER(device);
     return k_ema_lerp(list, ntensors, max_blocks, (float)decay, (float)(1.0 - decay), (hipStream_t)stream);
+}
+
+// ---- guarded step: the argument checks need no device
+size_t dwn_grad_guard_workspace_bytes(int ntensors, int max_blocks) {
+    if (ntensors < 0 || max_blocks < 1) return 0;
+    const size_t nseg = ntensors == 0 ? 1 : ((size_t)ntensors + DWN_GS_SEG - 1) / DWN_GS_SEG;
+    return nseg * (size_t)max_blocks * 16;
+}
+int dwn_grad_sumsq_multi(const dwn_guarded_entry* list, int ntensors, int max_blocks, double grad_scale, void* ws,
+                         size_t ws_bytes, double* pair, int device, void* stream) {
+    g_err[0] = 0;
+    if (ntensors < 0) return dwn_set_error(-2, "grad_sumsq_multi: ntensors < 0");
+    if (max_blocks < 1 || max_blocks > 65536) return dwn_set_error(-2, "grad_sumsq_multi: 1 <= max_blocks <= 65536");
+    if (!list && ntensors > 0) return dwn_set_error(-1, "grad_sumsq_multi: null table");
+    if (!ws || !pair) return dwn_set_error(-1, "grad_sumsq_multi: null pointer (ws, pair)");
+    if (((size_t)ws & 15) || ((size_t)pair & 7)) return dwn_set_error(-2, "grad_sumsq_multi: ws 16-byte, pair 8-byte aligned");
+    if (ws_bytes < dwn_grad_guard_workspace_bytes(ntensors, max_blocks)) return dwn_set_error(-6, "grad_sumsq_multi: workspace too small");
+    ENTER(device);
+    return k_grad_sumsq(list, ntensors, max_blocks, grad_scale, ws, pair, (hipStream_t)stream);
+}
+int dwn_step_guard_finalize(const double* pair_a, const double* pair_b, double max_norm, int skip_nonfinite,
+                            const dwn_guarded_entry* list, int ntensors, dwn_step_guard* guard, int device, void* stream) {
+    g_err[0] = 0;
+    if (ntensors < 0) return dwn_set_error(-2, "step_guard_finalize: ntensors < 0");
+    if (!guard) return dwn_set_error(-1, "step_guard_finalize: null guard");
+    if (!pair_a) return dwn_set_error(-1, "step_guard_finalize: null pair_a");
+    if (!list && ntensors > 0) return dwn_set_error(-1, "step_guard_finalize: null table");
+    if (!(max_norm == max_norm)) return dwn_set_error(-2, "step_guard_finalize: max_norm is NaN");
+    ENTER(device);
+    return k_step_guard_finalize(pair_a, pair_b, max_norm, skip_nonfinite ? 1 : 0, list, ntensors, guard, (hipStream_t)stream);
+}
+int dwn_adamw_ema_multi_guarded(const dwn_guarded_entry* list, int ntensors, int max_blocks, double lr, double beta1,
+                                double beta2, double eps, double weight_decay, double ema_decay, double grad_scale,
+                                const dwn_step_guard* guard, int device, void* stream) {
+    g_err[0] = 0;
+    if (ntensors < 0) return dwn_set_error(-2, "adamw_ema_multi_guarded: ntensors < 0");
+    if (max_blocks < 1 || max_blocks > 65535 || ntensors > 65535)
+        return dwn_set_error(-2, "adamw_ema_multi_guarded: max_blocks and ntensors are grid dimensions (1 <= max_blocks, both <= 65535)");
+    if (!list && ntensors > 0) return dwn_set_error(-1, "adamw_ema_multi_guarded: null table");
+    if (!guard) return dwn_set_error(-1, "adamw_ema_multi_guarded: null guard");
+    ENTER(device);
+    return k_adamw_ema_guarded(list, ntensors, max_blocks, lr, beta1, beta2, eps, weight_decay, ema_decay, grad_scale, guard,
+                               (hipStream_t)stream);
 }
 
 int dwn_pw_bwd_fused_supported(int dtype, long long M, int E, int Cin) {

@@ -2370,6 +2370,217 @@ int k_ema_lerp(const TensorListEntry* list, int ntensors, int max_blocks, float 
 }
 
 // ------------------------------------------------------------------------------------------------
+// guarded step: the squared norm and the non-finite count of all gradients stay on the device, a one-workgroup
+// finaliser turns them into the clip coefficient and the skip decision, and the guarded AdamW/EMA kernel reads both from there.
+// No atomics and no "last workgroup" tail: per-workgroup partials by plain stores, a second launch folds them in a fixed order,
+// so the result is the same bits on every launch, in the ordered build as in this one.
+// ------------------------------------------------------------------------------------------------
+// Work is cut into chunks of GS_VEC float4 (+ the unaligned head in a tensor's first chunk and the scalar tail in its last); the
+// chunks of all tensors of a segment are numbered through, and every workgroup takes a contiguous run of them: a 1-element tensor
+// and a 16 M-element readout weight share one table without idle workgroups.
+constexpr int GS_VEC = 1024;                               // float4 per chunk: 4 per lane
+struct GsPartial { double sumsq; long long nonfinite; };
+
+__device__ __forceinline__ int gs_head(const float* g, i64 numel) {           // floats in front of the first 16-byte boundary
+    const i64 h = (i64)(((16 - ((size_t)g & 15)) & 15) >> 2);
+    return (int)(h < numel ? h : numel);
+}
+__device__ __forceinline__ int gs_chunks(const float* g, i64 numel) {
+    if (!g || numel <= 0) return 0;
+    const i64 nvec = (numel - gs_head(g, numel)) >> 2;
+    const i64 c = (nvec + GS_VEC - 1) / GS_VEC;
+    return (int)(c > 0 ? c : 1);
+}
+__device__ __forceinline__ void gs_take(float x, double& acc, int& bad) {
+    const bool fin = (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u;
+    const double d = fin ? (double)x : 0.0;
+    acc = fma(d, d, acc);                                  // the square of a float is exact in double
+    bad += fin ? 0 : 1;
+}
+// workgroup sum in a fixed order: butterfly inside each wave, the four wave results through LDS, added by one lane
+__device__ __forceinline__ void gs_block_sum(double& acc, long long& bad, double* lds_s, long long* lds_c) {
+    for (int o = 32; o > 0; o >>= 1) {
+        acc += __shfl_xor(acc, o, 64);
+        bad += __shfl_xor(bad, o, 64);
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { lds_s[wave] = acc; lds_c[wave] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int nw = blockDim.x >> 6;
+        acc = lds_s[0]; bad = lds_c[0];
+        for (int w = 1; w < nw; ++w) { acc += lds_s[w]; bad += lds_c[w]; }
+    }
+}
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const dwn_guarded_entry* list, int ntensors, GsPartial* partial) {
+    __shared__ int pre[DWN_GS_SEG + 1];                    // exclusive prefix of the chunk counts
+    __shared__ int wsum[4];
+    __shared__ double lds_s[4];
+    __shared__ long long lds_c[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // every lane counts the chunks of four consecutive tensors; inclusive scan over the 256 lane sums
+    int c[4], mine = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int t = tid * 4 + j;
+        c[j] = t < ntensors ? gs_chunks(list[t].grad, list[t].numel) : 0;
+        mine += c[j];
+    }
+    int inc = mine;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += up;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int base = inc - mine;
+    for (int w = 0; w < wave; ++w) base += wsum[w];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (tid * 4 + j < ntensors) pre[tid * 4 + j] = base;
+        base += c[j];
+    }
+    const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (tid == 0) pre[ntensors] = total;
+    __syncthreads();
+
+    const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
+    const i64 beg64 = (i64)blockIdx.x * per;
+    const int beg = (int)(beg64 < total ? beg64 : total);
+    const int end = beg + per < total ? beg + per : total;
+    double acc = 0.0;
+    int bad = 0;
+    if (beg < end) {
+        int lo = 0, hi = ntensors - 1;                     // the last tensor whose first chunk is <= beg and that has chunks
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (pre[mid] <= beg) lo = mid; else hi = mid - 1;
+        }
+        int t = lo;
+        for (int ch = beg; ch < end; ++ch) {
+            while (ch >= pre[t + 1]) ++t;                  // (skips tensors without chunks as well)
+            const float* g = list[t].grad;
+            const i64 numel = list[t].numel;
+            const int h = gs_head(g, numel);
+            const i64 nvec = (numel - h) >> 2;
+            const int k = ch - pre[t];
+            const float4* gv = reinterpret_cast<const float4*>(g + h);
+            float4 x[4];
+            const i64 v0 = (i64)k * GS_VEC + tid;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const i64 v = v0 + j * 256;
+                x[j] = v < nvec ? gv[v] : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { gs_take(x[j].x, acc, bad); gs_take(x[j].y, acc, bad); gs_take(x[j].z, acc, bad); gs_take(x[j].w, acc, bad); }
+            if (k == 0 && tid < h) gs_take(g[tid], acc, bad);
+            if (ch + 1 == pre[t + 1]) {                    // the tensor's last chunk: the 0-3 floats behind the last float4
+                const i64 i = (i64)h + nvec * 4 + tid;
+                if (i < numel) gs_take(g[i], acc, bad);
+            }
+        }
+    }
+    long long bad64 = bad;
+    gs_block_sum(acc, bad64, lds_s, lds_c);
+    if (tid == 0) { GsPartial p; p.sumsq = acc; p.nonfinite = bad64; partial[blockIdx.x] = p; }
+}
+// one workgroup: the partials in index order per lane, then the same fixed tree; pair = [grad_scale^2 * sum, count]
+__global__ __launch_bounds__(256) void grad_sumsq_fold_kernel(const GsPartial* partial, int npartial, double scale_sq, double* pair) {
+    __shared__ double lds_s[4];
+    __shared__ long long lds_c[4];
+    double acc = 0.0;
+    long long bad = 0;
+    for (int i = threadIdx.x; i < npartial; i += 256) { acc += partial[i].sumsq; bad += partial[i].nonfinite; }
+    gs_block_sum(acc, bad, lds_s, lds_c);
+    if (threadIdx.x == 0) { pair[0] = acc * scale_sq; pair[1] = (double)bad; }
+}
+int k_grad_sumsq(const dwn_guarded_entry* list, int ntensors, int max_blocks, double grad_scale, void* ws, double* pair,
+                 hipStream_t s) {
+    GsPartial* partial = reinterpret_cast<GsPartial*>(ws);
+    int nseg = 0;
+    for (int t0 = 0; t0 < ntensors; t0 += DWN_GS_SEG, ++nseg) {            // DWN_GS_SEG tensors per launch: the prefix lives in LDS
+        const int nt = ntensors - t0 < DWN_GS_SEG ? ntensors - t0 : DWN_GS_SEG;
+        hipLaunchKernelGGL(grad_sumsq_kernel, dim3(max_blocks), dim3(256), 0, s, list + t0, nt, partial + (size_t)nseg * max_blocks);
+        DWN_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(grad_sumsq_fold_kernel, dim3(1), dim3(256), 0, s, partial, nseg * max_blocks, grad_scale * grad_scale, pair);
+    DWN_CHECK_LAUNCH();
+    return 0;
+}
+
+// the guard finaliser: every lane forms the same decision from the one or two pairs; lane 0 writes the guard, and when the step
+// is taken every entry's device step counter advances (the counters of one call must be distinct words)
+__global__ __launch_bounds__(256) void step_guard_finalize_kernel(const double* pair_a, const double* pair_b, double max_norm,
+                                                                  int skip_nonfinite, const dwn_guarded_entry* list, int ntensors,
+                                                                  dwn_step_guard* guard) {
+    double sumsq = pair_a[0], bad = pair_a[1];
+    if (pair_b) { sumsq += pair_b[0]; bad += pair_b[1]; }
+    const double norm = sqrt(sumsq);
+    double coef = 1.0;
+    if (max_norm > 0.0) { coef = max_norm / (norm + 1e-6); coef = coef < 1.0 ? coef : 1.0; }      // clip_grad_norm_'s formula
+    const int skip = skip_nonfinite && bad > 0.0;
+    if (threadIdx.x == 0) {
+        guard->norm = norm;
+        guard->coef = (float)coef;
+        guard->skip = skip;
+        guard->nonfinite = (long long)bad;
+        if (skip) guard->skipped_steps += 1; else guard->good_steps += 1;
+    }
+    if (!skip)
+        for (int i = threadIdx.x; i < ntensors; i += 256)
+            if (list[i].step) *list[i].step += 1;
+}
+int k_step_guard_finalize(const double* pair_a, const double* pair_b, double max_norm, int skip_nonfinite,
+                          const dwn_guarded_entry* list, int ntensors, dwn_step_guard* guard, hipStream_t s) {
+    hipLaunchKernelGGL(step_guard_finalize_kernel, dim3(1), dim3(256), 0, s, pair_a, pair_b, max_norm, skip_nonfinite, list,
+                       ntensors, guard);
+    DWN_CHECK_LAUNCH();
+    return 0;
+}
+
+// adamw_ema_kernel with the gradient factor, the skip decision and the step count read from the device.  The bias corrections are
+// formed per tensor from its own counter (already advanced by the finaliser), in double, and cast where dwn_adamw_ema_multi casts.
+__global__ __launch_bounds__(256) void adamw_ema_guarded_kernel(const dwn_guarded_entry* list, int ntensors, float decay_w,
+                                                                float omb1, float beta2, float omb2, float eps, double lr,
+                                                                double beta1_d, double beta2_d, float ema_decay, float ema_omd,
+                                                                float grad_scale, const dwn_step_guard* guard) {
+    const dwn_guarded_entry e = list[blockIdx.y];
+    if ((i64)blockIdx.x * 256 >= e.numel) return;          // before the pow below: most workgroups of a small tensor have no work
+    float* p = e.param; const float* g = e.grad; float* m = e.exp_avg; float* v = e.exp_avg_sq; float* ema = e.ema;
+    if (guard->skip) {                                     // the reference's scaler skips optimizer.step; model_ema.update runs anyway
+        if (ema)
+            for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < e.numel; i += (i64)gridDim.x * 256)
+                ema[i] = ema_decay * ema[i] + ema_omd * p[i];
+        return;
+    }
+    const double t = (double)*e.step;
+    const float step_size = (float)(lr / (1.0 - pow(beta1_d, t)));
+    const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2_d, t));
+    const float gs = grad_scale * guard->coef;
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < e.numel; i += (i64)gridDim.x * 256) {
+        float gi = g[i] * gs;
+        float pi = p[i] * decay_w;
+        float mi = m[i] + omb1 * (gi - m[i]);
+        float vi = beta2 * v[i] + omb2 * gi * gi;
+        float denom = sqrtf(vi) / bc2_sqrt + eps;
+        pi = pi - step_size * (mi / denom);
+        p[i] = pi; m[i] = mi; v[i] = vi;
+        if (ema) ema[i] = ema_decay * ema[i] + ema_omd * pi;
+    }
+}
+int k_adamw_ema_guarded(const dwn_guarded_entry* list, int ntensors, int max_blocks, double lr, double beta1, double beta2,
+                        double eps, double weight_decay, double ema_decay, double grad_scale, const dwn_step_guard* guard,
+                        hipStream_t s) {
+    if (ntensors <= 0) return 0;
+    hipLaunchKernelGGL(adamw_ema_guarded_kernel, dim3(max_blocks, ntensors), dim3(256), 0, s, list, ntensors,
+                       (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, lr,
+                       beta1, beta2, (float)ema_decay, (float)(1.0 - ema_decay), (float)grad_scale, guard);
+    DWN_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // small utilities
 // ------------------------------------------------------------------------------------------------
 // zero-fill as a kernel (not hipMemsetAsync): always replayed by a captured hipGraph, 16 bytes per lane

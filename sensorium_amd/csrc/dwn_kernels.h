@@ -94,6 +94,14 @@ int k_adamw_ema(const TensorListEntry* list, int ntensors, int max_blocks, float
                 float omb2, float eps, float step_size, float bc2_sqrt, float ema_decay, float ema_omd,
                 float grad_scale, hipStream_t s);
 int k_ema_lerp(const TensorListEntry* list, int ntensors, int max_blocks, float decay, float omd, hipStream_t s);
+// guarded step (dwn.h dwn_grad_sumsq_multi / dwn_step_guard_finalize / dwn_adamw_ema_multi_guarded)
+int k_grad_sumsq(const dwn_guarded_entry* list, int ntensors, int max_blocks, double grad_scale, void* ws, double* pair,
+                 hipStream_t s);
+int k_step_guard_finalize(const double* pair_a, const double* pair_b, double max_norm, int skip_nonfinite,
+                          const dwn_guarded_entry* list, int ntensors, dwn_step_guard* guard, hipStream_t s);
+int k_adamw_ema_guarded(const dwn_guarded_entry* list, int ntensors, int max_blocks, double lr, double beta1, double beta2,
+                        double eps, double weight_decay, double ema_decay, double grad_scale, const dwn_step_guard* guard,
+                        hipStream_t s);
 int k_fill_f32(float* p, float v, int n, hipStream_t s);
 int k_pack_weight_dual(const float* src, void* plain, void* tr, int groups, int R, int C, int Rp, int ldp, int ldt, int dtype,
                        hipStream_t s);

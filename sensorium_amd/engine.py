@@ -170,6 +170,11 @@ class _DefaultLogging(Callback):
         for k, v in state.metrics.items():
             if k.startswith(prefix):
                 parts.append(f"{k}: {_fmt(v)}")
+        if state.phase == "train" and state.model is not None:
+            # guarded optimizer (optim.FusedAdamWEma(max_grad_norm / skip_nonfinite)): one device read per epoch, never per iteration
+            stats = getattr(getattr(state.model, "optimizer", None), "guard_stats", lambda: None)()
+            if stats is not None:
+                parts.append(f"skipped_steps: {stats['skipped_steps']}")
         state.logger.info(", ".join(parts))
 
 

@@ -25,7 +25,7 @@ def main():
     rows.sort()
     is_comm = lambda n: bool(re.search(r"nccl|rccl|oneRank", n, re.I))
     # steps end with the fused optimizer
-    opt = [i for i, r in enumerate(rows) if "adamw_ema_kernel" in r[2]]
+    opt = [i for i, r in enumerate(rows) if "adamw_ema_" in r[2]]
     if len(opt) < 3:
         raise SystemExit("need at least three steps in the trace")
     a, b = opt[-3] + 1, opt[-2] + 1                     # the second-to-last complete step (the last may be cut by profiler shutdown)

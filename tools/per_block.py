@@ -31,7 +31,7 @@ def short(n):
 
 def last_step(rows, which=-2):
     rows = sorted(rows, key=lambda r: int(r["Start_Timestamp"]))
-    idx = [i for i, r in enumerate(rows) if "adamw_ema_kernel" in r["Kernel_Name"]]
+    idx = [i for i, r in enumerate(rows) if "adamw_ema_" in r["Kernel_Name"]]
     return rows[idx[which - 1] + 1: idx[which] + 1]
 
 
