@@ -289,7 +289,7 @@ ResGeom geom_of(const dwn_block_args& a) {
 
 int check_block(const dwn_block_args& a) {
     if (a.Cin % 8 || a.Cmid % 8 || a.Cout % 8) return dwn_set_error(-2, "block: channel counts must be multiples of 8");
-    if (a.ks != 3) return dwn_set_error(-4, "block: spatial_kernel must be 3");
+    if (a.ks != 3 && a.ks != 5 && a.ks != 7) return dwn_set_error(-4, "block: spatial_kernel must be 3, 5 or 7 (the built set)");
     if (a.kt != 3 && a.kt != 5) return dwn_set_error(-4, "block: temporal_kernel must be 3 or 5");
     if (a.Hout != (a.Hin - 1) / a.stride + 1 || a.Wout != (a.Win - 1) / a.stride + 1)
         return dwn_set_error(-2, "block: Hout/Wout inconsistent with stride");

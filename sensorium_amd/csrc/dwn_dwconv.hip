@@ -1044,11 +1044,520 @@ static int launch_dw(K kernel, int threads, size_t dyn_lds, int slices, i64 work
     return launch_resident(kernel, threads, dyn_lds, 2, slices, work, false, s, a);
 }
 
+// ------------------------------------------------------------------------------------------------
+// spatial kernel sizes 5 and 7 (P = KS/2 = 2, 3), both storage types, stride 1, 2 and generic.
+//
+// 25 / 49 taps of 4 channels do not fit a thread's registers next to anything else (100 / 196 floats of weights forward, as
+// many weight-gradient accumulators backward), so neither is held per thread:
+//   * stencil weights live in LDS as [tap][channel] floats and are read as one broadcast ds_read_b128 per tap, shared by the
+//     XB pixels a thread has in flight (forward: XB outputs, backward: XB input pixels);
+//   * the weight gradient is split by TAP ROW over the waves of the workgroup: wave v owns tap row v % KS for the whole
+//     persistent kernel and keeps its KS accumulators (4 channels each) in registers; it needs z1 of pixels other threads
+//     activated, so the data-gradient pass leaves z1 of the band in a second LDS tile (zero halo of P columns).
+// Backward, per band of input rows:  stage g = dL/dy2 (true halo: ceil(P/s) columns each side, rows floor((hi0-P)/s) ..
+// (hi0+nri-1+P)/s)  ->  pass A: dh1 = (W^T g) * SiLU'(h1), BatchNorm-backward sums, z1 -> LDS  ->  pass B: dW[dy][dx] +=
+// sum over outputs (ho, wo) of g(ho, wo) * z1(s*ho - P + dy, s*wo - P + dx), the forward's own indexing: no parity cases, and
+// every product is a real tap at any stride.
+// ------------------------------------------------------------------------------------------------
+#define DWS_KS_BWD_THREADS 512
+// dynamic LDS the band choice may fill: two 512-thread workgroups per CU next to the static weight table
+#define DWS_KS_LDS_BUDGET(static_bytes) (80 * 1024 - (int)(static_bytes) - 1024)
+
+template <typename T, int KS, int ST, int NT>
+__global__ __launch_bounds__(NT, 4) void dw_spatial_fwd_ks_kernel(const DwSpatialFwd a) {
+    constexpr int NCV = SL<T>::NCV, CS = SL<T>::CS, LP = NT / NCV, P = KS / 2;
+    constexpr int XB = 4;                              // outputs per thread sharing one weight read per tap
+    typedef typename SL<T>::raw_t raw_t;
+    const int stride = ST > 0 ? ST : a.stride;
+    __shared__ float lstat[2 * CS];
+    __shared__ __attribute__((aligned(16))) float lw[KS * KS * CS];      // stencil weights [tap][channel] (broadcast reads)
+    const int tid = threadIdx.x;
+    const int cv = tid % NCV, pl = tid / NCV;
+    const int c0 = blockIdx.y * CS;
+    const int chan = c0 + cv * 4;
+    const bool chan_ok = chan < a.C;
+    const int chs = chan_ok ? chan : 0;               // safe channel for predicated loads
+    if (tid < 2 * CS) lstat[tid] = 0.f;
+    for (int i = tid; i < KS * KS * CS; i += NT) {
+        const int k = i / CS, c = c0 + i % CS;
+        lw[i] = c < a.C ? a.w[(i64)k * a.C + c] : 0.f;
+    }
+    __syncthreads();
+
+    float bs[4], bt[4];
+    ldc4(a.in.v1 + chs, bs);
+    ldc4(a.in.v2 + chs, bt);
+    f2_t st0[2] = {f2_t{0.f, 0.f}, f2_t{0.f, 0.f}}, st1[2] = {f2_t{0.f, 0.f}, f2_t{0.f, 0.f}};
+
+    const int Wp = a.Win + 2 * P;
+    const FastDiv dvp(Wp), dvo(a.Wout);
+    const int nbands = (a.Hout + a.rows_band - 1) / a.rows_band;
+    const int ntiles = a.planes * nbands;
+    const T* inp = reinterpret_cast<const T*>(a.in.p);
+    T* outp = reinterpret_cast<T*>(a.out);
+    raw_t* tile = reinterpret_cast<raw_t*>(dyn_smem);
+    for (int tile_id = blockIdx.x; tile_id < ntiles; tile_id += gridDim.x) {
+        const int plane = tile_id / nbands, band = tile_id % nbands;
+        const int ho0 = band * a.rows_band;
+        const int nro = (a.Hout - ho0 < a.rows_band) ? a.Hout - ho0 : a.rows_band;
+        const int hi0 = ho0 * stride - P;
+        const int rows_in = (nro - 1) * stride + KS;
+        const i64 plane_row0 = (i64)plane * a.Hin * a.Win;
+        // stage the activated input rows with their zero halo: flat (row, column) walk, flat index == tile index, NB loads in flight
+        {
+            constexpr int NB = 8;
+            const int total_st = rows_in * Wp;
+            const T* in0 = inp + plane_row0 * a.in.ld;
+            for (int f0 = pl; f0 < total_st; f0 += NB * LP) {
+                raw_t raw[NB];
+                bool okv[NB];
+#pragma unroll
+                for (int u = 0; u < NB; ++u) {
+                    const int f = f0 + u * LP;
+                    const int r = dvp.div(f);
+                    const int hi = hi0 + r, wi = dvp.rem(f, r) - P;
+                    okv[u] = chan_ok && f < total_st && (unsigned)hi < (unsigned)a.Hin && (unsigned)wi < (unsigned)a.Win;
+                    const unsigned off = okv[u] ? __umul24(__mul24(hi, a.Win) + wi, (unsigned)a.in.ld) : 0u;
+                    raw[u] = ld4_raw<T>(in0 + off + chs);
+                }
+#pragma unroll
+                for (int u = 0; u < NB; ++u) {
+                    const int f = f0 + u * LP;
+                    if (f < total_st) {
+                        float v[4];
+                        V4<T>::unpack(raw[u], v);
+                        bn_silu4(v, bs, bt);
+                        tile[f * NCV + cv] = okv[u] ? V4<T>::pack(v) : V4<T>::zero();
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        {
+            const int total = nro * a.Wout;
+            const i64 orow0 = ((i64)plane * a.Hout + ho0) * a.Wout;
+            T* out0 = outp + orow0 * a.C + chan;
+            const int wdiff = stride * Wp - stride * a.Wout;   // tile index of output i = i*stride + oy*wdiff (+ taps)
+            const int rowstep = Wp * NCV;
+            for (int i0 = pl; i0 < total; i0 += XB * LP) {
+                int ti[XB];
+                f2_t acc[XB][2];
+#pragma unroll
+                for (int u = 0; u < XB; ++u) {
+                    const int i = i0 + u * LP;
+                    const int iv = i < total ? i : 0;           // lanes past the band read output 0's taps and store nothing
+                    const int oy = dvo.div(iv);
+                    ti[u] = (iv * stride + __mul24(oy, wdiff)) * NCV + cv;
+                    acc[u][0] = f2_t{0.f, 0.f}; acc[u][1] = f2_t{0.f, 0.f};
+                }
+                // a LOOP over tap rows (not unrolled): unrolled, the compiler hoists all KS*KS weight reads out of the pixel loop
+                // and spills them; one row's KS weight vectors (4 channels each) is what a thread holds at a time
+#pragma unroll 1
+                for (int dy = 0; dy < KS; ++dy) {
+                    const float* wr = &lw[dy * KS * CS + cv * 4];
+                    const raw_t* tr = tile + dy * rowstep;
+#pragma unroll
+                    for (int dx = 0; dx < KS; ++dx) {
+                        const float4 wv = *reinterpret_cast<const float4*>(wr + dx * CS);
+#pragma unroll
+                        for (int u = 0; u < XB; ++u) {
+                            f2_t v0, v1;
+                            unpack_pairs<T>(tr[ti[u] + dx * NCV], v0, v1);
+                            acc[u][0] += f2_t{wv.x, wv.y} * v0;
+                            acc[u][1] += f2_t{wv.z, wv.w} * v1;
+                        }
+                        __builtin_amdgcn_sched_barrier(0);       // one tap's reads in flight: a whole row's would not fit the registers
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < XB; ++u) {
+                    const int i = i0 + u * LP;
+                    if (chan_ok && i < total) {
+                        const float o[4] = {acc[u][0].x, acc[u][0].y, acc[u][1].x, acc[u][1].y};
+                        const raw_t packed = V4<T>::pack(o);
+                        *reinterpret_cast<raw_t*>(out0 + __umul24((unsigned)i, (unsigned)a.C)) = packed;
+                        f2_t r0, r1;
+                        unpack_pairs<T>(packed, r0, r1);              // statistics of the values as stored
+                        st0[0] += r0; st0[1] += r1; st1[0] += r0 * r0; st1[1] += r1 * r1;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (a.stats) {
+        const float s0[4] = {st0[0].x, st0[0].y, st0[1].x, st0[1].y}, s1[4] = {st1[0].x, st1[0].y, st1[1].x, st1[1].y};
+        block_stats_flush<T>(lstat, s0, s1, cv, c0, a.C, a.stats, blockIdx.x % DWN_NREP);
+    }
+    DET_EXIT();
+}
+
+template <typename T, int KS, int ST>
+__global__ __launch_bounds__(DWS_KS_BWD_THREADS, DWS_KS_BWD_THREADS / 128) void dw_spatial_bwd_ks_kernel(const DwSpatialBwd a) {
+    constexpr int NT = DWS_KS_BWD_THREADS, NW = NT / 64;
+    constexpr int NCV = SL<T>::NCV, CS = SL<T>::CS, LP = NT / NCV, PLW = 64 / NCV, P = KS / 2;
+    constexpr int XB = 1;                              // input pixels per thread and batch (2 would share a weight read but spill)
+    static_assert(NW >= KS, "every tap row needs a wave");
+    typedef typename SL<T>::raw_t raw_t;
+    __shared__ float lstat[2 * CS];
+    __shared__ __attribute__((aligned(16))) float lw[KS * KS * CS];      // stencil weights (broadcast reads), later dW
+    // BatchNorm-1 scale, shift, invstd, -mean*invstd per channel: read where a pixel is activated / finished instead of held
+    // (16 registers that the tap-row accumulators need)
+    __shared__ __attribute__((aligned(16))) float lbn[4 * CS];
+    const int tid = threadIdx.x;
+    const int cv = tid % NCV, pl = tid / NCV;
+    const int c0 = blockIdx.y * CS;
+    const int chan = c0 + cv * 4;
+    const bool chan_ok = chan < a.C;
+    const int chs = chan_ok ? chan : 0;
+    const int s = ST > 0 ? ST : a.stride;
+    const int HL = (P + s - 1) / s;                  // halo columns of the gradient tile, each side
+    const int Wq = a.Wout + 2 * HL;                  // staged gradient columns wo = -HL .. Wout - 1 + HL
+    const int Wz = a.Win + 2 * P;                    // z1 tile columns wi = -P .. Win - 1 + P (halo stays zero)
+    const int rows_q_max = s == 1 ? a.rows_band + 2 * P : (a.rows_band - 1 + 2 * P) / s + 2;      // as the launcher sizes the tile
+    raw_t* tile = reinterpret_cast<raw_t*>(dyn_smem);
+    raw_t* zt = tile + rows_q_max * Wq * NCV;
+    if (tid < 2 * CS) lstat[tid] = 0.f;
+    if (tid < CS) {                                  // yhat = y*invstd + nbm
+        const int c = c0 + tid < a.C ? c0 + tid : 0;
+        lbn[tid] = a.y1.v1[c]; lbn[CS + tid] = a.y1.v2[c]; lbn[2 * CS + tid] = a.y1.v4[c]; lbn[3 * CS + tid] = -a.y1.v3[c] * a.y1.v4[c];
+    }
+    // (the set-up loops stay rolled: unrolled, their loads push the values the main loop keeps into scratch)
+#pragma unroll 1
+    for (int i = tid; i < KS * KS * CS; i += NT) {
+        const int k = i / CS, c = c0 + i % CS;
+        lw[i] = c < a.C ? a.w[(i64)k * a.C + c] : 0.f;
+    }
+#pragma unroll 1
+    for (int i = tid; i < a.rows_band * Wz * NCV; i += NT) zt[i] = V4<T>::zero();
+    __syncthreads();
+
+    // pass B role: this wave's tap row, its lane among the lanes of that row, and their number
+    const int wave = tid >> 6;
+    const int mydy = wave % KS;
+    const int gl = (wave / KS) * PLW + (pl % PLW);
+    const int gn = ((NW - mydy + KS - 1) / KS) * PLW;
+    f2_t dwr[KS][2];
+#pragma unroll
+    for (int k = 0; k < KS; ++k) { dwr[k][0] = f2_t{0.f, 0.f}; dwr[k][1] = f2_t{0.f, 0.f}; }
+    f2_t sp0[2] = {f2_t{0.f, 0.f}, f2_t{0.f, 0.f}}, sp1[2] = {f2_t{0.f, 0.f}, f2_t{0.f, 0.f}};
+
+    const FastDiv dvq(Wq), dvo(a.Wout);
+    const int nbands = (a.Hin + a.rows_band - 1) / a.rows_band;
+    const int ntiles = a.planes * nbands;
+    T* dhp = reinterpret_cast<T*>(a.dh1);
+    const T* y1p = reinterpret_cast<const T*>(a.y1.p);
+    const T* dpp = reinterpret_cast<const T*>(a.dy.p);
+    const T* dqp = reinterpret_cast<const T*>(a.dy.q);
+    for (int tile_id = blockIdx.x; tile_id < ntiles; tile_id += gridDim.x) {
+        const int plane = tile_id / nbands, band = tile_id % nbands;
+        const int hi0 = band * a.rows_band;
+        const int nri = (a.Hin - hi0 < a.rows_band) ? a.Hin - hi0 : a.rows_band;
+        // output rows that touch input rows [hi0, hi0+nri): ho = (hi + P - dy) / s
+        const int lo_num = hi0 - P;
+        const int ho_lo = lo_num >= 0 ? lo_num / s : -((-lo_num + s - 1) / s);
+        const int ho_hi = (hi0 + nri - 1 + P) / s;
+        const int rows_q = ho_hi - ho_lo + 1;
+        const i64 orow0 = (i64)plane * a.Hout * a.Wout;
+        // stage dL/dy2 = A1*dh2 + A2*y2 + A3 (BatchNorm backward) with zero padding; flat walk, 2*NB loads in flight per thread
+        {
+            constexpr int NB = 2;
+            const int total_st = rows_q * Wq;
+            float a1[4], a2[4], a3[4];
+            ldc4(a.dy.v1 + chs, a1); ldc4(a.dy.v2 + chs, a2); ldc4(a.dy.v3 + chs, a3);
+            const f2_t a1v[2] = {f2_t{a1[0], a1[1]}, f2_t{a1[2], a1[3]}}, a2v[2] = {f2_t{a2[0], a2[1]}, f2_t{a2[2], a2[3]}};
+            const f2_t a3v[2] = {f2_t{a3[0], a3[1]}, f2_t{a3[2], a3[3]}};
+            const T* dp0 = dpp + orow0 * a.dy.ld + chs;
+            const T* dq0 = dqp + orow0 * a.dy.ld + chs;
+            for (int f0 = pl; f0 < total_st; f0 += NB * LP) {
+                raw_t rp[NB], rq[NB];
+                bool okv[NB];
+#pragma unroll
+                for (int u = 0; u < NB; ++u) {
+                    const int f = f0 + u * LP;
+                    const int r = dvq.div(f);
+                    const int ho = ho_lo + r, wo = dvq.rem(f, r) - HL;
+                    okv[u] = chan_ok && f < total_st && (unsigned)ho < (unsigned)a.Hout && (unsigned)wo < (unsigned)a.Wout;
+                    const unsigned off = okv[u] ? __umul24(__mul24(ho, a.Wout) + wo, (unsigned)a.dy.ld) : 0u;
+                    rp[u] = ld4_raw<T>(dp0 + off);
+                    rq[u] = ld4_raw<T>(dq0 + off);
+                }
+#pragma unroll
+                for (int u = 0; u < NB; ++u) {
+                    const int f = f0 + u * LP;
+                    if (f < total_st) {
+                        f2_t p0, p1, q0, q1;
+                        unpack_pairs<T>(rp[u], p0, p1);
+                        unpack_pairs<T>(rq[u], q0, q1);
+                        p0 = a1v[0] * p0 + (a2v[0] * q0 + a3v[0]);
+                        p1 = a1v[1] * p1 + (a2v[1] * q1 + a3v[1]);
+                        const float p[4] = {p0.x, p0.y, p1.x, p1.y};
+                        tile[f * NCV + cv] = okv[u] ? V4<T>::pack(p) : V4<T>::zero();
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        // ---- pass A: data gradient, SiLU', BatchNorm-backward sums; z1 of the band -> zt
+        {
+            const i64 prow0 = (i64)plane * a.Hin * a.Win;
+            T* dh0 = dhp + prow0 * a.C + chan;
+            const T* y10 = y1p + prow0 * a.y1.ld + chs;
+            // activation of one pixel: z1 goes to the LDS tile, y / SiLU' stay for the epilogue
+            auto activate = [&](const raw_t& raw, const int zi, f2_t* y, f2_t* dsl) {
+                unpack_pairs<T>(raw, y[0], y[1]);
+                const float4 s4 = *reinterpret_cast<const float4*>(&lbn[cv * 4]), t4 = *reinterpret_cast<const float4*>(&lbn[CS + cv * 4]);
+                const f2_t bs2[2] = {f2_t{s4.x, s4.y}, f2_t{s4.z, s4.w}}, bt2[2] = {f2_t{t4.x, t4.y}, f2_t{t4.z, t4.w}};
+                f2_t z1[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const f2_t h = y[i] * bs2[i] + bt2[i];
+                    const f2_t sg = sigmoid2f_(h);
+                    z1[i] = h * sg;
+                    dsl[i] = sg * (1.0f + h * (1.0f - sg));
+                }
+                const float z[4] = {z1[0].x, z1[0].y, z1[1].x, z1[1].y};
+                zt[zi * NCV + cv] = V4<T>::pack(z);
+            };
+            auto finish_at = [&](const int pix, const f2_t* y, const f2_t* dsl, const f2_t* dz) {
+                const f2_t d0 = dz[0] * dsl[0], d1 = dz[1] * dsl[1];
+                const float dh[4] = {d0.x, d0.y, d1.x, d1.y};
+                const raw_t packed = V4<T>::pack(dh);
+                *reinterpret_cast<raw_t*>(dh0 + __umul24((unsigned)pix, (unsigned)a.C)) = packed;
+                f2_t r0, r1;
+                unpack_pairs<T>(packed, r0, r1);              // statistics of the values as stored
+                const float4 i4 = *reinterpret_cast<const float4*>(&lbn[2 * CS + cv * 4]), n4 = *reinterpret_cast<const float4*>(&lbn[3 * CS + cv * 4]);
+                const f2_t bi2[2] = {f2_t{i4.x, i4.y}, f2_t{i4.z, i4.w}}, nbm2[2] = {f2_t{n4.x, n4.y}, f2_t{n4.z, n4.w}};
+                sp0[0] += r0; sp0[1] += r1;
+                sp1[0] += r0 * (y[0] * bi2[0] + nbm2[0]);
+                sp1[1] += r1 * (y[1] * bi2[1] + nbm2[1]);
+            };
+            if constexpr (ST == 1 || ST == 2) {
+                // Input pixels of one parity class (hi % ST, wi % ST) = (HP, PX) receive the taps dy = dy0 + ST*m, dx = dx0 + ST*n
+                // (dy0 = (HP + P) % ST: hi + P - dy divisible by ST), all of them inside the zero-padded tile: branch-free, the
+                // tap set known at compile time from KS, ST and the class.  Pixel (k, j) of the class is hi = hfirst + ST*k,
+                // wi = PX + ST*j; tap (m, n) reads tile entry (r0 + k - m, q0 + j - n): one index per pixel, uniform offsets per tap.
+                auto run_class = [&](auto hp_c, auto px_c) {
+                    constexpr int HP = decltype(hp_c)::value, PX = decltype(px_c)::value;
+                    constexpr int DY0 = (HP + P) % ST, DX0 = (PX + P) % ST;
+                    const int hfirst = hi0 + ((hi0 % ST) == HP ? 0 : 1);
+                    const int nr = (hi0 + nri - hfirst + ST - 1) / ST;
+                    const int nc = (a.Win - PX + ST - 1) / ST;
+                    const int total = (nr > 0 && nc > 0) ? nr * nc : 0;
+                    const FastDiv dvc(nc > 0 ? nc : 1);
+                    const int r0 = (hfirst + P - DY0) / ST - ho_lo;
+                    const int q0 = (PX + P - DX0) / ST + HL;
+                    const int base = (r0 * Wq + q0) * NCV + cv;
+                    const int wdiff = Wq - nc;
+                    const int rowstep = Wq * NCV;
+                    for (int i0 = pl; i0 < total; i0 += XB * LP) {
+                        raw_t ry[XB];
+                        int gg[XB];
+                        int ti[XB];
+#pragma unroll
+                        for (int u = 0; u < XB; ++u) {
+                            const int i = i0 + u * LP;
+                            const int iv = (chan_ok && i < total) ? i : 0;
+                            const int k = dvc.div(iv);
+                            const int j = dvc.rem(iv, k);
+                            ti[u] = (iv + __mul24(k, wdiff)) * NCV + base;
+                            gg[u] = __mul24(hfirst + ST * k, a.Win) + (PX + ST * j);
+                            ry[u] = ld4_raw<T>(y10 + __umul24((unsigned)gg[u], (unsigned)a.y1.ld));
+                        }
+                        // the taps run first, on the tile alone: the y1 loads land behind them, and y / SiLU' (8 registers per
+                        // pixel) are not live next to a tap row's weights
+                        f2_t dz[XB][2];
+#pragma unroll
+                        for (int u = 0; u < XB; ++u) { dz[u][0] = f2_t{0.f, 0.f}; dz[u][1] = f2_t{0.f, 0.f}; }
+                        // a loop over the class's tap rows (not unrolled, as in the forward): one row of weights held at a time
+#pragma unroll 1
+                        for (int m = 0; m < (KS - DY0 + ST - 1) / ST; ++m) {
+                            const float* wr = &lw[(DY0 + ST * m) * KS * CS + cv * 4];
+                            const raw_t* tr = tile - m * rowstep;
+#pragma unroll
+                            for (int dx = DX0; dx < KS; dx += ST) {
+                                const float4 wv = *reinterpret_cast<const float4*>(wr + dx * CS);
+#pragma unroll
+                                for (int u = 0; u < XB; ++u) {
+                                    f2_t g0, g1;
+                                    unpack_pairs<T>(tr[ti[u] - ((dx - DX0) / ST) * NCV], g0, g1);
+                                    dz[u][0] += f2_t{wv.x, wv.y} * g0;
+                                    dz[u][1] += f2_t{wv.z, wv.w} * g1;
+                                }
+                                __builtin_amdgcn_sched_barrier(0);   // as in the forward
+                            }
+                        }
+#pragma unroll
+                        for (int u = 0; u < XB; ++u) {
+                            const int i = i0 + u * LP;
+                            if (chan_ok && i < total) {
+                                const int k = dvc.div(i);
+                                const int j = dvc.rem(i, k);
+                                f2_t y[2], dsl[2];
+                                activate(ry[u], (hfirst - hi0 + ST * k) * Wz + (PX + ST * j) + P, y, dsl);
+                                finish_at(gg[u], y, dsl, dz[u]);
+                            }
+                        }
+                    }
+                };
+                run_class(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+                if constexpr (ST == 2) {
+                    run_class(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
+                    run_class(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
+                    run_class(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
+                }
+            } else {
+                // generic stride: taps tested per pixel
+                const int total = nri * a.Win;
+                for (int i = pl; i < total; i += LP) {
+                    if (!chan_ok) continue;
+                    const int iy = i / a.Win;
+                    const int hi = hi0 + iy, wi = i - iy * a.Win;
+                    f2_t y[2], dsl[2], dz[2] = {f2_t{0.f, 0.f}, f2_t{0.f, 0.f}};
+                    activate(ld4_raw<T>(y10 + (i64)(hi * a.Win + wi) * a.y1.ld), iy * Wz + wi + P, y, dsl);
+#pragma unroll 1
+                    for (int dy = 0; dy < KS; ++dy) {
+                        const int nh = hi + P - dy;
+                        if (nh < 0 || nh % s != 0) continue;
+                        const int ho = nh / s;
+#pragma unroll 1
+                        for (int dx = 0; dx < KS; ++dx) {
+                            const int nw = wi + P - dx;
+                            if (nw < 0 || nw % s != 0) continue;
+                            const int wo = nw / s;
+                            f2_t g0, g1;
+                            unpack_pairs<T>(tile[((ho - ho_lo) * Wq + wo + HL) * NCV + cv], g0, g1);
+                            const float4 wv = *reinterpret_cast<const float4*>(&lw[(dy * KS + dx) * CS + cv * 4]);
+                            dz[0] += f2_t{wv.x, wv.y} * g0;
+                            dz[1] += f2_t{wv.z, wv.w} * g1;
+                        }
+                    }
+                    finish_at(hi * a.Win + wi, y, dsl, dz);
+                }
+            }
+        }
+        __syncthreads();
+        // ---- pass B: this wave's tap row of dW over the outputs whose input row s*ho - P + mydy lies in the band
+        {
+            const int num = hi0 + P - mydy;                                   // s*ho >= num
+            const int numl = hi0 + nri - 1 + P - mydy;                        // s*ho <= numl
+            const int ho_f = num > 0 ? (num + s - 1) / s : 0;
+            int ho_l = numl >= 0 ? numl / s : -1;
+            if (ho_l > a.Hout - 1) ho_l = a.Hout - 1;
+            const int total = ho_l >= ho_f ? (ho_l - ho_f + 1) * a.Wout : 0;
+            const int zr0 = s * ho_f - num;                                   // band row of output row ho_f under this tap row
+            const raw_t* gp0 = tile + ((ho_f - ho_lo) * Wq + HL) * NCV + cv;
+            const raw_t* zp0 = zt + zr0 * Wz * NCV + cv;
+            const int gdiff = Wq - a.Wout, zdiff = s * Wz - s * a.Wout;
+            for (int i = gl; i < total; i += gn) {
+                const int rr = dvo.div(i);
+                f2_t g0, g1;
+                unpack_pairs<T>(gp0[(i + __mul24(rr, gdiff)) * NCV], g0, g1);
+                const raw_t* zp = zp0 + (i * s + __mul24(rr, zdiff)) * NCV;
+#pragma unroll
+                for (int dx = 0; dx < KS; ++dx) {
+                    f2_t z0, z1;
+                    unpack_pairs<T>(zp[dx * NCV], z0, z1);
+                    dwr[dx][0] += z0 * g0;
+                    dwr[dx][1] += z1 * g1;
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // weight gradient: reduce over the threads sharing a tap row and channel vector through LDS, then global fp32 atomics
+    __syncthreads();
+#pragma unroll 1
+    for (int i = tid; i < KS * KS * CS; i += NT) lw[i] = 0.f;
+    __syncthreads();
+    DET_WAVES_BEGIN
+    if (chan_ok) {
+#pragma unroll
+        for (int dx = 0; dx < KS; ++dx) {
+            float* d = &lw[(mydy * KS + dx) * CS + cv * 4];
+            atomicAdd(d + 0, dwr[dx][0].x);
+            atomicAdd(d + 1, dwr[dx][0].y);
+            atomicAdd(d + 2, dwr[dx][1].x);
+            atomicAdd(d + 3, dwr[dx][1].y);
+        }
+    }
+    DET_WAVES_END
+    __syncthreads();
+    DET_ENTER();
+#pragma unroll 1
+    for (int i = tid; i < KS * KS * CS; i += NT) {
+        const int k = i / CS, c = c0 + i % CS;
+        if (c < a.C) atomicAdd(a.dw + (i64)c * (KS * KS) + k, lw[i]);
+    }
+    const float st0[4] = {sp0[0].x, sp0[0].y, sp0[1].x, sp0[1].y}, st1[4] = {sp1[0].x, sp1[0].y, sp1[1].x, sp1[1].y};
+    if (a.stats) block_stats_flush<T>(lstat, st0, st1, cv, c0, a.C, a.stats, blockIdx.x % DWN_NREP);
+    DET_EXIT();
+}
+
+// launchers of the two kernels above: tile bytes and band from P; the LDS limit and its error as for 3x3
+template <typename T, int KS>
+static int spatial_fwd_ks_t(DwSpatialFwd a, hipStream_t s) {
+    constexpr int CS = SL<T>::CS, P = KS / 2;
+    constexpr size_t STATIC = (size_t)(KS * KS + 2) * CS * sizeof(float);
+    const int Wp = a.Win + 2 * P;
+    auto tile_bytes = [&](int rb) { return (size_t)((rb - 1) * a.stride + KS) * Wp * 128; };
+    if (a.rows_band <= 0) {
+        size_t budget = (size_t)DWS_FWD_LDS_BUDGET;
+        if (budget > (size_t)DWS_KS_LDS_BUDGET(STATIC)) budget = (size_t)DWS_KS_LDS_BUDGET(STATIC);
+        int rb = 1;
+        while (rb < a.Hout && tile_bytes(rb + 1) <= budget) ++rb;
+        const int nb = (a.Hout + rb - 1) / rb;          // even split: no ragged last band
+        a.rows_band = (a.Hout + nb - 1) / nb;
+    }
+    if (a.rows_band > a.Hout) a.rows_band = a.Hout;
+    const size_t lds = tile_bytes(a.rows_band);
+    if (lds + STATIC > 156 * 1024) return dwn_set_error(-5, "dw_spatial: plane too wide for the LDS tile");
+    const int nbands = (a.Hout + a.rows_band - 1) / a.rows_band;
+    const int slices = (a.C + CS - 1) / CS;
+    const i64 work = (i64)a.planes * nbands;
+    const bool big = a.Hin * a.Win >= 512;
+    if (a.stride == 1) return big ? launch_dw(dw_spatial_fwd_ks_kernel<T, KS, 1, 512>, 512, lds, slices, work, s, a)
+                                  : launch_dw(dw_spatial_fwd_ks_kernel<T, KS, 1, 256>, 256, lds, slices, work, s, a);
+    if (a.stride == 2) return big ? launch_dw(dw_spatial_fwd_ks_kernel<T, KS, 2, 512>, 512, lds, slices, work, s, a)
+                                  : launch_dw(dw_spatial_fwd_ks_kernel<T, KS, 2, 256>, 256, lds, slices, work, s, a);
+    return launch_dw(dw_spatial_fwd_ks_kernel<T, KS, 0, 256>, 256, lds, slices, work, s, a);
+}
+
+template <typename T, int KS>
+static int spatial_bwd_ks_t(DwSpatialBwd a, hipStream_t s) {
+    constexpr int CS = SL<T>::CS, P = KS / 2;
+    constexpr size_t STATIC = (size_t)(KS * KS + 6) * CS * sizeof(float);
+    const int HL = (P + a.stride - 1) / a.stride;
+    const int Wq = a.Wout + 2 * HL, Wz = a.Win + 2 * P;
+    auto rows_q = [&](int rb) { return a.stride == 1 ? rb + 2 * P : (rb - 1 + 2 * P) / a.stride + 2; };   // staged output rows (bound)
+    auto tile_bytes = [&](int rb) { return ((size_t)rows_q(rb) * Wq + (size_t)rb * Wz) * 128; };          // gradient tile + z1 tile
+    if (a.rows_band <= 0) {
+        int rb = 1;
+        while (rb < a.Hin && tile_bytes(rb + 1) <= (size_t)DWS_KS_LDS_BUDGET(STATIC)) ++rb;
+        const int nb = (a.Hin + rb - 1) / rb;
+        a.rows_band = (a.Hin + nb - 1) / nb;
+    }
+    if (a.rows_band > a.Hin) a.rows_band = a.Hin;
+    const size_t lds = tile_bytes(a.rows_band);
+    if (lds + STATIC > 156 * 1024) return dwn_set_error(-5, "dw_spatial_bwd: plane too wide for the LDS tile");
+    const int nbands = (a.Hin + a.rows_band - 1) / a.rows_band;
+    const int slices = (a.C + CS - 1) / CS;
+    const i64 work = (i64)a.planes * nbands;
+    if (a.stride == 1) return launch_dw(dw_spatial_bwd_ks_kernel<T, KS, 1>, DWS_KS_BWD_THREADS, lds, slices, work, s, a);
+    if (a.stride == 2) return launch_dw(dw_spatial_bwd_ks_kernel<T, KS, 2>, DWS_KS_BWD_THREADS, lds, slices, work, s, a);
+    return launch_dw(dw_spatial_bwd_ks_kernel<T, KS, 0>, DWS_KS_BWD_THREADS, lds, slices, work, s, a);
+}
+
+#define DWS_KS_BUILT "dw_spatial: spatial_kernel must be 3, 5 or 7 (the built set)"
+
 template <typename T>
 static int spatial_fwd_t(DwSpatialFwd a, hipStream_t s) {
     constexpr int CS = SL<T>::CS;
-    if (a.ks != 3) return dwn_set_error(-4, "dw_spatial: only spatial_kernel=3 is built");
+    if (a.ks != 3 && a.ks != 5 && a.ks != 7) return dwn_set_error(-4, DWS_KS_BUILT);
     if (a.C % 8) return dwn_set_error(-2, "dw_spatial: C must be a multiple of 8");
+    if (a.ks == 5) return spatial_fwd_ks_t<T, 5>(a, s);
+    if (a.ks == 7) return spatial_fwd_ks_t<T, 7>(a, s);
     const int Wp = a.Win + 2;
     // bf16, stride 1/2: x-pair-packed tile (dot2 kernel), rows of ceil(Wp/2) pairs x 256 bytes
     const bool pair = TT<T>::IS_BF16 && (a.stride == 1 || a.stride == 2);
@@ -1317,8 +1826,10 @@ __global__ __launch_bounds__(DWS_BWD_THREADS, DWS_BWD_PAIR_MINW) void dw_spatial
 template <typename T>
 static int spatial_bwd_t(DwSpatialBwd a, hipStream_t s) {
     constexpr int CS = SL<T>::CS;
-    if (a.ks != 3) return dwn_set_error(-4, "dw_spatial: only spatial_kernel=3 is built");
+    if (a.ks != 3 && a.ks != 5 && a.ks != 7) return dwn_set_error(-4, DWS_KS_BUILT);
     if (a.C % 8) return dwn_set_error(-2, "dw_spatial: C must be a multiple of 8");
+    if (a.ks == 5) return spatial_bwd_ks_t<T, 5>(a, s);
+    if (a.ks == 7) return spatial_bwd_ks_t<T, 7>(a, s);
     const int Wq = a.Wout + 2;
     auto rows_q = [&](int rb) { return (rb - 1 + 2) / a.stride + 2; };   // upper bound on staged output rows
     // bf16, stride 1: x-pair-packed gradient tile (dot2 kernel), rows of ceil(Wq/2) pairs x 256 bytes

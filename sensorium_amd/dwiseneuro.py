@@ -11,8 +11,8 @@ Compute dtype: fp32 by default (parity mode); bf16 storage with fp32 accumulatio
 under ``torch.autocast`` (the reference trains under fp16 autocast, src/argus_models.py:50 — fp16 and bf16
 autocast both select the bf16 path here) or when ``compute_dtype=torch.bfloat16`` is set explicitly.
 
-Constraints of the HIP path (raised loudly, no fallback): channel counts multiples of 8, spatial_kernel 3,
-temporal_kernel 3 or 5, CUDA/HIP tensors only.  Backward: in training mode (batch statistics), and in eval mode with frozen
+Constraints of the HIP path (raised loudly, no fallback): channel counts multiples of 8, spatial_kernel 3, 5
+or 7 (5 and 7 through the stored-y1 path: no rebuilt-y1 / row-walk / tile-resident variants), temporal_kernel 3 or 5, CUDA/HIP tensors only.  Backward: in training mode (batch statistics), and in eval mode with frozen
 BatchNorm statistics when the input requires a gradient or ``freeze_batchnorm()`` is on.  The gradient w.r.t. the model input
 exists in both: through the batch statistics in training mode, through the fixed affine map in eval mode.
 """
