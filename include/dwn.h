@@ -425,6 +425,14 @@ int dwn_dw_spatial_fwd_rc_supported(const dwn_dw_spatial_fwd_args* a, int dtype)
 int dwn_dw_spatial_bwd_rc_supported(const dwn_dw_spatial_bwd_args* a, int dtype);
 int dwn_dw_temporal_fwd(const dwn_dw_temporal_fwd_args* a, int dtype, int device, void* stream);
 int dwn_dw_temporal_bwd(const dwn_dw_temporal_bwd_args* a, int dtype, int device, void* stream);
+/* The two entries above are built for kt 3 and 5 and answer -4 for every other size.  Sizes 7 and 9 have entries of their own, with
+ * the same argument structs and the same outputs (y3 or the z3 + pooling epilogue and the statistics forward; dh2, dw [C][kt] and the
+ * two BatchNorm-2 backward sums backward).  The backward is built for dy_kind == DWN_LD_PLAIN only, the form dwn_block_backward runs
+ * (y3 recomputed from y2, rounded to the storage type as a stored y3 would read back).  Refusals, all answered before the device is
+ * entered and with nothing written: kt not 7 or 9 -> -4; C % 8 != 0 -> -2; backward with DWN_LD_AFFINE2 / DWN_LD_DY3 (the stored-y3
+ * loaders, built for 3 and 5 only) or any other loader -> -3.  dwn_block_forward / dwn_block_backward take kt 3, 5, 7 and 9. */
+int dwn_dw_temporal_wide_fwd(const dwn_dw_temporal_fwd_args* a, int dtype, int device, void* stream);
+int dwn_dw_temporal_wide_bwd(const dwn_dw_temporal_bwd_args* a, int dtype, int device, void* stream);
 int dwn_bn_finalize(const double* stats, int stat_c, double count, const dwn_bn* bn, int C, int training,
                     float momentum, float eps, int device, void* stream);
 int dwn_bn_bwd_finalize(const double* stats, double count, const dwn_bn* bn, float* abc, int C, int device,

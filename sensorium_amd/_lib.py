@@ -216,6 +216,8 @@ SYMBOLS = {
     "dwn_dw_spatial_fwd_rc_supported": (c_i, [_P(DwSpatialFwdArgs), c_i]),
     "dwn_dw_temporal_fwd": (c_i, [_P(DwTemporalFwdArgs), c_i, c_i, c_p]),
     "dwn_dw_temporal_bwd": (c_i, [_P(DwTemporalBwdArgs), c_i, c_i, c_p]),
+    "dwn_dw_temporal_wide_fwd": (c_i, [_P(DwTemporalFwdArgs), c_i, c_i, c_p]),
+    "dwn_dw_temporal_wide_bwd": (c_i, [_P(DwTemporalBwdArgs), c_i, c_i, c_p]),
     "dwn_bn_finalize": (c_i, [c_p, c_i, c_d, _P(BN), c_i, c_i, c_f, c_f, c_i, c_p]),
     "dwn_bn_bwd_finalize": (c_i, [c_p, c_d, _P(BN), c_p, c_i, c_i, c_p]),
     "dwn_pack_weight": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
@@ -287,8 +289,9 @@ def _load():
     ab = bool(os.environ.get("DWN_LIB_PATH"))      # an explicitly chosen other build: a same-box A/B run of an older library
     for name, (restype, argtypes) in SYMBOLS.items():
         if ab and name in ("dwn_stem_input_grad", "dwn_stem_backward_input", "dwn_grad_guard_workspace_bytes", "dwn_grad_sumsq_multi",
-                           "dwn_step_guard_finalize", "dwn_adamw_ema_multi_guarded") and not hasattr(lib, name):
-            continue                     # (A/B: a library from before the input gradients / the guarded step; the plain training step calls neither)
+                           "dwn_step_guard_finalize", "dwn_adamw_ema_multi_guarded", "dwn_dw_temporal_wide_fwd",
+                           "dwn_dw_temporal_wide_bwd") and not hasattr(lib, name):
+            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries; the plain training step calls none of them)
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

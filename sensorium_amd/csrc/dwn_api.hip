@@ -290,7 +290,7 @@ ResGeom geom_of(const dwn_block_args& a) {
 int check_block(const dwn_block_args& a) {
     if (a.Cin % 8 || a.Cmid % 8 || a.Cout % 8) return dwn_set_error(-2, "block: channel counts must be multiples of 8");
     if (a.ks != 3 && a.ks != 5 && a.ks != 7) return dwn_set_error(-4, "block: spatial_kernel must be 3, 5 or 7 (the built set)");
-    if (a.kt != 3 && a.kt != 5) return dwn_set_error(-4, "block: temporal_kernel must be 3 or 5");
+    if (a.kt != 3 && a.kt != 5 && a.kt != 7 && a.kt != 9) return dwn_set_error(-4, "block: temporal_kernel must be 3, 5, 7 or 9 (the built set)");
     if (a.Hout != (a.Hin - 1) / a.stride + 1 || a.Wout != (a.Win - 1) / a.stride + 1)
         return dwn_set_error(-2, "block: Hout/Wout inconsistent with stride");
     return 0;
@@ -362,11 +362,26 @@ int dwn_dw_spatial_bwd_rc_supported(const dwn_dw_spatial_bwd_args* a, int dtype)
 int dwn_dw_spatial_fwd_rc_supported(const dwn_dw_spatial_fwd_args* a, int dtype) { return dw_spatial_fwd_rc_walk_supported(*a, dtype) ? 1 : 0; }
 int dwn_dw_temporal_fwd(const dwn_dw_temporal_fwd_args* a, int dtype, int device, void* stream) {
     ENTER(device);
+    // this entry's built set stays {3, 5}: the launcher behind it also serves the block path, where 7 and 9 go on to the wide kernels
+    if (a->kt != 3 && a->kt != 5) return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
     return launch_dw_temporal_fwd(*a, dtype, (hipStream_t)stream);
 }
 int dwn_dw_temporal_bwd(const dwn_dw_temporal_bwd_args* a, int dtype, int device, void* stream) {
     ENTER(device);
+    if (a->kt != 3 && a->kt != 5) return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
     return launch_dw_temporal_bwd(*a, dtype, (hipStream_t)stream);
+}
+int dwn_dw_temporal_wide_fwd(const dwn_dw_temporal_fwd_args* a, int dtype, int device, void* stream) {
+    g_err[0] = 0;
+    if (int rc = dw_temporal_wide_check(a->kt, a->C, LD_PLAIN)) return rc;
+    ENTER(device);
+    return launch_dw_temporal_wide_fwd(*a, dtype, (hipStream_t)stream);
+}
+int dwn_dw_temporal_wide_bwd(const dwn_dw_temporal_bwd_args* a, int dtype, int device, void* stream) {
+    g_err[0] = 0;
+    if (int rc = dw_temporal_wide_check(a->kt, a->C, a->dy_kind)) return rc;
+    ENTER(device);
+    return launch_dw_temporal_wide_bwd(*a, dtype, (hipStream_t)stream);
 }
 int dwn_bn_finalize(const double* stats, int stat_c, double count, const dwn_bn* bn, int C, int training,
                     float momentum, float eps, int device, void* stream) {

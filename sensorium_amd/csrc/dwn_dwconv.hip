@@ -833,12 +833,21 @@ __global__ __launch_bounds__(256) void dw_temporal_fwd_kernel(const DwTemporalFw
                 if (t >= 0 && t < a.T) { ld4<T>(ip + t * tstride, win[k]); bn_silu4(win[k], bs, bt); }
                 else { win[k][0] = win[k][1] = win[k][2] = win[k][3] = 0.f; }
             }
+            [[maybe_unused]] T* sp = op;                                  // KT > 5: frame t of the next store
+            [[maybe_unused]] const T* lp = ip + P * tstride;           // KT > 5: frame t0 + u + P of the next load
             for (int t0 = 0; t0 < a.T; t0 += KT) {
                 raw_t raw[KT];
 #pragma unroll
                 for (int u = 0; u < KT; ++u) {
                     int tl = t0 + u + P;
-                    raw[u] = ld4_raw<T>(ip + (tl < a.T ? tl : 0) * tstride);
+                    if constexpr (KT > 5) {
+                        // sizes 7 and 9: the look-ahead pointer advances in vector registers; KT scalar offsets at once run the
+                        // deterministic build out of scalar registers
+                        raw[u] = ld4_raw<T>(tl < a.T ? lp : ip);
+                        lp += tstride;
+                    } else {
+                        raw[u] = ld4_raw<T>(ip + (tl < a.T ? tl : 0) * tstride);
+                    }
                 }
 #pragma unroll
                 for (int u = 0; u < KT; ++u) {
@@ -859,9 +868,9 @@ __global__ __launch_bounds__(256) void dw_temporal_fwd_kernel(const DwTemporalFw
                         silu_n<4>(z);
 #pragma unroll
                         for (int i = 0; i < 4; ++i) ps[i] += round_t<T>(z[i]);
-                        st4<T>(op + t * tstride, z);
+                        st4<T>(KT > 5 ? sp : op + t * tstride, z);
                     } else {
-                        st4<T>(op + t * tstride, acc);
+                        st4<T>(KT > 5 ? sp : op + t * tstride, acc);
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
                             float r = round_t<T>(acc[i]);
@@ -869,6 +878,7 @@ __global__ __launch_bounds__(256) void dw_temporal_fwd_kernel(const DwTemporalFw
                             st1[i] += r * r;
                         }
                     }
+                    if constexpr (KT > 5) sp += tstride;
                 }
             }
             if constexpr (ZOUT) {
@@ -1879,6 +1889,7 @@ static int temporal_fwd_t(const DwTemporalFwd& a, hipStream_t s) {
     return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
 }
 int launch_dw_temporal_fwd(const DwTemporalFwd& a, int dtype, hipStream_t s) {
+    if (a.kt == 7 || a.kt == 9) return launch_dw_temporal_wide_fwd(a, dtype, s);       // sizes 7 and 9: at the end of this file
     return dtype == DWN_BF16 ? temporal_fwd_t<bf16_t>(a, s) : temporal_fwd_t<float>(a, s);
 }
 
@@ -2059,5 +2070,248 @@ static int temporal_bwd_t(const DwTemporalBwd& a, hipStream_t s) {
     return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
 }
 int launch_dw_temporal_bwd(const DwTemporalBwd& a, int dtype, hipStream_t s) {
+    if (a.kt == 7 || a.kt == 9) return launch_dw_temporal_wide_bwd(a, dtype, s);       // sizes 7 and 9: below
     return dtype == DWN_BF16 ? temporal_bwd_t<bf16_t>(a, s) : temporal_bwd_t<float>(a, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// temporal kernel sizes 7 and 9: the y3-recomputing backward with another register plan.
+//
+// dw_temporal_bwd_rc_kernel holds, per thread, the weights, the weight-gradient accumulators and four rings of [KT][4] floats:
+// 24*KT registers before the loads in flight (216 at KT = 9), which does not fit the 256 of two waves per SIMD.  Here
+//   * the weights are an LDS table [tap][channel], one broadcast ds_read_b128 per tap and output frame, read through a volatile
+//     pointer so that the reads of the unrolled tap loop stay where they are used (hoisted, they are the 4*KT registers again);
+//   * there is no SiLU' ring and the y2 ring is in LDS, in storage form, a column per thread (KT * 2 or 4 KB per workgroup, one
+//     write and one read per frame): both serve the output frame only, so y2(t) is unpacked and its sigmoid taken a second
+//     time there, 2P frames after the first.  Only frames inside [0, T) are ever read back, so the ring has no zero slots;
+//   * the loads are not issued a batch of KT frames at a time but D frames ahead of their use, rolling through the unrolled
+//     batch: D + 1 raw frames of each tensor are live instead of KT.
+// What remains is the z2 ring, the dy3 ring and the weight gradient, 12*KT registers.  The arithmetic is that of the rc kernel
+// (y3 rounded to storage as a stored y3 would read back, the same sums), with one difference in order: the newest tap of dz2,
+// the one that waits for the frame's own dy3, is added last.
+// ------------------------------------------------------------------------------------------------
+typedef float dwt_f4_t __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) dwt_f4_t dwt_lds_f4_t;      // an LDS pointer by type: a volatile read through a generic one is a flat load
+
+template <typename T, int KT>
+__global__ __launch_bounds__(256, DWT_RC_MINW) void dw_temporal_bwd_wide_kernel(const DwTemporalBwd a) {
+    constexpr int NCV = SL<T>::NCV, CS = SL<T>::CS, LP = SL<T>::LP, P = KT / 2, NW = 2 * P + 1;
+    constexpr int TB = NW;            // frames per unrolled batch == window length: ring indices are compile-time, no shifting
+    constexpr int D = TT<T>::IS_BF16 ? 4 : (KT > 7 ? 2 : 3);     // frames a load is issued ahead of its use
+    static_assert(NW == KT && D < TB, "odd kernel: window length == kernel length; the look-ahead stays inside one batch");
+    typedef typename SL<T>::raw_t raw_t;
+    __shared__ float lstat[2 * CS];
+    __shared__ float lw[KT * CS];
+    __shared__ __attribute__((aligned(16))) float lwt[KT * CS];       // weights [tap][channel of the slice]
+    __shared__ raw_t lyr[NW * 256];                                   // y2 ring [slot][thread], as stored
+    const int tid = threadIdx.x;
+    const int cv = tid % NCV, pl = tid / NCV;
+    const int c0 = blockIdx.y * CS;
+    const int chan = c0 + cv * 4;
+    const bool chan_ok = chan < a.C;
+    const int chs = chan_ok ? chan : 0;
+    if (tid < 2 * CS) lstat[tid] = 0.f;
+    for (int i = tid; i < KT * CS; i += 256) {
+        const int k = i / CS, c = c0 + i % CS;
+        lw[i] = 0.f;
+        lwt[i] = c < a.C ? a.w[(i64)k * a.C + c] : 0.f;
+    }
+    __syncthreads();
+    const volatile dwt_lds_f4_t* wtab = (const volatile dwt_lds_f4_t*)lwt + cv;      // tap k: wtab[k * NCV]
+    raw_t* const yr = lyr + tid;            // a thread's own column: no barrier; a slot is written before the step that reads it
+    float dwacc[KT][4];
+#pragma unroll
+    for (int k = 0; k < KT; ++k) dwacc[k][0] = dwacc[k][1] = dwacc[k][2] = dwacc[k][3] = 0.f;
+    float bs[4], bt[4], a1[4], a2[4], a3[4];
+    ldc4(a.y2.v1 + chs, bs); ldc4(a.y2.v2 + chs, bt);
+    ldc4(a.dy.v1 + chs, a1); ldc4(a.dy.v2 + chs, a2); ldc4(a.dy.v3 + chs, a3);
+    float st0[4] = {0.f, 0.f, 0.f, 0.f}, st1[4] = {0.f, 0.f, 0.f, 0.f};
+
+    const i64 npos = (i64)a.B * a.HW;
+    T* dhp = reinterpret_cast<T*>(a.dh2);
+    const T* y2p = reinterpret_cast<const T*>(a.y2.p);
+    const T* dpp = reinterpret_cast<const T*>(a.dy.p);
+    const i64 tstride = (i64)a.HW * a.C;
+
+    if (chan_ok) {
+        for (i64 pos = (i64)blockIdx.x * LP + pl; pos < npos; pos += (i64)gridDim.x * LP) {
+            const i64 b = pos / a.HW, hw = pos % a.HW;
+            const i64 e0 = (b * a.T * a.HW + hw) * a.C + chan;
+            // rings of NW = KT slots: at unrolled step u of a batch, frame t + j of (y2 as stored, z2) lives in slot (u + j) % NW
+            // and dy3(t + k - P) in win[(u + k) % KT].  Frames outside [0, T) are zero slots.
+            float zw[NW][4], win[KT][4];
+#pragma unroll
+            for (int j = 0; j < NW; ++j) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { zw[j][i] = 0.f; win[j][i] = 0.f; }
+            }
+            // z2 of a stored y2 frame; with ds also SiLU' (the output frame's second visit)
+            auto activate = [&](const raw_t& raw, float* y, float* z, float* ds) {
+                V4<T>::unpack(raw, y);
+                float h4[4], sg4[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) h4[i] = fmaf(y[i], bs[i], bt[i]);
+                sigmoid_n<4>(h4, sg4);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float h = h4[i], sg = sg4[i];
+                    z[i] = h * sg;
+                    if (ds) ds[i] = sg * (1.0f + h * (1.0f - sg));
+                }
+            };
+            // the frames fetched for the output frame t: dh3(t + P) and y2(t + 2P), clamped inside the tensor (unused past T)
+            auto fetch = [&](int t, raw_t& rp, raw_t& ry) {
+                const int td = t + P, ty = t + 2 * P;
+                rp = ld4_raw<T>(dpp + e0 + (td < a.T ? td : 0) * tstride);
+                ry = ld4_raw<T>(y2p + e0 + (ty < a.T ? ty : 0) * tstride);
+            };
+            // at virtual frame t = -P the window covers frames -P .. P-1: load frames 0 .. P-1 into slots P .. 2P-1
+#pragma unroll
+            for (int j = 0; j < P; ++j)
+                if (j < a.T) {
+                    float y[4];
+                    const raw_t r = ld4_raw<T>(y2p + e0 + j * tstride);
+                    yr[(P + j) * 256] = r;
+                    activate(r, y, zw[P + j], nullptr);
+                }
+            raw_t rp[TB], ry[TB];                       // slot u: the frames of step u; D + 1 of them are live at a time
+#pragma unroll
+            for (int u = 0; u < D; ++u) fetch(-P + u, rp[u], ry[u]);
+            for (int t0 = -P; t0 < a.T; t0 += TB) {
+#pragma unroll
+                for (int u = 0; u < TB; ++u) {
+                    const int t = t0 + u;
+                    if (t >= a.T) break;
+                    fetch(t + D, rp[(u + D) % TB], ry[(u + D) % TB]);
+                    const int sn = (u + NW - 1) % NW;                   // newest slot (frame t + 2P)
+                    const int s0 = u % NW;                              // slot of the output frame t
+                    if (t + 2 * P < a.T) {
+                        float y[4];
+                        yr[sn * 256] = ry[u];
+                        activate(ry[u], y, zw[sn], nullptr);
+                    } else {
+                        zw[sn][0] = zw[sn][1] = zw[sn][2] = zw[sn][3] = 0.f;
+                    }
+                    const bool dy_ok = t + P < a.T;
+                    float p[4];
+                    V4<T>::unpack(rp[u], p);
+                    if (u >= P || t >= 0) {
+                        // one pass over the taps: y3(t + P) = sum_j w[j] z2(t + j), and of dz2(t) = sum_k w[k] dy3(t + P - k) and
+                        // dW[k] += z2(t) dy3(t + P - k) the taps k >= 1, whose dy3 the ring already holds
+                        float y3[4] = {0.f, 0.f, 0.f, 0.f}, dz[4] = {0.f, 0.f, 0.f, 0.f}, w0[4];
+#pragma unroll
+                        for (int k = 0; k < KT; ++k) {
+                            const dwt_f4_t wk = wtab[k * NCV];
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                y3[i] = fmaf(wk[i], zw[(u + k) % NW][i], y3[i]);
+                                if (k == 0) w0[i] = wk[i];
+                                else {
+                                    const float gk = win[(u + KT - 1 - k) % KT][i];
+                                    dz[i] = fmaf(wk[i], gk, dz[i]);
+                                    dwacc[k][i] = fmaf(zw[s0][i], gk, dwacc[k][i]);
+                                }
+                            }
+                        }
+                        float y[4], z[4], ds[4], dh[4];
+                        activate(yr[s0 * 256], y, z, ds);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const float g0 = dy_ok ? fmaf(a1[i], p[i], fmaf(a2[i], round_t<T>(y3[i]), a3[i])) : 0.f;
+                            win[sn][i] = g0;
+                            dz[i] = fmaf(w0[i], g0, dz[i]);
+                            dwacc[0][i] = fmaf(zw[s0][i], g0, dwacc[0][i]);
+                            dh[i] = dz[i] * ds[i];
+                        }
+                        st4<T>(dhp + e0 + t * tstride, dh);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const float r = round_t<T>(dh[i]);
+                            st0[i] += r;
+                            st1[i] = fmaf(r, y[i], st1[i]);              // raw sum(dh2 * y2): normalised once, below
+                        }
+                    } else {
+                        // the P frames before frame 0: only dy3(t + P) is due
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) win[sn][i] = 0.f;
+                        if (dy_ok) {
+                            float y3[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                            for (int k = 0; k < KT; ++k) {
+                                const dwt_f4_t wk = wtab[k * NCV];
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) y3[i] = fmaf(wk[i], zw[(u + k) % NW][i], y3[i]);
+                            }
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) win[sn][i] = fmaf(a1[i], p[i], fmaf(a2[i], round_t<T>(y3[i]), a3[i]));
+                        }
+                    }
+                }
+            }
+        }
+    }
+    // sum(dh2 * (y2 - mean) * invstd) = invstd * (sum(dh2 * y2) - mean * sum(dh2)), as in the rc kernel; mean and invstd are
+    // fetched here, not held through the loop
+    {
+        float bm[4], bi[4];
+        ldc4(a.y2.v3 + chs, bm); ldc4(a.y2.v4 + chs, bi);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) st1[i] = bi[i] * fmaf(-bm[i], st0[i], st1[i]);
+    }
+    DET_WAVES_BEGIN
+    if (chan_ok) {
+#pragma unroll
+        for (int k = 0; k < KT; ++k)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) atomicAdd(&lw[k * CS + cv * 4 + i], dwacc[k][i]);
+    }
+    DET_WAVES_END
+    __syncthreads();
+    DET_ENTER();
+    for (int i = tid; i < KT * CS; i += 256) {
+        int k = i / CS, c = c0 + i % CS;
+        if (c < a.C) atomicAdd(a.dw + (i64)c * KT + k, lw[i]);
+    }
+    if (a.stats) block_stats_flush<T>(lstat, st0, st1, cv, c0, a.C, a.stats, blockIdx.x % DWN_NREP);
+    DET_EXIT();
+}
+
+// what the two launchers below refuse, in this order; host only, so the C entries ask it before they enter the device
+int dw_temporal_wide_check(int kt, int C, int dy_kind) {
+    if (kt != 7 && kt != 9) return dwn_set_error(-4, "dw_temporal_wide: only temporal_kernel 7 or 9 is built (3 and 5: dwn_dw_temporal_fwd / _bwd)");
+    if (C % 8) return dwn_set_error(-2, "dw_temporal_wide: C must be a multiple of 8");
+    if (dy_kind != LD_PLAIN)
+        return dwn_set_error(-3, "dw_temporal_wide_bwd: the stored-y3 loaders (LD_AFFINE2, LD_DY3) are built for temporal_kernel 3 and 5 only");
+    return 0;
+}
+
+template <typename T>
+static int temporal_wide_fwd_t(const DwTemporalFwd& a, hipStream_t s) {
+    constexpr int CS = SL<T>::CS, LP = SL<T>::LP;
+    const int slices = (a.C + CS - 1) / CS;
+    const i64 work = ((i64)a.B * a.HW + LP - 1) / LP;
+    if (a.z_scale) {
+        if (!a.z_shift || a.stats) return dwn_set_error(-2, "dw_temporal: the z3 epilogue needs z_shift and no statistics (eval mode)");
+        if (a.kt == 9) return launch_dw(dw_temporal_fwd_kernel<T, 9, true>, 256, 0, slices, work, s, a);
+        return launch_dw(dw_temporal_fwd_kernel<T, 7, true>, 256, 0, slices, work, s, a);
+    }
+    if (a.kt == 9) return launch_dw(dw_temporal_fwd_kernel<T, 9>, 256, 0, slices, work, s, a);
+    return launch_dw(dw_temporal_fwd_kernel<T, 7>, 256, 0, slices, work, s, a);
+}
+int launch_dw_temporal_wide_fwd(const DwTemporalFwd& a, int dtype, hipStream_t s) {
+    if (int rc = dw_temporal_wide_check(a.kt, a.C, LD_PLAIN)) return rc;
+    return dtype == DWN_BF16 ? temporal_wide_fwd_t<bf16_t>(a, s) : temporal_wide_fwd_t<float>(a, s);
+}
+
+template <typename T>
+static int temporal_wide_bwd_t(const DwTemporalBwd& a, hipStream_t s) {
+    constexpr int CS = SL<T>::CS, LP = SL<T>::LP;
+    const int slices = (a.C + CS - 1) / CS;
+    const i64 work = ((i64)a.B * a.HW + LP - 1) / LP;
+    if (a.kt == 9) return launch_dw(dw_temporal_bwd_wide_kernel<T, 9>, 256, 0, slices, work, s, a);
+    return launch_dw(dw_temporal_bwd_wide_kernel<T, 7>, 256, 0, slices, work, s, a);
+}
+int launch_dw_temporal_wide_bwd(const DwTemporalBwd& a, int dtype, hipStream_t s) {
+    if (int rc = dw_temporal_wide_check(a.kt, a.C, a.dy_kind)) return rc;
+    return dtype == DWN_BF16 ? temporal_wide_bwd_t<bf16_t>(a, s) : temporal_wide_bwd_t<float>(a, s);
 }

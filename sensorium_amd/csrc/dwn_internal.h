@@ -22,6 +22,10 @@ int launch_dw_spatial_fwd(const DwSpatialFwd& a, int dtype, hipStream_t s);
 int launch_dw_spatial_bwd(const DwSpatialBwd& a, int dtype, hipStream_t s);
 int launch_dw_temporal_fwd(const DwTemporalFwd& a, int dtype, hipStream_t s);
 int launch_dw_temporal_bwd(const DwTemporalBwd& a, int dtype, hipStream_t s);
+// temporal kernel sizes 7 and 9 (the two launchers above hand these sizes on); the check is host-only
+int dw_temporal_wide_check(int kt, int C, int dy_kind);
+int launch_dw_temporal_wide_fwd(const DwTemporalFwd& a, int dtype, hipStream_t s);
+int launch_dw_temporal_wide_bwd(const DwTemporalBwd& a, int dtype, hipStream_t s);
 bool pw_bwd_fused_supported(int dtype, long long M, int E, int Cin);
 int launch_pw_bwd_fused(const void* dh1, const void* a0, const void* bp, const float* r3, void* da0, float* tacc,
                         long long M, int E, int Cin, int dtype, const void* res, const float* res_coef, int res_n,

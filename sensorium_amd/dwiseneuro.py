@@ -12,7 +12,7 @@ under ``torch.autocast`` (the reference trains under fp16 autocast, src/argus_mo
 autocast both select the bf16 path here) or when ``compute_dtype=torch.bfloat16`` is set explicitly.
 
 Constraints of the HIP path (raised loudly, no fallback): channel counts multiples of 8, spatial_kernel 3, 5
-or 7 (5 and 7 through the stored-y1 path: no rebuilt-y1 / row-walk / tile-resident variants), temporal_kernel 3 or 5, CUDA/HIP tensors only.  Backward: in training mode (batch statistics), and in eval mode with frozen
+or 7 (5 and 7 through the stored-y1 path: no rebuilt-y1 / row-walk / tile-resident variants), temporal_kernel 3, 5, 7 or 9 (7 and 9 through the kernels of DESIGN.md 12f), CUDA/HIP tensors only.  Backward: in training mode (batch statistics), and in eval mode with frozen
 BatchNorm statistics when the input requires a gradient or ``freeze_batchnorm()`` is on.  The gradient w.r.t. the model input
 exists in both: through the batch statistics in training mode, through the fixed affine map in eval mode.
 """
