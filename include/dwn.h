@@ -130,6 +130,10 @@ typedef struct dwn_gemm_nn_args {
      * N % 128 == 0, plain / gate loader, store / K-concat epilogue); DWN_NN_TILE128 = never those kernels (the tests compare them
      * with the 128-row kernel bit for bit) */
     int variant;
+    /* DWN_EPI_READOUT, optional: the Softplus beta in DEVICE memory (one fp32).  Non-null: read by the kernel (one uniform load per
+     * workgroup) instead of sp_beta — a learnable beta, or one changed between replays of a captured graph.  Plain loader only.
+     * Null: sp_beta, and the kernel that ran before this field existed. */
+    const float* sp_beta_dev;
 } dwn_gemm_nn_args;
 #define DWN_NN_AUTO 0
 #define DWN_NN_XL128 1
@@ -337,6 +341,15 @@ typedef struct dwn_readout_args {
      * instead of packing the weight again. */
     void* wt;
     int f32_products;                       /* DWN_F32_AUTO (= native here: the readout has no training flag) / _NATIVE / _SPLIT3 */
+    /* learnable Softplus beta; both null = the fixed softplus_beta above, and the kernels that ran before these
+     * fields existed.
+     * beta_dev: one fp32 in device memory, > 0, read by the forward epilogue and by the backward instead of softplus_beta (which
+     *   is then ignored).  The same value gives the same bits of out / dx / dw as the fixed path.  Forward needs only this one.
+     * dbeta: one fp32 in device memory; dwn_readout_backward OVERWRITES it with sum_{b,n,t} dout * d out / d beta — reduced in
+     *   float64, one partial per workgroup in the workspace and a fixed-order finaliser: no atomics, bit-reproducible in both
+     *   builds.  dwn_readout_backward wants both pointers or neither (-2 otherwise); dwn_readout_workspace_bytes(a, 1) accounts
+     *   for the partials when beta_dev is set. */
+    const float* beta_dev; float* dbeta;
 } dwn_readout_args;
 
 typedef struct dwn_tensor_entry {

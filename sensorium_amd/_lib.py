@@ -56,7 +56,7 @@ class GemmNNArgs(C.Structure):
                 ("sp_beta", c_f), ("out_nct", c_p), ("Tn", c_i), ("n_valid", c_i), ("y3", c_p), ("ldy3", c_ll),
                 ("s3", c_p), ("t3", c_p), ("dg", c_p), ("dg_ld", c_i), ("rows_per_sample", c_i),
                 ("a2", c_p), ("a2_ld", c_ll), ("K1", c_i), ("b_sample_stride", c_ll), ("b_rows_per_sample", c_i),
-                ("gate3", c_p), ("dps3", c_p), ("coef3", c_p), ("coef3_ld", c_i), ("variant", c_i)]
+                ("gate3", c_p), ("dps3", c_p), ("coef3", c_p), ("coef3_ld", c_i), ("variant", c_i), ("sp_beta_dev", c_p)]
 
 
 class GemmTNArgs(C.Structure):
@@ -144,7 +144,7 @@ class ReadoutArgs(C.Structure):
     _fields_ = [("dtype", c_i), ("B", c_i), ("T", c_i), ("Cin", c_i), ("groups", c_i), ("n_out", c_i),
                 ("softplus_beta", c_f), ("x", c_p), ("w", c_p), ("bias", c_p), ("drop_mask", c_p), ("out", c_p),
                 ("dout", c_p), ("dx", c_p), ("dw", c_p), ("dbias", c_p), ("ws", c_p), ("ws_bytes", c_sz), ("wt", c_p),
-                ("f32_products", c_i)]
+                ("f32_products", c_i), ("beta_dev", c_p), ("dbeta", c_p)]      # learnable Softplus beta: both null = softplus_beta
 
 
 class TensorEntry(C.Structure):

@@ -124,7 +124,10 @@ class MouseModel(Model):
         if self.buckets is not None:
             self.buckets.adopt_ema(ema.ema)       # sharded readout buckets: EMA copies laid out like the parameters
         by_name = dict(ema.ema.named_parameters())
-        ema_params = [by_name[n] for n, p in self.nn_module.named_parameters() if p.requires_grad]
+        # in the optimizer's flat order (group by group): with the Softplus parameters in a group of their own that is not the
+        # module's registration order
+        name_of = {id(p): n for n, p in self.nn_module.named_parameters()}
+        ema_params = [by_name[name_of[id(p)]] for g in self.optimizer.param_groups for p in g["params"]]
         self.optimizer.bind_ema(ema_params, ema.decay, owner=ema)
 
     def set_ema(self, decay: float):
@@ -162,6 +165,15 @@ class MouseModel(Model):
             self.buckets = GradBuckets(self.nn_module, comm_dtype=comm, shard_optional=bool(shard), single_rank=single)
             if self._model_ema is not None:                   # ... so the EMA copy taken earlier must follow (val_step uses it)
                 self._model_ema.set(self.nn_module)
+        # learnable Softplus beta: a group of its own without weight decay (decoupled decay would pull beta towards 0 all run
+        # long), lr / betas as everybody's; params["softplus_optimizer"] overrides.  Without such parameters: one group, as ever
+        soft = [p for p in getattr(self.nn_module, "softplus_parameters", list)() if p.requires_grad]
+        if soft:
+            ids = {id(p) for p in soft}
+            params = [{"params": [p for p in params if id(p) not in ids]},
+                      {"params": soft, "weight_decay": 0.0, **dict(self.params.get("softplus_optimizer", {}))}]
+            if not params[0]["params"]:
+                params = params[1:]                      # (only the gate parameters are trainable)
         self.optimizer = MouseModel.optimizer[oname](params, **okwargs)
         if self.buckets is not None and self.buckets.shard:
             self.optimizer.set_shard_map(self.buckets.owned_range)

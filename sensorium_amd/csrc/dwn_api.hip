@@ -966,7 +966,7 @@ int dwn_cortex_backward(const dwn_cortex_args* ap, int device, void* stream) {
 
 // ------------------------------------------------------------------------------------------------ readout
 namespace {
-struct ReadoutWs { void* wp; void* dz; void* xd; size_t bytes; int Npad, Rg, Rp, ldp, ldt; };
+struct ReadoutWs { void* wp; void* dz; void* xd; double* dbp; size_t bytes; int Npad, Rg, Rp, ldp, ldt; };
 ReadoutWs carve_readout(const dwn_readout_args& a, int backward, void* base, size_t cap) {
     ReadoutWs w; memset(&w, 0, sizeof(w));
     Carver c(base, cap);
@@ -980,6 +980,7 @@ ReadoutWs carve_readout(const dwn_readout_args& a, int backward, void* base, siz
     w.wp = c.take<char>(backward ? (a.wt ? 0 : (size_t)a.groups * Kg * w.ldt * ts) : (size_t)w.Npad * w.ldp * ts);
     if (backward) w.dz = c.take<char>((size_t)M * a.groups * w.Rp * ts);
     if (a.drop_mask) w.xd = c.take<char>((size_t)M * a.Cin * ts);      // x * dropout mask, materialised once
+    if (backward && a.beta_dev) w.dbp = c.take<double>(k_readout_dbeta_parts(a.B, w.Rp, a.groups));   // dbeta: one partial per workgroup
     w.bytes = c.off + 256;
     return w;
 }
@@ -1012,12 +1013,14 @@ int dwn_readout_forward(const dwn_readout_args* ap, int device, void* stream) {
         x = ld_plain(w.xd, a.Cin);
     }
     GemmNN g = nn_base(x, kind, w.wp, w.ldp, nullptr, 0, M, w.Rg, Kg, a.groups);
-    g.epi = EPI_READOUT; g.bias = a.bias; g.sp_beta = a.softplus_beta; g.out_nct = a.out; g.Tn = a.T; g.n_valid = a.n_out;
+    g.epi = EPI_READOUT; g.bias = a.bias; g.sp_beta = a.softplus_beta; g.sp_beta_dev = a.beta_dev; g.out_nct = a.out; g.Tn = a.T; g.n_valid = a.n_out;
     g.f32_split = f32_split_of(a.f32_products, false);            // the caller says (it knows whether this is an inference forward)
     PROF(DWN_FAM_READOUT_FWD, launch_gemm_nn(g, dt, s));
     return 0;
 }
 int dwn_readout_backward(const dwn_readout_args* ap, int device, void* stream) {
+    if (ap && (ap->beta_dev != nullptr) != (ap->dbeta != nullptr))       // (answered before the device is entered)
+        return dwn_set_error(-2, "readout_backward: beta_dev and dbeta come together (both null: the fixed softplus_beta)");
     ENTER(device);
     const dwn_readout_args& a = *ap;
     hipStream_t s = (hipStream_t)stream;
@@ -1026,7 +1029,7 @@ int dwn_readout_backward(const dwn_readout_args* ap, int device, void* stream) {
     const int M = a.B * a.T, Kg = a.Cin / a.groups, dt = a.dtype;
     const void* wt = a.wt;                       // per group W^T [Kg][Rp], zero padded: kept from the forward, or packed now
     if (!wt) { TRY(k_pack_weight_dual(a.w, nullptr, w.wp, a.groups, w.Rg, Kg, w.Rp, w.ldp, w.ldt, dt, s)); wt = w.wp; }
-    TRY(k_readout_dz(a.dout, a.out, a.softplus_beta, a.B, a.T, a.n_out, w.Rg, w.Rp, a.groups, w.dz, a.dbias, dt, s));
+    TRY(k_readout_dz(a.dout, a.out, a.softplus_beta, a.beta_dev, w.dbp, a.dbeta, a.B, a.T, a.n_out, w.Rg, w.Rp, a.groups, w.dz, a.dbias, dt, s));
     LoadDesc dz = ld_plain(w.dz, (i64)a.groups * w.Rp);
     {
         GemmNN g = nn_base(dz, LD_PLAIN, wt, w.ldt, a.dx, a.Cin, M, Kg, w.Rp, a.groups);

@@ -2144,12 +2144,34 @@ int k_gate_weights(const float* w, const float* gate, void* dst, int B, int N, i
 // The derivative sigmoid(beta*z) is formed as -expm1(-beta*out): for a quiet neuron (beta*z << 0) beta*out = log1p(exp(beta*z))
 // is tiny and 1 - exp(-beta*out) would cancel to steps of 6e-8 (17 % off at beta*z = -15, exactly 0 from -17 down), while
 // the Poisson gradient 1 - y/(out + eps) on such an element is of order 1/out, so dL/dz stays O(y).
-template <typename T>
-__global__ __launch_bounds__(256) void readout_dz_kernel(const float* dout, const float* out, float beta, int Tn,
-                                                         int n_valid, int Rg, int Rp, int groups, T* dz, float* db) {
+// Learnable beta: LB = true reads beta from device memory (one uniform load) and, in the same pass
+// over dout / out, reduces this workgroup's part of  dbeta = sum dout * dg/dbeta  in float64 into part[workgroup] — no atomics:
+// a one-workgroup finaliser (readout_dbeta_fold_kernel) adds the partials in a fixed order.  LB = false is the fixed-beta
+// kernel: the same arithmetic in the same order as before the variant existed (the compiler schedules the shared body slightly
+// differently: one more address instruction at -O3 for gfx950).
+// With g = softplus(beta z)/beta, u = beta*g (the stored output), e = exp(-u), sigma = sigmoid(beta z) = 1 - e:
+//   beta^2 * dg/dbeta = beta z sigma - u = sigma*log(sigma) - u*e        (beta z = u + log(sigma))
+// Both terms have the same sign, so nothing cancels (recovering beta z and forming beta z sigma - u does: 2.6 % off at beta z = 15,
+// exactly 0 from 17.5 up).  log(sigma) = log(-expm1(-u)) up to u = ln 2 and log1p(-e) above: sigma itself rounds to 1 - k 2^-24
+// there (5.4 % off at beta z = 17.5 without the split).  out == 0 (beta z below about -104 + ln beta): 0 * -inf, contributes 0.
+// u = beta*out is rounded to fp32 and e = exp(-u) carries that error u times over (1.4e-6 relative at u = 23): the product's exact
+// residual du = fma(beta, out, -u) puts it back, e (1 - du).  The division by beta^2 is done once, in float64, by the finaliser.
+__device__ __forceinline__ float readout_dbeta_term(float beta, float out) {
+    const float u = beta * out;
+    const float e0 = expf(-u);
+    const float e = fmaf(-e0, fmaf(beta, out, -u), e0);
+    const float sg = -expm1f(-u);
+    if (!(sg > 0.f)) return 0.f;
+    const float lg = u <= 0.69314718f ? logf(sg) : log1pf(-e);
+    return sg * lg - u * e;
+}
+template <typename T, bool LB>
+__device__ __forceinline__ void readout_dz_body(const float* dout, const float* out, float beta, int Tn, int n_valid, int Rg,
+                                                int Rp, int groups, T* dz, float* db, [[maybe_unused]] double* part) {
     extern __shared__ float tile[];        // [64][Tn+1]
     const int b = blockIdx.y, n0 = blockIdx.x * 64, tid = threadIdx.x;
     const int npad_total = groups * Rp;
+    [[maybe_unused]] double acc = 0.0;
     for (int i = tid; i < 64 * Tn; i += 256) {
         int nl = i / Tn, t = i % Tn;
         int np = n0 + nl;                  // index in the padded [groups][Rp] space
@@ -2159,10 +2181,20 @@ __global__ __launch_bounds__(256) void readout_dz_kernel(const float* dout, cons
         if (np < npad_total && r < Rg && n < n_valid) {
             i64 off = ((i64)b * n_valid + n) * Tn + t;
             v = dout[off] * -expm1f(-beta * out[off]);
+            if constexpr (LB) acc += (double)dout[off] * (double)readout_dbeta_term(beta, out[off]);
         }
         tile[nl * (Tn + 1) + t] = v;
     }
-    __syncthreads();
+    if constexpr (LB) {
+        // fixed order: butterfly inside each wave, the four wave sums through LDS, added by one lane
+        __shared__ double wsum[4];
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if ((tid & 63) == 0) wsum[tid >> 6] = acc;
+        __syncthreads();
+        if (tid == 0) part[(i64)blockIdx.y * gridDim.x + blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    } else {
+        __syncthreads();
+    }
     for (int i = tid; i < 64 * Tn; i += 256) {
         int t = i / 64, nl = i % 64;
         int np = n0 + nl;
@@ -2181,10 +2213,47 @@ __global__ __launch_bounds__(256) void readout_dz_kernel(const float* dout, cons
     }
     DET_EXIT();
 }
-int k_readout_dz(const float* dout, const float* out, float beta, int B, int Tn, int n_valid, int Rg, int Rp,
-                 int groups, void* dz, float* db, int dtype, hipStream_t s) {
+template <typename T>
+__global__ __launch_bounds__(256) void readout_dz_kernel(const float* dout, const float* out, float beta, int Tn,
+                                                         int n_valid, int Rg, int Rp, int groups, T* dz, float* db) {
+    readout_dz_body<T, false>(dout, out, beta, Tn, n_valid, Rg, Rp, groups, dz, db, nullptr);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void readout_dz_dbeta_kernel(const float* dout, const float* out, const float* beta_p, int Tn,
+                                                               int n_valid, int Rg, int Rp, int groups, T* dz, float* db,
+                                                               double* part) {
+    readout_dz_body<T, true>(dout, out, *beta_p, Tn, n_valid, Rg, Rp, groups, dz, db, part);
+}
+// one workgroup: the partials in index order per lane, then the same fixed tree; dbeta = sum / beta^2
+__global__ __launch_bounds__(256) void readout_dbeta_fold_kernel(const double* part, int npart, const float* beta_p, float* dbeta) {
+    __shared__ double wsum[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < npart; i += 256) acc += part[i];
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double beta = (double)*beta_p;
+        *dbeta = (float)((((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]) / (beta * beta));
+    }
+}
+// beta_dev == null: the fixed-beta kernel with the scalar `beta`.  Otherwise beta is read from beta_dev, and `part` (one double
+// per workgroup: k_readout_dbeta_parts) + `dbeta` receive the gradient w.r.t. it (overwritten).
+size_t k_readout_dbeta_parts(int B, int Rp, int groups) { return (size_t)((groups * Rp + 63) / 64) * (size_t)B; }
+int k_readout_dz(const float* dout, const float* out, float beta, const float* beta_dev, double* part, float* dbeta, int B, int Tn,
+                 int n_valid, int Rg, int Rp, int groups, void* dz, float* db, int dtype, hipStream_t s) {
     dim3 grid((groups * Rp + 63) / 64, B);
     size_t lds = (size_t)64 * (Tn + 1) * sizeof(float);
+    if (beta_dev) {
+        if (!part || !dbeta) return dwn_set_error(-2, "readout_dz: a device beta needs the partials workspace and the dbeta result");
+        DISPATCH_T(dtype,
+            hipLaunchKernelGGL((readout_dz_dbeta_kernel<bf16_t>), grid, dim3(256), lds, s, dout, out, beta_dev, Tn, n_valid, Rg, Rp, groups, (bf16_t*)dz, db, part),
+            hipLaunchKernelGGL((readout_dz_dbeta_kernel<float>), grid, dim3(256), lds, s, dout, out, beta_dev, Tn, n_valid, Rg, Rp, groups, (float*)dz, db, part));
+        DWN_CHECK_LAUNCH();
+        hipLaunchKernelGGL(readout_dbeta_fold_kernel, dim3(1), dim3(256), 0, s, part, (int)(grid.x * grid.y), beta_dev, dbeta);
+        DWN_CHECK_LAUNCH();
+        return 0;
+    }
     DISPATCH_T(dtype,
         hipLaunchKernelGGL((readout_dz_kernel<bf16_t>), grid, dim3(256), lds, s, dout, out, beta, Tn, n_valid, Rg, Rp, groups, (bf16_t*)dz, db),
         hipLaunchKernelGGL((readout_dz_kernel<float>), grid, dim3(256), lds, s, dout, out, beta, Tn, n_valid, Rg, Rp, groups, (float*)dz, db));

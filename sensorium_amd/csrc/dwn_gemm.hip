@@ -107,6 +107,7 @@ __device__ __forceinline__ void x3_store(unsigned char* rowp, int row, int kc, c
 template <typename T, int ALD, int EPI, int BN, int SINGLE, bool SPLIT = false>
 __global__ __launch_bounds__(256, 2) void gemm_nn_kernel(const GemmNN g) {
     constexpr int KC = TT<T>::KC;
+    constexpr bool RO = EPI == EPI_READOUT || EPI == EPI_READOUT_LB;     // the readout epilogue, beta as an argument or in device memory
     constexpr int BM = 128;
     constexpr int ROWB = 128;                          // bytes per tile row per k-step
     constexpr int BK = ROWB / (int)sizeof(T);          // 64 bf16 / 32 f32
@@ -512,9 +513,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nn_kernel(const GemmNN g) {
             }
         }
 
-        if constexpr (EPI == EPI_READOUT) {
+        if constexpr (RO) {
             // out[b][n][t] = softplus_beta(acc + bias[n]); lanes lr = 16 consecutive rows m = b*Tn + t
-            const float beta = g.sp_beta;
+            // (EPI_READOUT_LB: beta from device memory — a kernel-argument pointer, so one scalar load for the workgroup)
+            const float beta = EPI == EPI_READOUT_LB ? *g.sp_beta_dev : g.sp_beta;
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
 #pragma unroll
@@ -707,7 +709,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nn_kernel(const GemmNN g) {
             }
         }
         if constexpr (single && HN) {
-            if constexpr (EPI == EPI_READOUT) __syncthreads();   // no barrier in that epilogue: all waves must be done with sA
+            if constexpr (RO) __syncthreads();   // no barrier in that epilogue: all waves must be done with sA
             store_a();
             __syncthreads();
         }
@@ -721,7 +723,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nn_kernel(const GemmNN g) {
         const int m0_ = mt * BM;
         bool fast = m0_ + BM <= g.M;
         if constexpr (EPI == EPI_DG || EPI == EPI_DH3) fast = fast && (m0_ / g.rows_per_sample == (m0_ + BM - 1) / g.rows_per_sample);
-        if constexpr (EPI == EPI_READOUT) fast = false;
+        if constexpr (RO) fast = false;
         using T_ = std::true_type;
         using F_ = std::false_type;
         if constexpr (single) {
@@ -733,7 +735,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nn_kernel(const GemmNN g) {
             tile(mt, F_{}, F_{});       // k-loop variant: its prefetches live inside the k loop; one generic copy
         }
     }
-    if constexpr (EPI != EPI_READOUT) {
+    if constexpr (!RO) {
         if (g.stats) {
             if constexpr (EPI == EPI_DH3) {            // sum(dh*(y - mean)*invstd) = invstd * (sum(dh*y) - mean*sum(dh))
                 float mu3[KC], is3[KC];
@@ -835,7 +837,7 @@ static int launch_nn_t(const GemmNN& g, hipStream_t s) {
         if (g.K <= 2 * BK && !g.b_sample_stride)
             return n64 ? launch_nn_k<T, ALD, EPI, 64, 2>(g, s) : launch_nn_k<T, ALD, EPI, 128, 2>(g, s);
     }
-    if constexpr (ALD == LD_PLAIN && TT<T>::IS_BF16) {
+    if constexpr (ALD == LD_PLAIN && TT<T>::IS_BF16 && EPI != EPI_READOUT_LB) {   // (nn_use_dma: never for a readout epilogue)
         if (nn_use_dma(g, n64 ? 64 : 128))
             return n64 ? launch_nn_k<T, ALD, EPI, 64, 3>(g, s) : launch_nn_k<T, ALD, EPI, 128, 3>(g, s);
     }
@@ -845,6 +847,10 @@ static int launch_nn_t(const GemmNN& g, hipStream_t s) {
 template <typename T>
 static int launch_nn_d(const GemmNN& g, hipStream_t s) {
     if (g.K % TT<T>::KC != 0) return dwn_set_error(-2, "gemm_nn: K must be a multiple of the 16-byte vector");
+    if (g.epi == EPI_READOUT && g.sp_beta_dev) {       // learnable beta: instantiations of their own, the fixed ones untouched
+        if (g.a_kind == LD_PLAIN) return launch_nn_t<T, LD_PLAIN, EPI_READOUT_LB>(g, s);
+        return dwn_set_error(-3, "gemm_nn: the readout epilogue with sp_beta_dev needs a plain loader");
+    }
     if (g.epi == EPI_READOUT) {
         if (g.a_kind == LD_BNACT) return launch_nn_t<T, LD_BNACT, EPI_READOUT>(g, s);
         if (g.a_kind == LD_PLAIN) return launch_nn_t<T, LD_PLAIN, EPI_READOUT>(g, s);

@@ -222,12 +222,47 @@ class Cortex(nn.Module):
         return x
 
 
+class SoftplusGate(nn.Module):
+    """Holder of one readout's learnable Softplus ``beta``: a single 0-d parameter, initialised from ``softplus_beta``.
+
+    ``param="beta"``: the parameter ``beta`` IS the Softplus beta.  Nothing keeps it positive: ``beta <= 0`` is outside the contract
+    (the readout then returns NaN / Inf — not a fault).  ``param="log"``: the parameter is ``log_beta = log(beta)`` and ``value()``
+    hands ``log_beta.exp()`` to the kernels, so beta stays positive and its gradient is ``beta`` times the other form's — the
+    recommended form when the optimizer clips the gradient norm."""
+
+    def __init__(self, softplus_beta: float, param: str = "beta"):
+        super().__init__()
+        if param not in ("beta", "log"):
+            raise ValueError("softplus_param: 'beta' or 'log'")
+        if not float(softplus_beta) > 0.0:
+            raise ValueError("a learnable Softplus beta must start positive")
+        self.param = param
+        if param == "beta":
+            self.beta = nn.Parameter(torch.tensor(float(softplus_beta), dtype=torch.float32))
+        else:
+            self.log_beta = nn.Parameter(torch.tensor(math.log(float(softplus_beta)), dtype=torch.float32))
+
+    def value(self) -> torch.Tensor:
+        """The current beta: a 0-d fp32 tensor on the parameter's device, differentiable w.r.t. the parameter."""
+        return self.beta if self.param == "beta" else self.log_beta.float().exp()
+
+    def extra_repr(self) -> str:
+        return f"param={self.param!r}"
+
+
 class Readout(nn.Module):
-    """Per-mouse readout (reference: dwiseneuro.py:266-287) executed by ``ops.ReadoutFn``."""
+    """Per-mouse readout (reference: dwiseneuro.py:266-287) executed by ``ops.ReadoutFn``.
+
+    ``learnable_softplus=True``: ``gate`` is a ``SoftplusGate`` instead of ``nn.Softplus`` and the kernels read beta from its
+    device memory, forward (also inside a captured graph) and backward; ``softplus_beta`` stays the construction value and
+    ``beta()`` returns the current one."""
 
     def __init__(self, in_features: int, out_features: int, groups: int = 1, softplus_beta: float = 1.0,
-                 drop_rate: float = 0.0):
+                 drop_rate: float = 0.0, learnable_softplus: bool = False, softplus_param: str = "beta"):
         super().__init__()
+        if softplus_param not in ("beta", "log"):           # checked with the feature off too: a typo must not pass silently
+            raise ValueError("softplus_param: 'beta' or 'log'")
+        self.learnable_softplus = bool(learnable_softplus)
         self.in_features = in_features
         self.out_features = out_features
         self.groups = groups
@@ -236,7 +271,13 @@ class Readout(nn.Module):
         padded = int(math.ceil(out_features / groups) * groups)
         self.layer = nn.Sequential(nn.Dropout1d(p=drop_rate),
                                    nn.Conv1d(in_features, padded, (1,), groups=groups, bias=True))
-        self.gate = nn.Softplus(beta=softplus_beta)
+        self.gate = SoftplusGate(softplus_beta, softplus_param) if self.learnable_softplus else nn.Softplus(beta=softplus_beta)
+
+    def beta(self) -> torch.Tensor:
+        """The Softplus beta in use, as a 0-d fp32 tensor on the readout's device (no host read-back)."""
+        if self.learnable_softplus:
+            return self.gate.value().detach()
+        return torch.tensor(self.softplus_beta, dtype=torch.float32, device=self.layer[1].weight.device)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         mask = None
@@ -245,6 +286,8 @@ class Readout(nn.Module):
             mask = torch.empty(x.shape[0], x.shape[2], dtype=torch.float32, device=x.device).bernoulli_(keep)
             mask.div_(keep)
         conv = self.layer[1]
+        if self.learnable_softplus:
+            return ops.ReadoutFn.apply(x, mask, self, conv.weight, conv.bias, self.gate.value())
         return ops.ReadoutFn.apply(x, mask, self, conv.weight, conv.bias)
 
 
@@ -310,7 +353,12 @@ class DwiseNeuro(nn.Module):
                  softplus_beta: float = 0.07,
                  drop_rate: float = 0.4,
                  drop_path_rate: float = 0.1,
-                 compute_dtype: Optional[torch.dtype] = None):
+                 compute_dtype: Optional[torch.dtype] = None,
+                 learnable_softplus: bool = False,
+                 softplus_param: str = "beta"):
+        """``learnable_softplus``: every readout trains a Softplus beta of its own, starting from ``softplus_beta``
+        (``readouts.<k>.gate.beta``, or ``readouts.<k>.gate.log_beta`` with ``softplus_param="log"``; see ``SoftplusGate``).
+        Off (the default), the module tree and the state_dict are the reference's."""
         super().__init__()
         self.compute_dtype = compute_dtype
         self.fp32_eval_products = "bf16x3"     # see set_fp32_eval_products
@@ -325,7 +373,12 @@ class DwiseNeuro(nn.Module):
         self.readouts = nn.ModuleList()
         for n in readout_outputs:
             self.readouts.append(Readout(in_features=cortex_features[-1], out_features=n, groups=groups,
-                                         softplus_beta=softplus_beta, drop_rate=drop_rate))
+                                         softplus_beta=softplus_beta, drop_rate=drop_rate,
+                                         learnable_softplus=learnable_softplus, softplus_param=softplus_param))
+
+    def softplus_parameters(self):
+        """The readouts' learnable Softplus parameters (empty unless ``learnable_softplus``): they take no weight decay."""
+        return [p for r in self.readouts if r.learnable_softplus for p in r.gate.parameters()]
 
     def set_fp32_eval_products(self, mode: str = "bf16x3") -> "DwiseNeuro":
         """How the fp32 path multiplies in the EVAL-mode forward (val_step / predict run fp32, src/argus_models.py:73-99).

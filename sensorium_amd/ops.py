@@ -521,25 +521,34 @@ class CortexFn(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------
 class ReadoutFn(torch.autograd.Function):
     """Readout.forward (dwiseneuro.py:283-287): Dropout1d -> grouped Conv1d(k=1)+bias -> [:N] -> Softplus(beta).
-    x: [B,T,C] (compute dtype) -> [B,N,T] fp32."""
+    x: [B,T,C] (compute dtype) -> [B,N,T] fp32.
+    ``beta``: ``None`` (the module's fixed ``softplus_beta``) or a 0-d fp32 tensor on x's device, > 0: the kernels read it from
+    device memory and backward returns its gradient (a float64 reduction fused into the dz pass)."""
 
     @staticmethod
-    def forward(ctx, x, drop_mask, mod, weight, bias):
+    def forward(ctx, x, drop_mask, mod, weight, bias, beta=None):
         _require_gpu(x, "ReadoutFn")
         x = x.contiguous()
         dev = x.device
+        beta_in = beta
+        if beta is not None:
+            if beta.dim() != 0 or beta.dtype != torch.float32 or beta.device != dev:
+                raise RuntimeError("ReadoutFn: beta must be a 0-d fp32 tensor on the input's device")
+            beta = beta.detach()
         B, T, Cin = x.shape
         n = mod.out_features
         out = torch.empty(B, n, T, dtype=torch.float32, device=dev)
         a = L.ReadoutArgs()
         a.dtype = _DT[x.dtype]; a.B = B; a.T = T; a.Cin = Cin; a.groups = mod.groups; a.n_out = n
-        a.softplus_beta = mod.softplus_beta
+        a.softplus_beta = mod.softplus_beta; a.beta_dev = _ptr(beta)
         a.x = x.data_ptr(); a.w = weight.data_ptr(); a.bias = bias.data_ptr(); a.drop_mask = _ptr(drop_mask)
         a.out = out.data_ptr()
         # eval-mode forward (the module is not training; a no_grad forward of a training module keeps the training numerics)
         a.f32_products = _f32_products(mod, inference_readout=True) if not mod.training else L.F32_NATIVE
         # a backward will follow: the pack pass also writes the weight in the data gradient's layout and backward reuses it
         # (the optimizer only touches the weight after backward)
+        # (beta counts: with only the gate trainable the backward still forms dx and dW — as it always has for a frozen weight —
+        # since dz, which dbeta rides on, is one pass with them; a dbeta-only backward is not built, DESIGN.md 12g)
         wt = None
         if any(ctx.needs_input_grad):
             wt = torch.empty(L.lib.dwn_readout_wt_bytes(C.byref(a)), dtype=torch.uint8, device=dev)
@@ -555,6 +564,11 @@ class ReadoutFn(torch.autograd.Function):
         tensors = [x, weight, bias, out]
         if drop_mask is not None:
             tensors.append(drop_mask)
+        ctx.has_beta = beta is not None
+        # the gate parameter itself (the "beta" form): its gradient is written straight into its all-reduce slot, like dw / db
+        ctx.beta_param = beta_in if isinstance(beta_in, torch.nn.Parameter) else None
+        if beta is not None:
+            tensors.append(beta)
         ctx.save_for_backward(*tensors)
         return out
 
@@ -564,6 +578,7 @@ class ReadoutFn(torch.autograd.Function):
         t = ctx.saved_tensors
         x, weight, bias, out = t[:4]
         drop_mask = t[4] if ctx.has_mask else None
+        beta = t[-1] if ctx.has_beta else None
         dev = x.device
         dout = dout.contiguous().float()
         B, T, Cin = x.shape
@@ -571,13 +586,16 @@ class ReadoutFn(torch.autograd.Function):
         conv = mod.layer[1]
         dw = grad_out(conv.weight)                   # overwritten by dwn_readout_backward (no 64 MB clear per readout)
         db = grad_out(conv.bias, zero=True)
+        dbeta = None
+        if beta is not None:                         # overwritten by dwn_readout_backward
+            dbeta = grad_out(ctx.beta_param) if ctx.beta_param is not None else torch.empty((), dtype=torch.float32, device=dev)
         idx, dx_full = ctx.active, None
         if idx is not None and idx.numel() < B:
             # compact backward: the three products see nb x T rows instead of B x T (ten readouts with one-hot mouse
             # weights: 3-4 of 32 samples each); zero rows contribute exactly nothing to dW / dbias and get dx = 0
             dx_full = torch.zeros_like(x)
             if idx.numel() == 0:
-                return dx_full, None, None, dw.zero_(), db
+                return dx_full, None, None, dw.zero_(), db, (None if dbeta is None else dbeta.zero_())
             x, out, dout = x.index_select(0, idx), out.index_select(0, idx), dout.index_select(0, idx)
             if drop_mask is not None:
                 drop_mask = drop_mask.index_select(0, idx)
@@ -585,7 +603,7 @@ class ReadoutFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         a = L.ReadoutArgs()
         a.dtype = _DT[x.dtype]; a.B = B; a.T = T; a.Cin = Cin; a.groups = mod.groups; a.n_out = n
-        a.softplus_beta = mod.softplus_beta
+        a.softplus_beta = mod.softplus_beta; a.beta_dev = _ptr(beta); a.dbeta = _ptr(dbeta)
         a.x = x.data_ptr(); a.w = weight.data_ptr(); a.bias = bias.data_ptr(); a.drop_mask = _ptr(drop_mask)
         a.out = out.data_ptr(); a.dout = dout.data_ptr(); a.dx = dx.data_ptr(); a.dw = dw.data_ptr()
         a.dbias = db.data_ptr()
@@ -597,7 +615,7 @@ class ReadoutFn(torch.autograd.Function):
         if dx_full is not None:
             dx_full.index_copy_(0, idx, dx)
             dx = dx_full
-        return dx, None, None, dw, db
+        return dx, None, None, dw, db, dbeta
 
 
 # ------------------------------------------------------------------------------------------------
