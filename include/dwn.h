@@ -605,6 +605,41 @@ int dwn_assemble_inputs(const dwn_clip_desc* descs, int B, int T, int H0, int W0
 int dwn_assemble_targets(const dwn_clip_desc* descs, int B, int T, float* const* targets, const int* n_neurons,
                          int n_mice, int max_neurons, float* mice_weights, int device, void* stream);
 
+/* ---- gaze shifter: a per-frame translation of ONE channel of the model input, resampled bilinearly.
+ * x, out, dout, dx: [B][Cin][T][H][W] fp32 contiguous; shift, dshift: [B][T][2] fp32, (dy, dx) in pixels.  Channel
+ * `video_channel` is resampled, every other channel is copied (forward) / passes dout through (backward).  With the plane
+ * extended by the constant `fill` outside [0,H) x [0,W), iy = floor(dy), fy = dy - iy (fp32), likewise ix, fx:
+ *   out[y][x] = (1-fy)(1-fx) v(y+iy, x+ix)   + (1-fy) fx v(y+iy, x+ix+1)
+ *             +    fy (1-fx) v(y+iy+1, x+ix) +    fy  fx v(y+iy+1, x+ix+1)
+ * (= grid_sample bilinear, zeros padding, align_corners=True for fill = 0).  A shift of exactly 0 copies the plane bit for bit.
+ * A tap whose weight is 0 contributes nothing whatever it holds (Inf, NaN, a non-finite fill); a tap of weight 1 gives its bits.
+ * Any finite shift is legal (beyond the frame: out = fill, dx = dshift = 0; the float -> int conversion is clamped); a NaN / Inf
+ * shift gives a frame of NaN in out (backward: dx = 0 and dshift = NaN for that frame).  No access leaves the tensors.
+ * Backward: dx = the adjoint gather sum_{a,b} w_a w_b dout[y-iy-a][x-ix-b] (out-of-frame terms dropped), dshift[b][t] =
+ * sum_{y,x} dout * d out / d (dy, dx) with iy, ix held constant (the right derivative at integer shifts), accumulated in float64
+ * by one workgroup per frame in a fixed order.  No atomics anywhere: the same inputs give the same bits, in both builds.
+ * dwn_gaze_shift_forward needs x, shift, out.  dwn_gaze_shift_backward needs shift, dout and at least one of dx, dshift (a null
+ * one is skipped; both null: -1); dshift also needs x.  Argument errors (null pointer -1, geometry -2) are answered before the
+ * device is entered. */
+typedef struct dwn_gaze_args {
+    int B, Cin, T, H, W;
+    int video_channel;
+    float fill;
+    int pad_;
+    const float* x;
+    const float* shift;
+    float* out;
+    const float* dout;
+    float* dx;
+    float* dshift;
+} dwn_gaze_args;
+int dwn_gaze_shift_forward(const dwn_gaze_args* a, int device, void* stream);
+int dwn_gaze_shift_backward(const dwn_gaze_args* a, int device, void* stream);
+/* mean[b][t][k] = mean over H x W of channel c0 + k of x [B][Cin][T][H][W] fp32, k in [0, nc): float64 accumulation in a fixed
+ * order (one workgroup per plane, no atomics), so a constant plane returns its constant bit for bit (-0.0 included).  Null
+ * pointer -1; non-positive size, or [c0, c0 + nc) outside [0, Cin): -2 — before the device is entered. */
+int dwn_plane_mean(const float* x, int B, int Cin, int T, int H, int W, int c0, int nc, float* mean, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

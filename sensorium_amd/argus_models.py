@@ -29,6 +29,7 @@ from .ema import ModelEma
 from .engine import Model
 from .losses import MicePoissonLoss
 from .optim import FusedAdamWEma
+from .shifter import DwiseNeuroGaze
 
 
 def deep_to(obj, device, non_blocking: bool = False):
@@ -77,7 +78,7 @@ def fill_distill_targets(distill_prediction, target, distill_ratio: float):
 class MouseModel(Model):
     """``fit`` / ``validate`` / ``save`` come from ``engine.Model`` (the argus surface train.py:141-145 uses);
     ``load_model`` finds this class by the ``model_name`` stored in the checkpoint."""
-    nn_module = {"dwiseneuro": DwiseNeuro}
+    nn_module = {"dwiseneuro": DwiseNeuro, "dwiseneuro_gaze": DwiseNeuroGaze}
     loss = {"mice_poisson": MicePoissonLoss}
     optimizer = {"AdamW": FusedAdamWEma}
 

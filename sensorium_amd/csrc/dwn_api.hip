@@ -307,7 +307,7 @@ int dwn_sizeof(const char* name) {
     SZ(dwn_dw_spatial_bwd_args); SZ(dwn_dw_temporal_fwd_args); SZ(dwn_dw_temporal_bwd_args); SZ(dwn_bn);
     SZ(dwn_stem_args); SZ(dwn_block_args); SZ(dwn_pool_args); SZ(dwn_cortex_args); SZ(dwn_readout_args);
     SZ(dwn_tensor_entry); SZ(dwn_clip_src); SZ(dwn_clip_desc); SZ(dwn_pw_bwd_args); SZ(dwn_dw_spatial_rc_fwd_args);
-    SZ(dwn_stem_input_grad_args); SZ(dwn_guarded_entry); SZ(dwn_step_guard);
+    SZ(dwn_stem_input_grad_args); SZ(dwn_guarded_entry); SZ(dwn_step_guard); SZ(dwn_gaze_args);
 #undef SZ
     return -1;
 }
@@ -1177,6 +1177,43 @@ int dwn_assemble_targets(const dwn_clip_desc* descs, int B, int T, float* const*
         return dwn_set_error(-2, "assemble_targets: B, T, n_mice, max_neurons must be positive");
     if (B > 65535 || n_mice > 65535) return dwn_set_error(-2, "assemble_targets: B and n_mice are grid dimensions (<= 65535)");
     return k_assemble_targets(descs, B, T, targets, n_neurons, n_mice, max_neurons, mice_weights, (hipStream_t)stream);
+}
+
+// ---- gaze shifter: the argument checks need no device
+static int gaze_geometry(const dwn_gaze_args* a) {
+    if (a->B <= 0 || a->Cin <= 0 || a->T <= 0 || a->H <= 0 || a->W <= 0) return dwn_set_error(-2, "gaze_shift: B, Cin, T, H, W must be positive");
+    if (a->video_channel < 0 || a->video_channel >= a->Cin) return dwn_set_error(-2, "gaze_shift: video_channel outside [0, Cin)");
+    if ((long long)a->H * a->W > (1ll << 30) || (long long)a->B * a->Cin * a->T >= (1ll << 31))
+        return dwn_set_error(-2, "gaze_shift: more than 2^30 pixels per plane or 2^31 planes");
+    return 0;
+}
+int dwn_gaze_shift_forward(const dwn_gaze_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "gaze_shift_forward: null arguments");
+    TRY(gaze_geometry(a));
+    if (!a->x || !a->shift || !a->out) return dwn_set_error(-1, "gaze_shift_forward: null pointer (x, shift, out)");
+    ENTER(device);
+    return k_gaze_forward(*a, (hipStream_t)stream);
+}
+int dwn_gaze_shift_backward(const dwn_gaze_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "gaze_shift_backward: null arguments");
+    TRY(gaze_geometry(a));
+    if (!a->dx && !a->dshift) return dwn_set_error(-1, "gaze_shift_backward: dx and dshift are both null");
+    if (!a->shift || !a->dout) return dwn_set_error(-1, "gaze_shift_backward: null pointer (shift, dout)");
+    if (a->dshift && !a->x) return dwn_set_error(-1, "gaze_shift_backward: dshift needs x");
+    ENTER(device);
+    return k_gaze_backward(*a, (hipStream_t)stream);
+}
+int dwn_plane_mean(const float* x, int B, int Cin, int T, int H, int W, int c0, int nc, float* mean, int device, void* stream) {
+    g_err[0] = 0;
+    if (!x || !mean) return dwn_set_error(-1, "plane_mean: null pointer (x, mean)");
+    if (B <= 0 || Cin <= 0 || T <= 0 || H <= 0 || W <= 0) return dwn_set_error(-2, "plane_mean: B, Cin, T, H, W must be positive");
+    if (nc <= 0 || c0 < 0 || c0 >= Cin || nc > Cin - c0) return dwn_set_error(-2, "plane_mean: channels [c0, c0 + nc) outside [0, Cin)");
+    if ((long long)H * W > (1ll << 30) || (long long)B * Cin * T >= (1ll << 31))
+        return dwn_set_error(-2, "plane_mean: more than 2^30 pixels per plane or 2^31 planes");
+    ENTER(device);
+    return k_plane_mean(x, B, Cin, T, H, W, c0, nc, mean, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -113,6 +113,10 @@ int k_assemble_inputs(const dwn_clip_desc* descs, int B, int T, int H0, int W0, 
 int k_assemble_targets(const dwn_clip_desc* descs, int B, int T, float* const* targets, const int* n_neurons,
                        int n_mice, int max_neurons, float* mice_weights, hipStream_t s);
 int k_zero(void* p, size_t nbytes, hipStream_t s);
+// gaze shifter (dwn.h dwn_gaze_args; dwn_gaze.hip): arguments checked by the C-ABI layer
+int k_gaze_forward(const dwn_gaze_args& a, hipStream_t s);
+int k_gaze_backward(const dwn_gaze_args& a, hipStream_t s);      // a.dx and / or a.dshift
+int k_plane_mean(const float* x, int B, int Cin, int T, int H, int W, int c0, int nc, float* mean, hipStream_t s);
 int k_pw_bwd_prep(const float* w1, const float* abc, int E, int C, void* bp, float* gacc, float* r3, int dtype,
                   const float* res_abc, int res_C, hipStream_t s);
 // conv_pw weight gradient from the raw products (see pw_bwd_fused_kernel): tacc [(E + C + 8)][C] fp32 = rows T1 = dh1^T a0,

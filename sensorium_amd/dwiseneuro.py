@@ -422,8 +422,10 @@ class DwiseNeuro(nn.Module):
         for m, row in zip(layers, factors.unbind(0)):
             m._pooled = row
 
-    def trunk(self, x: torch.Tensor) -> torch.Tensor:
-        """core -> pool -> cortex; returns channels-last [B, T, C] features in the compute dtype."""
+    def trunk(self, x: torch.Tensor, mode_from: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """core -> pool -> cortex; returns channels-last [B, T, C] features in the compute dtype.
+        ``mode_from``: the tensor the eval-mode BatchNorm decision is taken from when ``x`` is not the caller's input but
+        something computed from it (a learned front end: ``DwiseNeuroGaze``); ``None`` = ``x`` itself."""
         if x.dim() != 5:
             raise RuntimeError("DwiseNeuro expects (batch, channel, time, height, width)")
         if self.training:
@@ -432,7 +434,8 @@ class DwiseNeuro(nn.Module):
         # eval: ONE BatchNorm mode for the whole forward, decided from the model's input (an inner activation requires grad whenever
         # a parameter does): frozen statistics with a backward if the input needs a gradient or freeze_batchnorm() is on, else eval
         mode = None if self.training else (
-            ops.L.BN_FROZEN if ops.wants_frozen(x, getattr(self, "bn_frozen_finetune", False)) else ops.L.BN_EVAL)
+            ops.L.BN_FROZEN if ops.wants_frozen(x if mode_from is None else mode_from,
+                                                getattr(self, "bn_frozen_finetune", False)) else ops.L.BN_EVAL)
         with ops.bn_mode_scope(mode):
             x = self.core(x, dtype)                               # [B,T,h,w,C]
             x = ops.PoolFn.apply(x)                               # [B,T,C]

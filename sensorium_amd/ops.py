@@ -16,6 +16,7 @@ from typing import Optional
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 
@@ -654,3 +655,81 @@ class PoissonLossFn(torch.autograd.Function):
                                                 dpred.data_ptr(), dev.index, _stream(dev)),
                 "dwn_poisson_loss_backward")
         return dpred, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------
+# gaze shifter (sensorium_amd/shifter.py)
+# ------------------------------------------------------------------------------------------------
+def _gaze_args(x_shape, video_channel: int, fill: float) -> L.GazeArgs:
+    a = L.GazeArgs()
+    a.B, a.Cin, a.T, a.H, a.W = (int(n) for n in x_shape)
+    a.video_channel = int(video_channel)
+    a.fill = float(fill)
+    return a
+
+
+class GazeShiftFn(torch.autograd.Function):
+    """Per-frame translation of channel ``video_channel`` of the NCDHW fp32 input by ``shift`` [B][T][2] = (dy, dx) pixels,
+    bilinear, constant ``fill`` outside the frame; every other channel is copied (include/dwn.h dwn_gaze_args).  Gradients
+    w.r.t. the input (an adjoint gather) and w.r.t. the shift (one float64 reduction per frame), both without atomics."""
+
+    @staticmethod
+    def forward(ctx, x, shift, video_channel=0, fill=0.0):
+        _require_gpu(x, "GazeShiftFn")
+        _require_gpu(shift, "GazeShiftFn")
+        if x.dim() != 5 or shift.shape != (x.shape[0], x.shape[2], 2):
+            raise RuntimeError("sensorium_amd.GazeShiftFn: x must be [B][C][T][H][W] and shift [B][T][2]")
+        x = x.contiguous().float()
+        shift = shift.contiguous().float()
+        dev = x.device
+        out = torch.empty_like(x)
+        a = _gaze_args(x.shape, video_channel, fill)
+        a.x = x.data_ptr(); a.shift = shift.data_ptr(); a.out = out.data_ptr()
+        L.check(L.lib.dwn_gaze_shift_forward(C.byref(a), dev.index, _stream(dev)), "dwn_gaze_shift_forward")
+        ctx.geom = (tuple(x.shape), int(video_channel), float(fill))
+        ctx.save_for_backward(x if ctx.needs_input_grad[1] else None, shift)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        x, shift = ctx.saved_tensors
+        shape, video_channel, fill = ctx.geom
+        dev = dout.device
+        dout = dout.contiguous().float()
+        dx = torch.empty(shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        dshift = torch.empty_like(shift) if ctx.needs_input_grad[1] else None
+        if dx is None and dshift is None:
+            return None, None, None, None
+        a = _gaze_args(shape, video_channel, fill)
+        a.x = _ptr(x); a.shift = shift.data_ptr(); a.dout = dout.data_ptr(); a.dx = _ptr(dx); a.dshift = _ptr(dshift)
+        L.check(L.lib.dwn_gaze_shift_backward(C.byref(a), dev.index, _stream(dev)), "dwn_gaze_shift_backward")
+        return dx, dshift, None, None
+
+
+class PlaneMeanFn(torch.autograd.Function):
+    """mean over H x W of channels [c0, c0 + nc) of the NCDHW fp32 input -> [B][T][nc] (dwn_plane_mean: float64 accumulation in a
+    fixed order, a constant plane returns its constant bit for bit).  The backward — a broadcast of dmean / (H W) into the chosen
+    channels — is plain torch: it runs only when the caller's input requires a gradient (attribution)."""
+
+    @staticmethod
+    def forward(ctx, x, c0, nc):
+        _require_gpu(x, "PlaneMeanFn")
+        if x.dim() != 5:
+            raise RuntimeError("sensorium_amd.PlaneMeanFn: x must be [B][C][T][H][W]")
+        x = x.contiguous().float()
+        B, Cin, T, H, W = x.shape
+        dev = x.device
+        mean = torch.empty(B, T, int(nc), dtype=torch.float32, device=dev)
+        L.check(L.lib.dwn_plane_mean(x.data_ptr(), B, Cin, T, H, W, int(c0), int(nc), mean.data_ptr(), dev.index, _stream(dev)),
+                "dwn_plane_mean")
+        ctx.geom = (tuple(x.shape), int(c0), int(nc))
+        return mean
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dmean):
+        shape, c0, nc = ctx.geom
+        dx = torch.zeros(shape, dtype=torch.float32, device=dmean.device)
+        dx[:, c0:c0 + nc] = (dmean.float().permute(0, 2, 1) / float(shape[3] * shape[4]))[..., None, None]
+        return dx, None, None
