@@ -640,6 +640,48 @@ int dwn_gaze_shift_backward(const dwn_gaze_args* a, int device, void* stream);
  * pointer -1; non-positive size, or [c0, c0 + nc) outside [0, Cin): -2 — before the device is entered. */
 int dwn_plane_mean(const float* x, int B, int Cin, int T, int H, int W, int c0, int nc, float* mean, int device, void* stream);
 
+/* ---- correlation objective: per-neuron Pearson correlation of ONE mouse over the (sample, frame) values of the
+ * rows R = {b : w[b * w_stride] != 0}, n = |R| * T, and the loss share * red_j (1 - r_j) with its gradient.
+ * pred, target, dpred: [B][N][T] fp32 contiguous ((B, N) tensors: T = 1).  stat: double [DWN_CORR_STAT_ROWS][N], rows
+ *   0 mean_p   1 mean_t   2 M2p = sum (p - mean_p)^2   3 M2t   4 C = sum (p - mean_p)(t - mean_t)          (dwn_corr_moments)
+ *   5 r = (C/n) / ((sd_p + eps)(sd_t + eps)), sd = sqrt(M2/n)   6 c1 = 1/(n a c)   7 c2 = r/(n sd_p a), 0 where sd_p == 0
+ *                                                    with a = sd_p + eps, c = sd_t + eps            (dwn_corr_loss_finalize)
+ * count: one double, n (0 when the mouse has no row: every row of stat is then 0, the loss term and dpred are exactly 0 — decided
+ * on the device).  Rows with w == 0 are never read (they may hold NaN) and get dpred = 0.
+ * dwn_corr_moments: needs pred, target, w, stat, count.  Means in a first sweep, centred sums in a second sweep of the same
+ *   workgroup, float64 throughout; one workgroup per tile of DWN_CORR_TILE neurons, rows split over the waves and merged in LDS
+ *   in a fixed order.  No atomics: the same inputs give the same bits on every launch and in both builds.
+ * dwn_corr_loss_finalize: needs stat, count, share, loss_acc, ws.  Fills rows 5-7 and adds share * rho * sum_j (1 - r_j) to
+ *   *loss_acc (double, zeroed by the caller before the first mouse; rho = 1/N for DWN_CORR_MEAN, 1 for DWN_CORR_SUM): one partial
+ *   per workgroup into ws, folded by a one-workgroup launch in a fixed order.  ws: dwn_corr_ws_bytes(a) bytes, 8-byte aligned.
+ * dwn_corr_loss_backward: needs pred, target, w, stat, share, dpred (gscale: the incoming gradient, a device scalar; null = 1).
+ *   dpred = -g share rho [c1 (t - mean_t) - c2 (p - mean_p)], evaluated in float64 and rounded once.
+ * share is a DEVICE scalar (fp32).  Nothing is allocated and nothing is read back: every entry can be captured.  Argument errors
+ * (null pointer -1, geometry -2, workspace -3) are answered before the device is entered. */
+#define DWN_CORR_STAT_ROWS 8
+#define DWN_CORR_TILE 16
+enum { DWN_CORR_MEAN = 0, DWN_CORR_SUM = 1 };
+typedef struct dwn_corr_args {
+    int B, N, T;
+    int reduction;            /* DWN_CORR_MEAN / DWN_CORR_SUM */
+    double eps;               /* added to each standard deviation (> 0) */
+    long long w_stride;       /* elements between the weights of consecutive rows (>= 1): a column of mice_weights is passed as is */
+    const float* pred;
+    const float* target;
+    const float* w;
+    double* stat;
+    double* count;
+    const float* share;
+    double* loss_acc;
+    const float* gscale;
+    float* dpred;
+    void* ws; size_t ws_bytes;
+} dwn_corr_args;
+size_t dwn_corr_ws_bytes(const dwn_corr_args* a);
+int dwn_corr_moments(const dwn_corr_args* a, int device, void* stream);
+int dwn_corr_loss_finalize(const dwn_corr_args* a, int device, void* stream);
+int dwn_corr_loss_backward(const dwn_corr_args* a, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ include/dwn.h) and fails loudly if it is missing — there is no PyTorch/CPU fal
 """
 from . import _lib  # noqa: F401  (raises ImportError when the HIP library is absent)
 from .dwiseneuro import DwiseNeuro  # noqa: F401
-from .losses import MicePoissonLoss  # noqa: F401
+from .losses import MiceCorrelationLoss, MicePoissonCorrelationLoss, MicePoissonLoss  # noqa: F401
 from .shifter import DwiseNeuroGaze, GazeShifter  # noqa: F401
 
-__all__ = ["DwiseNeuro", "DwiseNeuroGaze", "GazeShifter", "MicePoissonLoss"]
+__all__ = ["DwiseNeuro", "DwiseNeuroGaze", "GazeShifter", "MicePoissonLoss", "MiceCorrelationLoss", "MicePoissonCorrelationLoss"]

@@ -190,6 +190,14 @@ class GazeArgs(C.Structure):              # gaze shifter (include/dwn.h dwn_gaze
                 ("pad_", c_i), ("x", c_p), ("shift", c_p), ("out", c_p), ("dout", c_p), ("dx", c_p), ("dshift", c_p)]
 
 
+class CorrArgs(C.Structure):              # correlation objective (include/dwn.h dwn_corr_args)
+    _fields_ = [("B", c_i), ("N", c_i), ("T", c_i), ("reduction", c_i), ("eps", c_d), ("w_stride", c_ll), ("pred", c_p),
+                ("target", c_p), ("w", c_p), ("stat", c_p), ("count", c_p), ("share", c_p), ("loss_acc", c_p), ("gscale", c_p),
+                ("dpred", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
+
+
+CORR_STAT_ROWS, CORR_TILE = 8, 16          # DWN_CORR_STAT_ROWS, DWN_CORR_TILE
+CORR_MEAN, CORR_SUM = 0, 1
 MIX_BOX, MIX_BLEND = 0, 1
 VID_U8, VID_F32 = 0, 1
 
@@ -202,6 +210,7 @@ _STRUCTS = {
     "dwn_clip_src": ClipSrc, "dwn_clip_desc": ClipDesc, "dwn_pw_bwd_args": PwBwdArgs,
     "dwn_dw_spatial_rc_fwd_args": DwSpatialRcFwdArgs, "dwn_stem_input_grad_args": StemInputGradArgs,
     "dwn_guarded_entry": GuardedEntry, "dwn_step_guard": StepGuard, "dwn_gaze_args": GazeArgs,
+    "dwn_corr_args": CorrArgs,
 }
 
 # every symbol include/dwn.h declares: (restype, argtypes)
@@ -267,6 +276,10 @@ SYMBOLS = {
     "dwn_gaze_shift_forward": (c_i, [_P(GazeArgs), c_i, c_p]),
     "dwn_gaze_shift_backward": (c_i, [_P(GazeArgs), c_i, c_p]),
     "dwn_plane_mean": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p]),
+    "dwn_corr_ws_bytes": (c_sz, [_P(CorrArgs)]),
+    "dwn_corr_moments": (c_i, [_P(CorrArgs), c_i, c_p]),
+    "dwn_corr_loss_finalize": (c_i, [_P(CorrArgs), c_i, c_p]),
+    "dwn_corr_loss_backward": (c_i, [_P(CorrArgs), c_i, c_p]),
 }
 
 
@@ -276,7 +289,7 @@ class DwnError(RuntimeError):
 
 # csrc/Makefile HASH_SRCS, in its order
 HASH_SRCS = ("dwn_api.hip", "dwn_gemm.hip", "dwn_gemm_xl.hip", "dwn_gemm_kd.hip", "dwn_dwconv.hip", "dwn_dwrc.hip", "dwn_dwbwd.hip", "dwn_dwfwd.hip",
-             "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_common.h", "dwn_internal.h", "dwn_kernels.h", "dwn_launch.h",
+             "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_corr.hip", "dwn_common.h", "dwn_internal.h", "dwn_kernels.h", "dwn_launch.h",
              "../../include/dwn.h")
 
 
@@ -299,8 +312,9 @@ def _load():
         if ab and name in ("dwn_stem_input_grad", "dwn_stem_backward_input", "dwn_grad_guard_workspace_bytes", "dwn_grad_sumsq_multi",
                            "dwn_step_guard_finalize", "dwn_adamw_ema_multi_guarded", "dwn_dw_temporal_wide_fwd",
                            "dwn_dw_temporal_wide_bwd", "dwn_gaze_shift_forward", "dwn_gaze_shift_backward",
-                           "dwn_plane_mean") and not hasattr(lib, name):
-            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter; the plain training step calls none of them)
+                           "dwn_plane_mean", "dwn_corr_ws_bytes", "dwn_corr_moments", "dwn_corr_loss_finalize",
+                           "dwn_corr_loss_backward") and not hasattr(lib, name):
+            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective; the plain training step calls none of them)
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -312,7 +326,7 @@ def _load():
                           f"`make -C {LIB_PATH.parent}` — binaries are not in git, so what runs must be what is committed")
     for cname, struct in _STRUCTS.items():
         n = lib.dwn_sizeof(cname.encode())
-        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args"))):      # (A/B: ABI 7 only appended)
+        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args"))):      # (A/B: ABI 7 only appended)
             raise ImportError(f"struct layout mismatch for {cname}: C {n} bytes vs ctypes {C.sizeof(struct)}")
     return lib
 

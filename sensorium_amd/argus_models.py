@@ -27,7 +27,7 @@ from .ddp import GradBuckets
 from .dwiseneuro import DwiseNeuro
 from .ema import ModelEma
 from .engine import Model
-from .losses import MicePoissonLoss
+from .losses import MiceCorrelationLoss, MicePoissonCorrelationLoss, MicePoissonLoss
 from .optim import FusedAdamWEma
 from .shifter import DwiseNeuroGaze
 
@@ -79,7 +79,8 @@ class MouseModel(Model):
     """``fit`` / ``validate`` / ``save`` come from ``engine.Model`` (the argus surface train.py:141-145 uses);
     ``load_model`` finds this class by the ``model_name`` stored in the checkpoint."""
     nn_module = {"dwiseneuro": DwiseNeuro, "dwiseneuro_gaze": DwiseNeuroGaze}
-    loss = {"mice_poisson": MicePoissonLoss}
+    loss = {"mice_poisson": MicePoissonLoss, "mice_correlation": MiceCorrelationLoss,
+            "mice_poisson_correlation": MicePoissonCorrelationLoss}
     optimizer = {"AdamW": FusedAdamWEma}
 
     def __init__(self, params: dict):

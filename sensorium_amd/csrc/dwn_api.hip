@@ -308,6 +308,7 @@ int dwn_sizeof(const char* name) {
     SZ(dwn_stem_args); SZ(dwn_block_args); SZ(dwn_pool_args); SZ(dwn_cortex_args); SZ(dwn_readout_args);
     SZ(dwn_tensor_entry); SZ(dwn_clip_src); SZ(dwn_clip_desc); SZ(dwn_pw_bwd_args); SZ(dwn_dw_spatial_rc_fwd_args);
     SZ(dwn_stem_input_grad_args); SZ(dwn_guarded_entry); SZ(dwn_step_guard); SZ(dwn_gaze_args);
+    SZ(dwn_corr_args);
 #undef SZ
     return -1;
 }
@@ -1214,6 +1215,42 @@ int dwn_plane_mean(const float* x, int B, int Cin, int T, int H, int W, int c0, 
         return dwn_set_error(-2, "plane_mean: more than 2^30 pixels per plane or 2^31 planes");
     ENTER(device);
     return k_plane_mean(x, B, Cin, T, H, W, c0, nc, mean, (hipStream_t)stream);
+}
+
+// ---- correlation objective: the argument checks need no device
+static int corr_geometry(const dwn_corr_args* a) {
+    if (a->B <= 0 || a->N <= 0 || a->T <= 0) return dwn_set_error(-2, "corr: B, N, T must be positive");
+    if ((long long)a->N * a->T > (1ll << 31) - 4096) return dwn_set_error(-2, "corr: N * T must stay below 2^31 - 4096");
+    if (a->w_stride < 1) return dwn_set_error(-2, "corr: w_stride must be at least 1");
+    if (!(a->eps > 0.0)) return dwn_set_error(-2, "corr: eps must be positive");
+    if (a->reduction != DWN_CORR_MEAN && a->reduction != DWN_CORR_SUM) return dwn_set_error(-2, "corr: reduction must be DWN_CORR_MEAN or DWN_CORR_SUM");
+    return 0;
+}
+size_t dwn_corr_ws_bytes(const dwn_corr_args* a) { return a && a->N > 0 ? k_corr_ws_bytes(a->N) : 0; }
+int dwn_corr_moments(const dwn_corr_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "corr_moments: null arguments");
+    TRY(corr_geometry(a));
+    if (!a->pred || !a->target || !a->w || !a->stat || !a->count) return dwn_set_error(-1, "corr_moments: null pointer (pred, target, w, stat, count)");
+    ENTER(device);
+    return k_corr_moments(*a, (hipStream_t)stream);
+}
+int dwn_corr_loss_finalize(const dwn_corr_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "corr_loss_finalize: null arguments");
+    TRY(corr_geometry(a));
+    if (!a->stat || !a->count || !a->share || !a->loss_acc || !a->ws) return dwn_set_error(-1, "corr_loss_finalize: null pointer (stat, count, share, loss_acc, ws)");
+    if (a->ws_bytes < k_corr_ws_bytes(a->N) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "corr_loss_finalize: workspace smaller than dwn_corr_ws_bytes or not 8-byte aligned");
+    ENTER(device);
+    return k_corr_finalize(*a, (hipStream_t)stream);
+}
+int dwn_corr_loss_backward(const dwn_corr_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "corr_loss_backward: null arguments");
+    TRY(corr_geometry(a));
+    if (!a->pred || !a->target || !a->w || !a->stat || !a->share || !a->dpred) return dwn_set_error(-1, "corr_loss_backward: null pointer (pred, target, w, stat, share, dpred)");
+    ENTER(device);
+    return k_corr_backward(*a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -117,6 +117,11 @@ int k_zero(void* p, size_t nbytes, hipStream_t s);
 int k_gaze_forward(const dwn_gaze_args& a, hipStream_t s);
 int k_gaze_backward(const dwn_gaze_args& a, hipStream_t s);      // a.dx and / or a.dshift
 int k_plane_mean(const float* x, int B, int Cin, int T, int H, int W, int c0, int nc, float* mean, hipStream_t s);
+// correlation objective (dwn.h dwn_corr_args; dwn_corr.hip): arguments checked by the C-ABI layer
+size_t k_corr_ws_bytes(int N);
+int k_corr_moments(const dwn_corr_args& a, hipStream_t s);
+int k_corr_finalize(const dwn_corr_args& a, hipStream_t s);
+int k_corr_backward(const dwn_corr_args& a, hipStream_t s);
 int k_pw_bwd_prep(const float* w1, const float* abc, int E, int C, void* bp, float* gacc, float* r3, int dtype,
                   const float* res_abc, int res_C, hipStream_t s);
 // conv_pw weight gradient from the raw products (see pw_bwd_fused_kernel): tacc [(E + C + 8)][C] fp32 = rows T1 = dh1^T a0,

@@ -20,21 +20,52 @@ class CorrelationMetric(Metric):
     per mouse and batch, O(epoch) memory) and calls ``corr`` on the concatenation at the end; the Pearson coefficient with
     the reference's ``eps`` on each standard deviation is a function of those sums alone:
     ``(E[pt] - E[p]E[t]) / ((std p + eps)(std t + eps))`` — equal to ``corr(..., axis=0)`` up to rounding (checked at 1e-6).
-    Mice without a weighted row in the epoch are left out, as in the reference."""
+    Mice without a weighted row in the epoch are left out, as in the reference.
+
+    ``fused=True``: ``update`` is one ``dwn_corr_moments`` launch per mouse — the batch's CENTRED moments (means,
+    M2p, M2t, C and n, float64) — merged into the running ones with the pairwise (Chan) formulas on N-vectors on the device; an
+    empty batch or an empty running state is handled by a ``where``, not a read-back.  ``compute`` keeps its one read-back per mouse
+    and epoch.  GPU tensors only.  The default computes exactly what it always did."""
     name = "corr"
     better = "max"
     eps = 1e-8
 
-    def __init__(self):
+    def __init__(self, fused: bool = False):
+        self.fused = bool(fused)
         self.reset()
 
     def reset(self):
         self.sums = {}                # mouse index -> [count (0-d), sum_p, sum_t, sum_pp, sum_tt, sum_pt] (float64, on the device)
+        self.moments = {}             # fused: mouse index -> [n (0-d), mean_p, mean_t, M2p, M2t, C] (float64, on the device)
+
+    @staticmethod
+    def merge_moments(a, b):
+        """Pairwise (Chan) merge of two sets [n, mean_p, mean_t, M2p, M2t, C]; either side may be empty (n = 0)."""
+        na, nb = a[0], b[0]
+        n = na + nb
+        fb = torch.where(n > 0, nb / n.clamp_min(1), torch.zeros_like(n))      # nb / n, 0 for two empty sides
+        dp, dt = b[1] - a[1], b[2] - a[2]
+        cross = na * fb                                                        # na nb / n
+        return [n, a[1] + dp * fb, a[2] + dt * fb, a[3] + b[3] + dp * dp * cross, a[4] + b[4] + dt * dt * cross,
+                a[5] + b[5] + dp * dt * cross]
+
+    @torch.no_grad()
+    def _update_fused(self, predictions, targets, mice_weights):
+        from . import ops
+        weights = mice_weights.float()
+        for k, (p, t) in enumerate(zip(predictions, targets)):
+            N = p.shape[1]
+            stat = ops.corr_moments(p, t, weights[..., k])
+            new = [stat[8 * N]] + [stat[i * N:(i + 1) * N] for i in range(5)]
+            old = self.moments.get(k)
+            self.moments[k] = new if old is None else self.merge_moments(old, new)
 
     @torch.no_grad()
     def update(self, step_output: dict):
         predictions = step_output["prediction"]
         targets, mice_weights = step_output["target"]
+        if self.fused:
+            return self._update_fused(predictions, targets, mice_weights)
         for k, (p, t) in enumerate(zip(predictions, targets)):
             rows = (mice_weights[..., k] != 0).to(torch.float64)              # [B]: 1 for this mouse's samples
             p, t = p.to(torch.float64), t.to(torch.float64)
@@ -49,6 +80,12 @@ class CorrelationMetric(Metric):
 
     def compute(self):
         out = {}
+        for k, (n, mp, mt, m2p, m2t, c) in self.moments.items():
+            n = float(n)                                                      # the epoch's one read-back per mouse
+            if n == 0:
+                continue
+            r = (c / n) / (((m2p / n).sqrt() + self.eps) * ((m2t / n).sqrt() + self.eps))
+            out[k] = float(r.mean())
         for k, (n, sp, st, spp, stt, spt) in self.sums.items():
             n = float(n)                                                      # the epoch's one read-back per mouse
             if n == 0:

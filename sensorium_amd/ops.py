@@ -658,6 +658,83 @@ class PoissonLossFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------
+# correlation objective: MiceCorrelationLoss, CorrelationMetric(fused=True)
+# ------------------------------------------------------------------------------------------------
+CORR_REDUCTIONS = {"mean": L.CORR_MEAN, "sum": L.CORR_SUM}
+
+
+def _corr_args(pred, target, w, stat, eps: float = 1e-8, reduction: str = "mean") -> L.CorrArgs:
+    """pred / target (B, N, T) or (B, N) fp32 contiguous, w a (B,) fp32 view of any stride, stat the (8 * N + 1,) float64 buffer:
+    DWN_CORR_STAT_ROWS rows of N and the count n behind them."""
+    a = L.CorrArgs()
+    a.B, a.N = int(pred.shape[0]), int(pred.shape[1])
+    a.T = int(pred.shape[2]) if pred.dim() == 3 else 1
+    a.reduction = CORR_REDUCTIONS[reduction]
+    a.eps = float(eps)
+    a.w_stride = max(int(w.stride(0)), 1)
+    a.pred, a.target, a.w = pred.data_ptr(), target.data_ptr(), w.data_ptr()
+    a.stat = stat.data_ptr()
+    a.count = stat.data_ptr() + 8 * L.CORR_STAT_ROWS * a.N
+    return a
+
+
+def _corr_inputs(pred, target, w, what: str):
+    _require_gpu(pred, what)
+    if pred.dim() not in (2, 3) or pred.shape != target.shape or w.dim() != 1 or w.shape[0] != pred.shape[0]:
+        raise ValueError(f"sensorium_amd.{what}: pred / target (B, N[, T]) of one shape and w (B,), got "
+                         f"{tuple(pred.shape)}, {tuple(target.shape)}, {tuple(w.shape)}")
+    return pred.contiguous().float(), target.contiguous().float(), w.float()
+
+
+def corr_moments(pred, target, w) -> torch.Tensor:
+    """dwn_corr_moments for one mouse: the (8 * N + 1,) float64 buffer whose rows 0-4 are mean_p, mean_t, M2p, M2t, C over the
+    (sample, frame) values of the rows with w != 0 and whose last element is n (rows 5-7 are left to dwn_corr_loss_finalize).
+    One launch, no read-back."""
+    pred, target, w = _corr_inputs(pred, target, w, "corr_moments")
+    dev = pred.device
+    stat = torch.empty(L.CORR_STAT_ROWS * pred.shape[1] + 1, dtype=torch.float64, device=dev)
+    a = _corr_args(pred, target, w, stat)
+    L.check(L.lib.dwn_corr_moments(C.byref(a), dev.index, _stream(dev)), "dwn_corr_moments")
+    return stat
+
+
+class CorrelationLossFn(torch.autograd.Function):
+    """share * red_j (1 - r_j) for one mouse: r_j the Pearson correlation of neuron j over the (sample, frame) values of the rows
+    with w != 0 (the weights' magnitudes enter through ``share`` alone, a 0-d device tensor).  Moments, coefficients and the
+    reduction run in float64 on the device; the value is returned as an fp32 scalar.  A mouse without a row gives exactly 0 and
+    a zero gradient, decided on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, target, w, share, eps, reduction):
+        pred, target, w = _corr_inputs(pred, target, w, "CorrelationLossFn")
+        share = share.float().reshape(())
+        dev = pred.device
+        stat = torch.empty(L.CORR_STAT_ROWS * pred.shape[1] + 1, dtype=torch.float64, device=dev)
+        acc = torch.zeros(1, dtype=torch.float64, device=dev)
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        a = _corr_args(pred, target, w, stat, eps, reduction)
+        L.check(L.lib.dwn_corr_moments(C.byref(a), dev.index, _stream(dev)), "dwn_corr_moments")
+        ws = _ws(L.lib.dwn_corr_ws_bytes(C.byref(a)), dev)
+        a.share, a.loss_acc, a.ws, a.ws_bytes = share.data_ptr(), acc.data_ptr(), ws.data_ptr(), ws.numel()
+        L.check(L.lib.dwn_corr_loss_finalize(C.byref(a), dev.index, _stream(dev)), "dwn_corr_loss_finalize")
+        L.check(L.lib.dwn_f64_to_f32(acc.data_ptr(), out.data_ptr(), 1, dev.index, _stream(dev)), "dwn_f64_to_f32")
+        ctx.eps, ctx.reduction = eps, reduction
+        ctx.save_for_backward(pred, target, w, share, stat)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, target, w, share, stat = ctx.saved_tensors
+        dev = pred.device
+        gscale = gout.contiguous().float()
+        dpred = torch.empty_like(pred)
+        a = _corr_args(pred, target, w, stat, ctx.eps, ctx.reduction)
+        a.share, a.gscale, a.dpred = share.data_ptr(), gscale.data_ptr(), dpred.data_ptr()
+        L.check(L.lib.dwn_corr_loss_backward(C.byref(a), dev.index, _stream(dev)), "dwn_corr_loss_backward")
+        return dpred, None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------
 # gaze shifter (DESIGN.md 12h; sensorium_amd/shifter.py)
 # ------------------------------------------------------------------------------------------------
 def _gaze_args(x_shape, video_channel: int, fill: float) -> L.GazeArgs:
