@@ -148,7 +148,10 @@ typedef struct dwn_gemm_tn_args {
     int M, R, Cc;
     float* dw; long long lddw;
     int groups;
-    int rows_per_split; int nsplit;       /* nsplit <= 0: chosen by the library */
+    int rows_per_split; int nsplit;       /* nsplit <= 0: both chosen by the library.  nsplit > 0 (rows_per_sample == 0): split i
+                                           * takes rows [i*rows_per_split, (i+1)*rows_per_split) cut at M; the splits must cover
+                                           * every row: rows_per_split <= 0 or nsplit * rows_per_split < M is refused with -2
+                                           * before anything is enqueued */
     int R_load;                           /* P columns per group incl. zero padding (>= R; 0 -> R) */
     /* per-sample products: with rows_per_sample > 0 (M % rows_per_sample == 0, groups == 1) the rows of sample b
      * accumulate into dw + b*dw_sample_stride — B separate [R][Cc] matrices P_b = load(P)_b^T load(Q)_b.

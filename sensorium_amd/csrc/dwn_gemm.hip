@@ -1168,6 +1168,11 @@ static int launch_tn_t(const GemmTN& g_in, hipStream_t s) {
             g.rows_per_split = (int)rows;
             g.nsplit = (int)((g.M + rows - 1) / rows);
         }
+    } else {
+        // splits chosen by the caller: they must cover every row (a split past M is an idle workgroup, a row past the last
+        // split would silently be left out of dW)
+        if (g.rows_per_split <= 0 || (i64)g.nsplit * g.rows_per_split < (i64)g.M)
+            return dwn_set_error(-2, "gemm_tn: nsplit > 0 needs rows_per_split > 0 and nsplit * rows_per_split >= M");
     }
     if (g.dw_f64 && (g.overwrite || g.rows_per_sample > 0)) return dwn_set_error(-2, "gemm_tn: dw_f64 excludes overwrite and per-sample mode");
     if (g.overwrite) {
