@@ -610,7 +610,7 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
     } else {
     {
         GemmNN g = nn_base(xin, LD_PLAIN, w.wpw, a.Cin, a.y1, a.Cmid, (int)Min, a.Cmid, a.Cin, 1);
-        g.f32_split = f32_split_of(a.f32_products, !tr);      // eval-mode fp32: bf16 hi/lo products (dwn_gemm.hip NN_F32_X3) unless NATIVE
+        g.f32_split = f32_split_of(a.f32_products, !tr);      // eval-mode fp32: bf16 hi/lo products (dwn_gemm_nn.h NN_F32_X3) unless NATIVE
         g.stats = tr ? w.st1 : nullptr; g.stat_nchan = a.Cmid;
         PROF(DWN_FAM_PW_FWD, launch_gemm_nn(g, dt, s));
     }

@@ -1,4 +1,4 @@
-// "XL" NN GEMM for the shapes where the 128x128 / 4-wave kernel of dwn_gemm.hip is bound by its own load path rather than
+// "XL" NN GEMM for the shapes where the 128x128 / 4-wave kernel of dwn_gemm_nn.h is bound by its own load path rather than
 // by HBM or the matrix cores (round 3): C[M][N] = A[M][K] . B[N][K]^T, bf16 operands, plain loads, store (+ BatchNorm
 // Σ/Σ²) epilogue — conv_pw of the 256-channel blocks (K = 256, N = 1792: src/models/dwiseneuro.py:91), the cortex layers
 // and their data gradients (:207), the readout data gradient (:276 backward).
@@ -19,7 +19,7 @@
 // ~64 KB per ~3 us per CU = the ~25 GB/s per CU LDS-DMA cadence MI355X_MICROARCH.md lists for a streaming fill.  Ablation builds
 // agree (no MFMAs / no stores / no A loads / no B loads: 200 / 187 / 181 / 194 of 243 us).  Fewer fill bytes per FLOP would need
 // a tile that does not fit the LDS; the next lever is keeping the weight operand in registers across k-steps.
-// MFMA operand roles as in dwn_gemm.hip (weights = A operand): acc[i][j][r] = C[m = i*16 + lr][n = j*16 + 4*lg + r].
+// MFMA operand roles as in dwn_gemm_nn.h (weights = A operand): acc[i][j][r] = C[m = i*16 + lr][n = j*16 + 4*lg + r].
 #include "dwn_internal.h"
 #include "dwn_launch.h"
 #include <stdlib.h>

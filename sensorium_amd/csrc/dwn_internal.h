@@ -11,8 +11,10 @@ typedef dwn_dw_spatial_bwd_args DwSpatialBwd;
 typedef dwn_dw_temporal_fwd_args DwTemporalFwd;
 typedef dwn_dw_temporal_bwd_args DwTemporalBwd;
 
+// dwn_gemm.hip: argument checks and the choice among the A-direct, the 256-row and the 128-row family; instantiates no kernel.
+// The 128-row family is gemm_nn_kernel (dwn_gemm_nn.h), compiled in the dwn_gemm_nn_*.hip files
 int launch_gemm_nn(const GemmNN& g, int dtype, hipStream_t s);
-int launch_gemm_tn(const GemmTN& g, int dtype, hipStream_t s);
+int launch_gemm_tn(const GemmTN& g, int dtype, hipStream_t s);      // dwn_gemm_tn.hip
 // 256-row / 8-wave LDS-DMA variant for the load-path-bound shapes (dwn_gemm_xl.hip)
 bool gemm_nn_xl_eligible(const GemmNN& g, int dtype);
 int launch_gemm_nn_xl(const GemmNN& g, hipStream_t s);
@@ -27,6 +29,7 @@ int launch_dw_temporal_bwd(const DwTemporalBwd& a, int dtype, hipStream_t s);
 int dw_temporal_wide_check(int kt, int C, int dy_kind);
 int launch_dw_temporal_wide_fwd(const DwTemporalFwd& a, int dtype, hipStream_t s);
 int launch_dw_temporal_wide_bwd(const DwTemporalBwd& a, int dtype, hipStream_t s);
+// fused conv_pw backward of the 64-channel blocks (dwn_pw_bwd.hip)
 bool pw_bwd_fused_supported(int dtype, long long M, int E, int Cin);
 int launch_pw_bwd_fused(const void* dh1, const void* a0, const void* bp, const float* r3, void* da0, float* tacc,
                         long long M, int E, int Cin, int dtype, const void* res, const float* res_coef, int res_n,

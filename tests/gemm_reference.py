@@ -16,7 +16,7 @@ import torch
 BF16, F32 = torch.bfloat16, torch.float32
 U = {BF16: 2.0 ** -8, F32: 2.0 ** -24}           # unit roundoff of the storage types
 KC = {BF16: 8, F32: 4}                            # elements per 16-byte vector
-BK = {BF16: 64, F32: 32}                          # k-tile of gemm_nn_kernel (dwn_gemm.hip: BK = 128 bytes / sizeof(T))
+BK = {BF16: 64, F32: 32}                          # k-tile of gemm_nn_kernel (dwn_gemm_nn.h: BK = 128 bytes / sizeof(T))
 LD_PLAIN, LD_PE, LD_BNACT, LD_AFFINE2, LD_GATE, LD_CAT1 = 0, 1, 2, 3, 5, 6       # DWN_LD_* of include/dwn.h
 SPLIT_EXTRA = 3 * 2.0 ** -16                      # f32_split: the dropped lo*lo term and the two split residuals
 EXACT_LIMIT = 2.0 ** 24
@@ -157,7 +157,7 @@ def _maxab(A, B):
 
 
 def _split3(A, B):
-    """hi*hi + hi*lo + lo*hi of the bf16 splits, in float32 (f32_split: dwn_gemm.hip x3_store, "small terms first")."""
+    """hi*hi + hi*lo + lo*hi of the bf16 splits, in float32 (f32_split: dwn_gemm_nn.h x3_store, "small terms first")."""
     ah, bh = A.to(BF16).float(), B.to(BF16).float()
     al, bl = (A - ah).to(BF16).float(), (B - bh).to(BF16).float()
     return (ah @ bl.t() + al @ bh.t()) + ah @ bh.t()
@@ -370,10 +370,10 @@ def nn_dispatch(case):
       gemm_nn_xl_eligible  (dwn_gemm_xl.hip)  bf16, plain loader, store epilogue, no per-sample weights; forced by DWN_NN_XL128 /
                                               XL256, else K >= 256, N >= 512, M >= 8192; launch_gemm_nn_xl: 256 columns when forced
                                               or with >= 256 such tiles
-      launch_nn_t          (dwn_gemm.hip)     n64 = N <= 64; HasSingle (plain or PE loader with store, plain with DG): K <= BK ->
+      launch_nn_t          (dwn_gemm_nn.h)    n64 = N <= 64; HasSingle (plain or PE loader with store, plain with DG): K <= BK ->
                                               one resident k-tile; HasSingle2 (plain loader, store / DG): K <= 2 BK and no per-sample
                                               weights -> two; plain bf16: nn_use_dma -> the LDS-DMA ring; else the k-loop
-      nn_use_dma           (dwn_gemm.hip)     K % 64 == 0, K >= 128, K1 % 64 == 0; per-sample weights, or K >= 512 with at most
+      nn_use_dma           (dwn_gemm_nn.h)    K % 64 == 0, K >= 128, K1 % 64 == 0; per-sample weights, or K >= 512 with at most
                                               5 * 256 tiles
     Returns a name such as "t128.single1", "t64.dma", "xl256", "kd"."""
     dt, M, N, K = case["dtype"], case["M"], case["N"], case["K"]

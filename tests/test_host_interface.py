@@ -286,3 +286,19 @@ def test_library_is_built_from_the_sources_in_the_tree():
     hdrs = re.search(r"^HDRS = (.*)$", mk, re.M).group(1).split()
     assert tuple(srcs + hdrs) == L.HASH_SRCS
     assert L.lib.dwn_source_hash().decode() == L.source_hash()
+
+
+def test_every_kernel_is_compiled_in_one_code_object():
+    """A kernel template instantiated in two translation units is compiled twice and lands in two code objects of the library.  The
+    GEMM family is spread over several files that share one header (csrc/dwn_gemm_nn.h: each launch_nn_t combination is declared
+    extern there and instantiated in exactly one dwn_gemm_nn_*.hip); tools/kernel_digest.py finds a symbol that slipped into two."""
+    import importlib.util
+    import sensorium_amd._lib as L
+    spec = importlib.util.spec_from_file_location("kernel_digest", ROOT / "tools" / "kernel_digest.py")
+    kd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kd)
+    if kd.llvm_tool("llvm-objdump") is None or kd.llvm_tool("llvm-readelf") is None:
+        pytest.skip("no llvm-objdump / llvm-readelf")
+    lines, duplicates = kd.digest([L.LIB_PATH])
+    assert any("gemm_nn_kernel<" in ln for ln in lines) and any("gemm_tn_kernel<" in ln for ln in lines)      # the tool saw the kernels
+    assert not duplicates, duplicates

@@ -2,6 +2,7 @@
 # A/B library variants: tools/build_variant.sh NAME "EXTRA_FLAGS" file1.hip [file2.hip ...]
 # recompiles the listed sources of sensorium_amd/csrc with EXTRA_FLAGS into build_ab/NAME/ and links them with the product build's
 # other objects -> build_ab/NAME/libdwiseneuro_hip.so (same ABI; load it with DWN_LIB_PATH for same-box A/B runs).
+# Files to name for a knob: NN_* (dwn_gemm_nn.h) -> every dwn_gemm_nn_*.hip; TN_* -> dwn_gemm_tn.hip.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 NAME=$1; EXTRA=$2; shift 2
