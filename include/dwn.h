@@ -685,6 +685,46 @@ int dwn_corr_moments(const dwn_corr_args* a, int device, void* stream);
 int dwn_corr_loss_finalize(const dwn_corr_args* a, int device, void* stream);
 int dwn_corr_loss_backward(const dwn_corr_args* a, int device, void* stream);
 
+/* ---- in-silico stimuli: a drifting Gabor rendered into ONE channel of the model input, and the reduction of the
+ * input gradient to the Gabor's parameters.  x, out, dout: [B][Cin][T][H][W] fp32 contiguous; params, dparams: [B][8] fp32 in the
+ * order cy, cx, sigma, theta, sf, tf, phase, amplitude (pixels, pixels, pixels, radians, cycles/pixel, cycles/frame, radians, grey
+ * levels).  For a pixel (y, x) of frame t inside the window rectangle (y0, x0, wh, ww) — wh == ww == 0: the whole plane —
+ *   dyp = y - cy, dxp = x - cx, u = dxp cos(theta) + dyp sin(theta), q = sf u - tf t + phase / (2 pi)          (cycles)
+ *   e   = exp(-(dxp^2 + dyp^2) / (2 sigma^2))  (DWN_GABOR_GAUSSIAN)   |   1  (DWN_GABOR_NONE: a full-field grating)
+ *   raw = background + amplitude e cos(2 pi q),   out = clamp ? min(max(raw, lo), hi) : raw
+ * and outside the window the video plane holds `pad`.  Coordinates are those of the plane, not of the window.  The carrier is
+ * evaluated at q - rint(q) (an exact reduction) with a sincospi call.  Channel `video_channel` is rendered, every other channel
+ * is copied from x bit for bit.
+ * dwn_gabor_forward needs x, params, out.  dwn_gabor_backward needs params, dout, dparams, ws and reads only the video channel of
+ * dout: dparams[b][k] = sum_{t, y, x} dout * d out / d p_k, where the gradient passes through the clamp iff lo <= raw <= hi (as
+ * torch.clamp), `raw` recomputed by the device function of the forward.  Per-pixel products in fp32, sums in float64: one partial
+ * per (clip, frame, chunk of 1024 window pixels) into ws (dwn_gabor_workspace_bytes(a) bytes, 8-byte aligned), folded per clip in
+ * a fixed order.  No atomics; the grids depend on the geometry alone: the same inputs give the same bits, in both builds.  With
+ * DWN_GABOR_NONE dsigma is exactly 0.
+ * A clip with a non-finite parameter, or with sigma <= 0 under the Gaussian envelope, renders NaN inside its window and gets NaN in
+ * all eight dparams; other clips are untouched.  No parameter is converted to an integer or enters an address.
+ * Nothing is allocated and nothing is read back: both entries can be captured.  Argument errors are answered before the device is
+ * entered: null pointer -1; geometry -2 (a non-positive size, video_channel outside [0, Cin), a window not inside the plane,
+ * clamp with lo > hi or a NaN bound, an unknown envelope); workspace too small or misaligned -3. */
+enum { DWN_GABOR_GAUSSIAN = 0, DWN_GABOR_NONE = 1 };
+typedef struct dwn_gabor_args {
+    int B, Cin, T, H, W;
+    int video_channel;
+    int envelope;             /* DWN_GABOR_GAUSSIAN / DWN_GABOR_NONE */
+    int clamp;                /* 0: out = raw; 1: out = raw clamped to [lo, hi] */
+    int y0, x0, wh, ww;       /* the window; wh == ww == 0 (then y0 == x0 == 0): the whole plane */
+    float background, lo, hi, pad;
+    const float* x;
+    const float* params;
+    float* out;
+    const float* dout;
+    float* dparams;
+    void* ws; size_t ws_bytes;
+} dwn_gabor_args;
+size_t dwn_gabor_workspace_bytes(const dwn_gabor_args* a);       /* 0 for arguments the entries would refuse */
+int dwn_gabor_forward(const dwn_gabor_args* a, int device, void* stream);
+int dwn_gabor_backward(const dwn_gabor_args* a, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,3 +121,154 @@ def most_exciting_input(model, mouse_index: int, neurons: Index, *, shape: Tuple
         with torch.enable_grad():       # (input requiring grad: the last entry comes from the same kernels as the others)
             trace[steps] = _response(model, x.detach().requires_grad_(True), mouse_index, nsel, fsel, "sum").detach()
     return (x[0] if squeeze else x), trace
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# parametric stimuli (sensorium_amd/stimuli.py)
+# ------------------------------------------------------------------------------------------------------------------------------
+def _split_base(base: dict):
+    """A ``base`` dict -> (Gabor parameters, DriftingGabor geometry)."""
+    from .stimuli import PARAM_NAMES
+    base = dict(base)
+    values = {k: base.pop(k) for k in list(base) if k in PARAM_NAMES}
+    for k in ("batch", "learn", "init"):
+        if k in base:
+            raise ValueError(f"base: {k!r} is set by the experiment, not by the caller")
+    if "frames" not in base:
+        raise ValueError("base: 'frames' (the length of the clips) is required")
+    return values, base
+
+
+def tuning_curve(model, mouse_index: int, base: dict, sweep: dict, *, neurons: Index = None, frames: Index = None,
+                 chunk: Optional[int] = None) -> torch.Tensor:
+    """Responses to ``K`` drifting Gabors that differ in one parameter: a tuning curve per neuron.
+
+    ``base`` holds the fixed Gabor parameters by name (``stimuli.PARAM_NAMES``; names left out take the defaults of
+    ``DriftingGabor``) together with the geometry of ``DriftingGabor``: ``frames`` (required), ``size``, ``envelope``,
+    ``background``, ``video_range``, ``window``, ``pad``, ``behavior``, ``pupil_center``, ``in_channels``, ``video_channel``.
+    ``sweep`` is ``{name: K values}``.  The clips are rendered on the model's device ``chunk`` at a time (default: all ``K`` in
+    one batch) and run through the eval-mode model without grad (restored afterwards).  Returns [K, N_sel] on the device: the
+    mean predicted response of the chosen ``neurons`` over the chosen ``frames`` (indices into the clip; default all)."""
+    from .stimuli import PARAM_NAMES, DriftingGabor
+    if len(sweep) != 1:
+        raise ValueError("sweep: exactly one parameter name")
+    (name, values), = sweep.items()
+    if name not in PARAM_NAMES:
+        raise ValueError(f"sweep: unknown Gabor parameter {name!r}: the names are {PARAM_NAMES}")
+    values = torch.as_tensor(values, dtype=torch.float32).flatten()
+    K = int(values.numel())
+    if K < 1:
+        raise ValueError("sweep: at least one value")
+    fixed, geometry = _split_base(base)
+    for k, v in fixed.items():
+        if torch.as_tensor(v).dim() != 0:
+            raise ValueError(f"base[{k!r}]: a scalar")
+    chunk = K if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be positive")
+    device = next(model.parameters()).device
+    nsel, fsel = _as_index(neurons, device), _as_index(frames, device)
+    rows = []
+    with _eval_mode(model), torch.no_grad():
+        for k0 in range(0, K, chunk):
+            vals = values[k0:k0 + chunk]
+            clips = DriftingGabor(int(vals.numel()), init={**fixed, name: vals}, **geometry).to(device)
+            out = model(clips(), index=mouse_index)
+            rows.append(out[:, nsel][:, :, fsel].float().mean(dim=2))
+    return torch.cat(rows, dim=0)
+
+
+DEFAULT_GABOR_SCALES = dict(cy=2.0, cx=2.0, sigma=1.0, theta=0.2, sf=0.01, tf=0.01, phase=0.3, amplitude=10.0)
+
+
+def gabor_bounds(gabor, bounds: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(lower, upper) [8] of the projection of ``optimal_gabor`` for the geometry of ``gabor``: the centre inside the window,
+    sigma >= ``sigma_min`` (1), 0 <= sf <= ``sf_max`` (0.5, Nyquist), 0 <= amplitude <= ``amplitude_max`` (half the video range;
+    unbounded without one); theta, tf and phase are free."""
+    from .stimuli import PARAM_NAMES
+    b = dict(sigma_min=1.0, sf_max=0.5, amplitude_max=None)
+    unknown = [k for k in (bounds or {}) if k not in b]
+    if unknown:
+        raise ValueError(f"bounds: unknown key(s) {unknown}: the keys are {tuple(b)}")
+    b.update(bounds or {})
+    if b["amplitude_max"] is None:
+        b["amplitude_max"] = 0.5 * (gabor.video_range[1] - gabor.video_range[0]) if gabor.video_range is not None else float("inf")
+    y0, x0, wh, ww = gabor.window if gabor.window is not None else (0, 0, *gabor.size)
+    inf = float("inf")
+    lo = dict(cy=float(y0), cx=float(x0), sigma=float(b["sigma_min"]), theta=-inf, sf=0.0, tf=-inf, phase=-inf, amplitude=0.0)
+    hi = dict(cy=float(y0 + wh - 1), cx=float(x0 + ww - 1), sigma=inf, theta=inf, sf=float(b["sf_max"]), tf=inf, phase=inf,
+              amplitude=float(b["amplitude_max"]))
+    return torch.tensor([lo[n] for n in PARAM_NAMES]), torch.tensor([hi[n] for n in PARAM_NAMES])
+
+
+def optimal_gabor(model, mouse_index: int, neurons: Index, *, starts, steps: int, lr: float, scales: Optional[dict] = None,
+                  bounds: Optional[dict] = None, frames: Index = None, shape: Tuple[int, int, int] = (16, 64, 64),
+                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, learn: Optional[Sequence[str]] = None,
+                  **geometry) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The Gabor that drives ``neurons`` best: multi-start gradient ascent in Gabor-parameter space.
+
+    ``starts`` is the start table — a dict of name -> scalar or [S] with at least one [S] entry, or a tensor [S, 8] in the order
+    of ``stimuli.PARAM_NAMES``; all ``S`` clips are one batch (in eval mode the clips are independent: BatchNorm is frozen and
+    squeeze-excitation is per sample).  The objective of a start is the summed predicted response of ``neurons`` over ``frames``
+    (default all) to its clip of ``shape`` = (frames, height, width); ``geometry`` are further ``DriftingGabor`` arguments
+    (``envelope``, ``background``, ``video_range``, ``window``, ``pad``, ``behavior``, ``pupil_center``, ...).
+
+    The eight parameters differ in scale, so the ascent runs on ``z`` with ``params = start + scales * z`` (``scales``: name ->
+    step scale, default ``DEFAULT_GABOR_SCALES``): ``steps`` Adam steps of size ``lr`` on ``z``, in plain torch on [S, 8].  After
+    every step the parameters are projected onto ``gabor_bounds(bounds)``.  ``learn`` restricts the ascent to some names.
+    Nothing synchronises with the host inside the loop; parameter ``.grad`` fields of the model are not touched.
+
+    Returns ``(params [S, 8], trace [steps + 1, S])``: the final parameters and the objective of every start before each step
+    plus the final one, on the device.  The best start is ``trace[-1].argmax()``."""
+    from .stimuli import PARAM_NAMES, DriftingGabor, default_params, param_table
+    device = next(model.parameters()).device
+    t, h, w = (int(n) for n in shape)
+    if isinstance(starts, dict):
+        sizes = {int(torch.as_tensor(v).numel()) for v in starts.values() if torch.as_tensor(v).dim() == 1}
+        if len(sizes) != 1:
+            raise ValueError("starts: a dict needs at least one [S] entry, and all [S] entries of one length")
+        S = sizes.pop()
+        probe = DriftingGabor(1, 1, (h, w), **{k: v for k, v in geometry.items() if k in ("window", "video_range")})
+        table = param_table(S, starts, default_params((h, w), probe.window, probe.video_range))
+    else:
+        table = torch.as_tensor(starts, dtype=torch.float32).detach().cpu()
+        if table.dim() != 2 or table.shape[1] != len(PARAM_NAMES) or table.shape[0] < 1:
+            raise ValueError("starts: a dict of name -> values or a tensor [S, 8]")
+        S = int(table.shape[0])
+    unknown = [k for k in (scales or {}) if k not in PARAM_NAMES]
+    if unknown:
+        raise ValueError(f"scales: unknown Gabor parameter(s) {unknown}")
+    sc = {**DEFAULT_GABOR_SCALES, **(scales or {})}
+    if int(steps) < 0 or any(not float(v) > 0 for v in sc.values()):
+        raise ValueError("steps must not be negative and every scale must be positive")
+    gabor = DriftingGabor(S, t, (h, w), **geometry).to(device)
+    lo, hi = (b.to(device) for b in gabor_bounds(gabor, bounds))
+    scale = torch.tensor([float(sc[n]) for n in PARAM_NAMES], device=device)
+    mask = torch.tensor([learn is None or n in learn for n in PARAM_NAMES], device=device)
+    start = table.to(device).clamp(lo, hi)
+    z = torch.zeros(S, len(PARAM_NAMES), device=device)
+    m, v = torch.zeros_like(z), torch.zeros_like(z)
+    nsel, fsel = _as_index(neurons, device), _as_index(frames, device)
+    trace = torch.zeros(steps + 1, S, dtype=torch.float32, device=device)
+
+    def objective(zz):
+        out = model(gabor.render(start + scale * zz), index=mouse_index)
+        return out[:, nsel][:, :, fsel].float().sum(dim=(1, 2))
+
+    b1, b2 = betas
+    with _eval_mode(model):
+        for i in range(steps):
+            zg = z.detach().requires_grad_(True)
+            with torch.enable_grad():
+                r = objective(zg)
+                (g,) = torch.autograd.grad(r.sum(), zg)
+            trace[i] = r.detach()
+            g = torch.where(mask, g, torch.zeros_like(g))
+            m.mul_(b1).add_(g, alpha=1 - b1)
+            v.mul_(b2).addcmul_(g, g, value=1 - b2)
+            step = (m / (1 - b1 ** (i + 1))) / ((v / (1 - b2 ** (i + 1))).sqrt() + eps)
+            p = (start + scale * (z + lr * step)).clamp(lo, hi)
+            z = (p - start) / scale
+        with torch.enable_grad():       # (an input requiring grad: the last entry comes from the same kernels as the others)
+            trace[steps] = objective(z.detach().requires_grad_(True)).detach()
+    return (start + scale * z).clamp(lo, hi), trace

@@ -308,7 +308,7 @@ int dwn_sizeof(const char* name) {
     SZ(dwn_stem_args); SZ(dwn_block_args); SZ(dwn_pool_args); SZ(dwn_cortex_args); SZ(dwn_readout_args);
     SZ(dwn_tensor_entry); SZ(dwn_clip_src); SZ(dwn_clip_desc); SZ(dwn_pw_bwd_args); SZ(dwn_dw_spatial_rc_fwd_args);
     SZ(dwn_stem_input_grad_args); SZ(dwn_guarded_entry); SZ(dwn_step_guard); SZ(dwn_gaze_args);
-    SZ(dwn_corr_args);
+    SZ(dwn_corr_args); SZ(dwn_gabor_args);
 #undef SZ
     return -1;
 }
@@ -1251,6 +1251,46 @@ int dwn_corr_loss_backward(const dwn_corr_args* a, int device, void* stream) {
     if (!a->pred || !a->target || !a->w || !a->stat || !a->share || !a->dpred) return dwn_set_error(-1, "corr_loss_backward: null pointer (pred, target, w, stat, share, dpred)");
     ENTER(device);
     return k_corr_backward(*a, (hipStream_t)stream);
+}
+
+// ---- in-silico stimuli: the argument checks need no device
+static int gabor_geometry(const dwn_gabor_args* a) {
+    if (a->B <= 0 || a->Cin <= 0 || a->T <= 0 || a->H <= 0 || a->W <= 0) return dwn_set_error(-2, "gabor: B, Cin, T, H, W must be positive");
+    if (a->video_channel < 0 || a->video_channel >= a->Cin) return dwn_set_error(-2, "gabor: video_channel outside [0, Cin)");
+    if ((long long)a->H * a->W > (1ll << 30) || (long long)a->B * a->Cin * a->T >= (1ll << 31))
+        return dwn_set_error(-2, "gabor: more than 2^30 pixels per plane or 2^31 planes");
+    if (a->envelope != DWN_GABOR_GAUSSIAN && a->envelope != DWN_GABOR_NONE) return dwn_set_error(-2, "gabor: envelope must be DWN_GABOR_GAUSSIAN or DWN_GABOR_NONE");
+    if (a->wh == 0 && a->ww == 0) {
+        if (a->y0 != 0 || a->x0 != 0) return dwn_set_error(-2, "gabor: window not inside the plane (an empty window must start at 0, 0)");
+    } else if (a->y0 < 0 || a->x0 < 0 || a->wh <= 0 || a->ww <= 0 || a->wh > a->H - a->y0 || a->ww > a->W - a->x0) {
+        return dwn_set_error(-2, "gabor: window not inside the plane");
+    }
+    if (a->clamp != 0 && a->clamp != 1) return dwn_set_error(-2, "gabor: clamp must be 0 or 1");
+    if (a->clamp && !(a->lo <= a->hi)) return dwn_set_error(-2, "gabor: video range needs lo <= hi");
+    const long long wpix = a->wh ? (long long)a->wh * a->ww : (long long)a->H * a->W;
+    if ((long long)a->B * a->T * ((wpix + 1023) / 1024) >= (1ll << 31)) return dwn_set_error(-2, "gabor: more than 2^31 partial sums");
+    return 0;
+}
+size_t dwn_gabor_workspace_bytes(const dwn_gabor_args* a) {
+    if (!a || gabor_geometry(a) != 0) { g_err[0] = 0; return 0; }
+    return k_gabor_ws_bytes(*a);
+}
+int dwn_gabor_forward(const dwn_gabor_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "gabor_forward: null arguments");
+    TRY(gabor_geometry(a));
+    if (!a->x || !a->params || !a->out) return dwn_set_error(-1, "gabor_forward: null pointer (x, params, out)");
+    ENTER(device);
+    return k_gabor_forward(*a, (hipStream_t)stream);
+}
+int dwn_gabor_backward(const dwn_gabor_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "gabor_backward: null arguments");
+    TRY(gabor_geometry(a));
+    if (!a->params || !a->dout || !a->dparams || !a->ws) return dwn_set_error(-1, "gabor_backward: null pointer (params, dout, dparams, ws)");
+    if (a->ws_bytes < k_gabor_ws_bytes(*a) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "gabor_backward: workspace smaller than dwn_gabor_workspace_bytes or not 8-byte aligned");
+    ENTER(device);
+    return k_gabor_backward(*a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -810,3 +810,74 @@ class PlaneMeanFn(torch.autograd.Function):
         dx = torch.zeros(shape, dtype=torch.float32, device=dmean.device)
         dx[:, c0:c0 + nc] = (dmean.float().permute(0, 2, 1) / float(shape[3] * shape[4]))[..., None, None]
         return dx, None, None
+
+
+# ------------------------------------------------------------------------------------------------
+# in-silico stimuli (sensorium_amd/stimuli.py)
+# ------------------------------------------------------------------------------------------------
+GABOR_ENVELOPES = {"gaussian": L.GABOR_GAUSSIAN, "none": L.GABOR_NONE}
+
+
+def _gabor_args(shape, video_channel, envelope, background, video_range, window, pad) -> L.GaborArgs:
+    if envelope not in GABOR_ENVELOPES:
+        raise ValueError(f"envelope: one of {tuple(GABOR_ENVELOPES)} (got {envelope!r})")
+    a = L.GaborArgs()
+    a.B, a.Cin, a.T, a.H, a.W = (int(n) for n in shape)
+    a.video_channel = int(video_channel)
+    a.envelope = GABOR_ENVELOPES[envelope]
+    a.background = float(background)
+    a.pad = float(pad)
+    if video_range is not None:
+        a.clamp, a.lo, a.hi = 1, float(video_range[0]), float(video_range[1])
+    if window is not None:
+        a.y0, a.x0, a.wh, a.ww = (int(n) for n in window)
+    return a
+
+
+class GaborFn(torch.autograd.Function):
+    """``GaborFn.apply(params, template, video_channel, envelope, background, video_range, window, pad) -> input``: a drifting
+    Gabor per clip (``params`` [B][8]: cy, cx, sigma, theta, sf, tf, phase, amplitude) rendered into channel ``video_channel`` of
+    a copy of ``template`` [B][C][T][H][W] (include/dwn.h dwn_gabor_args).  The gradient w.r.t. ``params`` is one float64
+    fixed-order reduction of the video channel of the incoming gradient; the gradient w.r.t. ``template`` passes through on the
+    copied channels and is zero on the video channel."""
+
+    @staticmethod
+    def forward(ctx, params, template, video_channel=0, envelope="gaussian", background=127.5, video_range=(0.0, 255.0),
+                window=None, pad=0.0):
+        _require_gpu(params, "GaborFn")
+        _require_gpu(template, "GaborFn")
+        if template.dim() != 5 or params.shape != (template.shape[0], 8):
+            raise RuntimeError("sensorium_amd.GaborFn: template must be [B][C][T][H][W] and params [B][8]")
+        template = template.contiguous().float()
+        params = params.contiguous().float()
+        dev = template.device
+        geom = (tuple(template.shape), int(video_channel), envelope, float(background),
+                None if video_range is None else (float(video_range[0]), float(video_range[1])),
+                None if window is None else tuple(int(n) for n in window), float(pad))
+        a = _gabor_args(*geom)
+        out = torch.empty_like(template)
+        a.x = template.data_ptr(); a.params = params.data_ptr(); a.out = out.data_ptr()
+        L.check(L.lib.dwn_gabor_forward(C.byref(a), dev.index, _stream(dev)), "dwn_gabor_forward")
+        ctx.geom = geom
+        ctx.save_for_backward(params)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        (params,) = ctx.saved_tensors
+        dev = dout.device
+        dout = dout.contiguous().float()
+        dparams = dtemplate = None
+        if ctx.needs_input_grad[0]:
+            a = _gabor_args(*ctx.geom)
+            nbytes = L.lib.dwn_gabor_workspace_bytes(C.byref(a))
+            ws = torch.empty(max(int(nbytes), 8) // 8, dtype=torch.float64, device=dev)
+            dparams = torch.empty_like(params)
+            a.params = params.data_ptr(); a.dout = dout.data_ptr(); a.dparams = dparams.data_ptr()
+            a.ws = ws.data_ptr(); a.ws_bytes = ws.numel() * 8
+            L.check(L.lib.dwn_gabor_backward(C.byref(a), dev.index, _stream(dev)), "dwn_gabor_backward")
+        if ctx.needs_input_grad[1]:
+            dtemplate = dout.clone()
+            dtemplate[:, ctx.geom[1]] = 0
+        return dparams, dtemplate, None, None, None, None, None, None
