@@ -725,6 +725,36 @@ size_t dwn_gabor_workspace_bytes(const dwn_gabor_args* a);       /* 0 for argume
 int dwn_gabor_forward(const dwn_gabor_args* a, int device, void* stream);
 int dwn_gabor_backward(const dwn_gabor_args* a, int device, void* stream);
 
+/* ---- behaviour modulator: a per-neuron gain on a readout's output, driven by the behaviour features of each frame.
+ * y, out, dout, dy: [B][N][T] fp32 contiguous (the readouts' layout); h, dh: [B][T][K] fp32; u, du: [N][K]; c, dc: [N];
+ * m = max_log_gain.
+ *   a[b,n,t]   = c[n] + sum_k h[b,t,k] u[n,k]          (fp32 FMAs, k ascending, starting from c[n])
+ *   gain       = exp(m tanh(a))                         in [e^-m, e^m], exactly 1 at a = 0
+ *   out[b,n,t] = y[b,n,t] gain
+ *   dy = dout gain,   s = dout y gain m sech^2(a),   du[n,k] = sum_{b,t} s h[b,t,k],   dc[n] = sum_{b,t} s,
+ *   dh[b,t,k] = sum_n s u[n,k]
+ * sech^2(a) = 4 e / (1 + e)^2 with e = exp(-2 |a|): it does not cancel for large |a|.  The products are fp32; the three sums run
+ * in float64 in a fixed order through per-workgroup partials in ws (dwn_modulator_ws_bytes(a) bytes, 8-byte aligned; it depends on
+ * B, N, T, K alone) and are rounded to fp32 once.  No atomics: the same inputs give the same bits, in both builds.  du, dc and dh
+ * are written, not accumulated.  A null dy / dh / du / dc is skipped, and its partials are neither computed nor stored.
+ * A frame (b, t) whose h row holds a NaN or an Inf gets NaN in out[b,:,t], dy[b,:,t] and in every sum the frame enters; other
+ * frames are untouched.  u = c = 0 returns y (and dout in dy) bit for bit.  No access leaves the tensors for any T.
+ * dwn_modulator_forward needs y, h, u, c, out (out must not alias y) and no workspace.  dwn_modulator_backward needs y, h, u, c,
+ * dout, ws and at least one of dy, dh, du, dc.  Nothing is allocated and nothing is read back: both entries can be captured.
+ * Argument errors are answered before the device is entered: null pointer -1; a non-positive size, K outside [1, 32], a
+ * max_log_gain that is not finite and positive, out == y, or a workspace that is too small or misaligned -2. */
+typedef struct dwn_modulator_args {
+    int B, N, T, K;
+    float max_log_gain; int pad_;
+    const float* y; const float* h; const float* u; const float* c;
+    float* out;
+    const float* dout; float* dy; float* dh; float* du; float* dc;
+    void* ws; size_t ws_bytes;
+} dwn_modulator_args;
+size_t dwn_modulator_ws_bytes(const dwn_modulator_args* a);      /* backward only; forward needs none; 0 for refused arguments */
+int dwn_modulator_forward(const dwn_modulator_args* a, int device, void* stream);
+int dwn_modulator_backward(const dwn_modulator_args* a, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,8 +8,9 @@ from . import _lib  # noqa: F401  (raises ImportError when the HIP library is ab
 from .dwiseneuro import DwiseNeuro  # noqa: F401
 from .losses import MiceCorrelationLoss, MicePoissonCorrelationLoss, MicePoissonLoss  # noqa: F401
 from .shifter import DwiseNeuroGaze, GazeShifter  # noqa: F401
+from .modulator import BehaviorModulator, DwiseNeuroBehavior  # noqa: F401
 from .stimuli import PARAM_NAMES, DriftingGabor  # noqa: F401
 from .attribution import optimal_gabor, tuning_curve  # noqa: F401
 
-__all__ = ["DwiseNeuro", "DwiseNeuroGaze", "GazeShifter", "MicePoissonLoss", "MiceCorrelationLoss", "MicePoissonCorrelationLoss",
+__all__ = ["DwiseNeuro", "DwiseNeuroGaze", "GazeShifter", "DwiseNeuroBehavior", "BehaviorModulator", "MicePoissonLoss", "MiceCorrelationLoss", "MicePoissonCorrelationLoss",
            "DriftingGabor", "PARAM_NAMES", "tuning_curve", "optimal_gabor"]

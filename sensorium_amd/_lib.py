@@ -203,6 +203,12 @@ class GaborArgs(C.Structure):             # in-silico stimuli (include/dwn.h dwn
                 ("ws_bytes", c_sz)]
 
 
+class ModulatorArgs(C.Structure):         # behaviour modulator (include/dwn.h dwn_modulator_args)
+    _fields_ = [("B", c_i), ("N", c_i), ("T", c_i), ("K", c_i), ("max_log_gain", c_f), ("pad_", c_i), ("y", c_p), ("h", c_p),
+                ("u", c_p), ("c", c_p), ("out", c_p), ("dout", c_p), ("dy", c_p), ("dh", c_p), ("du", c_p), ("dc", c_p),
+                ("ws", c_p), ("ws_bytes", c_sz)]
+
+
 CORR_STAT_ROWS, CORR_TILE = 8, 16          # DWN_CORR_STAT_ROWS, DWN_CORR_TILE
 CORR_MEAN, CORR_SUM = 0, 1
 GABOR_GAUSSIAN, GABOR_NONE = 0, 1          # DWN_GABOR_*
@@ -218,7 +224,7 @@ _STRUCTS = {
     "dwn_clip_src": ClipSrc, "dwn_clip_desc": ClipDesc, "dwn_pw_bwd_args": PwBwdArgs,
     "dwn_dw_spatial_rc_fwd_args": DwSpatialRcFwdArgs, "dwn_stem_input_grad_args": StemInputGradArgs,
     "dwn_guarded_entry": GuardedEntry, "dwn_step_guard": StepGuard, "dwn_gaze_args": GazeArgs,
-    "dwn_corr_args": CorrArgs, "dwn_gabor_args": GaborArgs,
+    "dwn_corr_args": CorrArgs, "dwn_gabor_args": GaborArgs, "dwn_modulator_args": ModulatorArgs,
 }
 
 # every symbol include/dwn.h declares: (restype, argtypes)
@@ -291,6 +297,9 @@ SYMBOLS = {
     "dwn_gabor_workspace_bytes": (c_sz, [_P(GaborArgs)]),
     "dwn_gabor_forward": (c_i, [_P(GaborArgs), c_i, c_p]),
     "dwn_gabor_backward": (c_i, [_P(GaborArgs), c_i, c_p]),
+    "dwn_modulator_ws_bytes": (c_sz, [_P(ModulatorArgs)]),
+    "dwn_modulator_forward": (c_i, [_P(ModulatorArgs), c_i, c_p]),
+    "dwn_modulator_backward": (c_i, [_P(ModulatorArgs), c_i, c_p]),
 }
 
 
@@ -301,7 +310,7 @@ class DwnError(RuntimeError):
 # csrc/Makefile HASH_SRCS, in its order
 HASH_SRCS = ("dwn_api.hip", "dwn_gemm.hip", "dwn_gemm_nn_1.hip", "dwn_gemm_nn_2.hip", "dwn_gemm_nn_3.hip", "dwn_gemm_nn_4.hip", "dwn_gemm_nn_5.hip",
              "dwn_gemm_nn_6.hip", "dwn_gemm_tn.hip", "dwn_pw_bwd.hip", "dwn_gemm_xl.hip", "dwn_gemm_kd.hip", "dwn_dwconv.hip", "dwn_dwrc.hip",
-             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
+             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
              "dwn_kernels.h", "dwn_launch.h", "dwn_gemm_nn.h",
              "../../include/dwn.h")
 
@@ -327,8 +336,9 @@ def _load():
                            "dwn_dw_temporal_wide_bwd", "dwn_gaze_shift_forward", "dwn_gaze_shift_backward",
                            "dwn_plane_mean", "dwn_corr_ws_bytes", "dwn_corr_moments", "dwn_corr_loss_finalize",
                            "dwn_corr_loss_backward", "dwn_gabor_workspace_bytes", "dwn_gabor_forward",
-                           "dwn_gabor_backward") and not hasattr(lib, name):
-            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli; the plain training step calls none of them)
+                           "dwn_gabor_backward", "dwn_modulator_ws_bytes", "dwn_modulator_forward",
+                           "dwn_modulator_backward") and not hasattr(lib, name):
+            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator; the plain training step calls none of them)
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -340,7 +350,7 @@ def _load():
                           f"`make -C {LIB_PATH.parent}` — binaries are not in git, so what runs must be what is committed")
     for cname, struct in _STRUCTS.items():
         n = lib.dwn_sizeof(cname.encode())
-        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args"))):      # (A/B: ABI 7 only appended)
+        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args"))):      # (A/B: ABI 7 only appended)
             raise ImportError(f"struct layout mismatch for {cname}: C {n} bytes vs ctypes {C.sizeof(struct)}")
     return lib
 

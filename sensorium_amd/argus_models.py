@@ -29,6 +29,7 @@ from .ema import ModelEma
 from .engine import Model
 from .losses import MiceCorrelationLoss, MicePoissonCorrelationLoss, MicePoissonLoss
 from .optim import FusedAdamWEma
+from .modulator import DwiseNeuroBehavior
 from .shifter import DwiseNeuroGaze
 
 
@@ -78,7 +79,7 @@ def fill_distill_targets(distill_prediction, target, distill_ratio: float):
 class MouseModel(Model):
     """``fit`` / ``validate`` / ``save`` come from ``engine.Model`` (the argus surface train.py:141-145 uses);
     ``load_model`` finds this class by the ``model_name`` stored in the checkpoint."""
-    nn_module = {"dwiseneuro": DwiseNeuro, "dwiseneuro_gaze": DwiseNeuroGaze}
+    nn_module = {"dwiseneuro": DwiseNeuro, "dwiseneuro_gaze": DwiseNeuroGaze, "dwiseneuro_behavior": DwiseNeuroBehavior}
     loss = {"mice_poisson": MicePoissonLoss, "mice_correlation": MiceCorrelationLoss,
             "mice_poisson_correlation": MicePoissonCorrelationLoss}
     optimizer = {"AdamW": FusedAdamWEma}

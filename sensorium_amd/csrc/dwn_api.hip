@@ -308,7 +308,7 @@ int dwn_sizeof(const char* name) {
     SZ(dwn_stem_args); SZ(dwn_block_args); SZ(dwn_pool_args); SZ(dwn_cortex_args); SZ(dwn_readout_args);
     SZ(dwn_tensor_entry); SZ(dwn_clip_src); SZ(dwn_clip_desc); SZ(dwn_pw_bwd_args); SZ(dwn_dw_spatial_rc_fwd_args);
     SZ(dwn_stem_input_grad_args); SZ(dwn_guarded_entry); SZ(dwn_step_guard); SZ(dwn_gaze_args);
-    SZ(dwn_corr_args); SZ(dwn_gabor_args);
+    SZ(dwn_corr_args); SZ(dwn_gabor_args); SZ(dwn_modulator_args);
 #undef SZ
     return -1;
 }
@@ -1291,6 +1291,42 @@ int dwn_gabor_backward(const dwn_gabor_args* a, int device, void* stream) {
     if (a->ws_bytes < k_gabor_ws_bytes(*a) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "gabor_backward: workspace smaller than dwn_gabor_workspace_bytes or not 8-byte aligned");
     ENTER(device);
     return k_gabor_backward(*a, (hipStream_t)stream);
+}
+
+// ---- behaviour modulator: the argument checks need no device
+static int modulator_geometry(const dwn_modulator_args* a) {
+    if (a->B <= 0 || a->N <= 0 || a->T <= 0) return dwn_set_error(-2, "modulator: B, N, T must be positive");
+    if (a->K < 1 || a->K > 32) return dwn_set_error(-2, "modulator: K outside [1, 32]");
+    if (!(a->max_log_gain > 0.f) || !(a->max_log_gain <= 3.402823466e38f)) return dwn_set_error(-2, "modulator: max_log_gain must be finite and positive");
+    // the grids are one workgroup per (128 neurons, 64 frames, sample): keep them and the partial counts below 2^31
+    const long long tiles = ((long long)a->N + 127) / 128 * (((long long)a->T + 63) / 64) * a->B;
+    if (tiles >= (1ll << 31) || (long long)a->B * a->T * a->K >= (1ll << 31) || (long long)a->N * a->K >= (1ll << 31))
+        return dwn_set_error(-2, "modulator: more than 2^31 tiles, behaviour features or weights");
+    return 0;
+}
+size_t dwn_modulator_ws_bytes(const dwn_modulator_args* a) {
+    if (!a || modulator_geometry(a) != 0) { g_err[0] = 0; return 0; }
+    return k_modulator_ws_bytes(*a);
+}
+int dwn_modulator_forward(const dwn_modulator_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "modulator_forward: null arguments");
+    TRY(modulator_geometry(a));
+    if (!a->y || !a->h || !a->u || !a->c || !a->out) return dwn_set_error(-1, "modulator_forward: null pointer (y, h, u, c, out)");
+    if (a->out == a->y) return dwn_set_error(-2, "modulator_forward: out must not alias y");
+    ENTER(device);
+    return k_modulator_forward(*a, (hipStream_t)stream);
+}
+int dwn_modulator_backward(const dwn_modulator_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "modulator_backward: null arguments");
+    TRY(modulator_geometry(a));
+    if (!a->y || !a->h || !a->u || !a->c || !a->dout) return dwn_set_error(-1, "modulator_backward: null pointer (y, h, u, c, dout)");
+    if (!a->dy && !a->dh && !a->du && !a->dc) return dwn_set_error(-1, "modulator_backward: dy, dh, du and dc are all null");
+    if (!a->ws) return dwn_set_error(-1, "modulator_backward: null pointer (ws)");
+    if (a->ws_bytes < k_modulator_ws_bytes(*a) || ((size_t)a->ws & 7)) return dwn_set_error(-2, "modulator_backward: workspace smaller than dwn_modulator_ws_bytes or not 8-byte aligned");
+    ENTER(device);
+    return k_modulator_backward(*a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -127,6 +127,10 @@ int k_corr_backward(const dwn_corr_args& a, hipStream_t s);
 size_t k_gabor_ws_bytes(const dwn_gabor_args& a);
 int k_gabor_forward(const dwn_gabor_args& a, hipStream_t s);
 int k_gabor_backward(const dwn_gabor_args& a, hipStream_t s);      // partials into a.ws, then the per-clip fold
+// behaviour modulator (dwn.h dwn_modulator_args; dwn_modulator.hip): arguments checked by the C-ABI layer
+size_t k_modulator_ws_bytes(const dwn_modulator_args& a);
+int k_modulator_forward(const dwn_modulator_args& a, hipStream_t s);
+int k_modulator_backward(const dwn_modulator_args& a, hipStream_t s);      // a.dy, a.dh, a.du, a.dc: each may be null
 int k_pw_bwd_prep(const float* w1, const float* abc, int E, int C, void* bp, float* gacc, float* r3, int dtype,
                   const float* res_abc, int res_C, hipStream_t s);
 // conv_pw weight gradient from the raw products (see pw_bwd_fused_kernel): tacc [(E + C + 8)][C] fp32 = rows T1 = dh1^T a0,

@@ -881,3 +881,57 @@ class GaborFn(torch.autograd.Function):
             dtemplate = dout.clone()
             dtemplate[:, ctx.geom[1]] = 0
         return dparams, dtemplate, None, None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------
+# behaviour modulator (sensorium_amd/modulator.py)
+# ------------------------------------------------------------------------------------------------
+def _modulator_args(y, h, u, c, max_log_gain: float) -> L.ModulatorArgs:
+    a = L.ModulatorArgs()
+    a.B, a.N, a.T = (int(n) for n in y.shape)
+    a.K = int(h.shape[2])
+    a.max_log_gain = float(max_log_gain)
+    a.y = y.data_ptr(); a.h = h.data_ptr(); a.u = u.data_ptr(); a.c = c.data_ptr()
+    return a
+
+
+class ModulatorFn(torch.autograd.Function):
+    """``ModulatorFn.apply(y, h, u, c, max_log_gain) -> y * exp(max_log_gain * tanh(c[n] + h[b,t,:] . u[n,:]))`` for a readout's
+    output ``y`` [B][N][T], the behaviour features ``h`` [B][T][K], the per-neuron weights ``u`` [N][K] and offsets ``c`` [N]
+    (include/dwn.h dwn_modulator_args).  The backward asks the kernels only for the gradients autograd needs; the three
+    reductions (du, dc over the rows, dh over the neurons) are float64 sums in a fixed order, without atomics."""
+
+    @staticmethod
+    def forward(ctx, y, h, u, c, max_log_gain=2.0):
+        for t in (y, h, u, c):
+            _require_gpu(t, "ModulatorFn")
+        if y.dim() != 3 or h.dim() != 3 or h.shape[:2] != (y.shape[0], y.shape[2]) or u.shape != (y.shape[1], h.shape[2]) \
+                or c.shape != (y.shape[1],):
+            raise RuntimeError("sensorium_amd.ModulatorFn: y must be [B][N][T], h [B][T][K], u [N][K] and c [N]")
+        y = y.contiguous().float(); h = h.contiguous().float(); u = u.contiguous().float(); c = c.contiguous().float()
+        dev = y.device
+        out = torch.empty_like(y)
+        a = _modulator_args(y, h, u, c, max_log_gain)
+        a.out = out.data_ptr()
+        L.check(L.lib.dwn_modulator_forward(C.byref(a), dev.index, _stream(dev)), "dwn_modulator_forward")
+        ctx.max_log_gain = float(max_log_gain)
+        ctx.save_for_backward(y, h, u, c)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        y, h, u, c = ctx.saved_tensors
+        need = ctx.needs_input_grad[:4]
+        if not any(need):
+            return None, None, None, None, None
+        dev = dout.device
+        dout = dout.contiguous().float()
+        dy, dh, du, dc = (torch.empty_like(t) if n else None for t, n in zip((y, h, u, c), need))
+        a = _modulator_args(y, h, u, c, ctx.max_log_gain)
+        nbytes = L.lib.dwn_modulator_ws_bytes(C.byref(a))
+        ws = torch.empty(max(int(nbytes), 8) // 8, dtype=torch.float64, device=dev)
+        a.dout = dout.data_ptr(); a.dy = _ptr(dy); a.dh = _ptr(dh); a.du = _ptr(du); a.dc = _ptr(dc)
+        a.ws = ws.data_ptr(); a.ws_bytes = ws.numel() * 8
+        L.check(L.lib.dwn_modulator_backward(C.byref(a), dev.index, _stream(dev)), "dwn_modulator_backward")
+        return dy, dh, du, dc, None
