@@ -755,6 +755,81 @@ size_t dwn_modulator_ws_bytes(const dwn_modulator_args* a);      /* backward onl
 int dwn_modulator_forward(const dwn_modulator_args* a, int device, void* stream);
 int dwn_modulator_backward(const dwn_modulator_args* a, int device, void* stream);
 
+/* ---- regularised MEI synthesis: a separable three-axis blur of one channel, per-clip moments of one channel and
+ * the two element-wise updates of the pixel-space ascent.  All tensors are [B][Cin][T][H][W] fp32 contiguous and ONE channel of
+ * them is used; the window rectangle (y0, x0, wh, ww) — wh == ww == 0 (then y0 == x0 == 0): the whole plane — is the same in
+ * every frame.  Nothing is allocated and nothing is read back: every entry can be captured.  No atomics, and every grid depends
+ * on the geometry alone: the same inputs give the same bits, in both builds.  No tensor value is converted to an index.
+ * Argument errors are answered before the device is entered: null pointer -1; geometry -2 (a non-positive size, a channel
+ * outside [0, Cin), a radius outside [0, DWN_BLUR_MAX_RADIUS], a window not inside the plane, lo > hi or a NaN bound, an unknown
+ * mode); workspace too small or misaligned -3.  The *_ws_bytes functions return 0 for arguments the entries would refuse.
+ *
+ * dwn_blur3d: dst[b][c_dst][t][y][x] = sum_{i,j,k} kt[i] kh[j] kw[k] src[b][c_src][t+i-Rt][y+j-Rh][x+k-Rw] inside the window, the
+ * source counting as zero outside the window and outside [0, T); inside the plane but outside the window dst[b][c_dst] is written
+ * with 0 and the source is not read there; the other channels of dst are not touched.  `taps` is a DEVICE table
+ * float[3][2 * DWN_BLUR_MAX_RADIUS + 1] read at run time (axis a = 0, 1, 2 for t, y, x uses entries 0 .. 2 Ra, entry Ra is the
+ * centre); the taps are neither assumed symmetric nor normalised.  Evaluated axis by axis in fp32: x and y in one launch (the
+ * frame tile and its halo in LDS) into ws, then t from ws into dst; every sum starts from its first product and continues with
+ * FMAs in ascending tap order, so a radius of 0 with tap 1.0f is the identity on that axis bit for bit.  ws holds
+ * dwn_blur3d_ws_bytes(a) = B T H W floats (4-byte aligned) and must not overlap src or dst; dst may be src, the same channel included (the second launch reads ws only).
+ *
+ * dwn_clip_moments: stat[b][4] = {n, mean, M2 = sum (x - mean)^2, S2 = sum x^2} in float64 over the n = T wh ww window elements of
+ * channel c of clip b.  One workgroup per (clip, chunk of DWN_MOMENTS_CHUNK elements) writes {sum, sum (x - chunk mean)^2, sum x^2}
+ * to ws (dwn_clip_moments_ws_bytes(a) bytes, 8-byte aligned); one workgroup per clip folds them in a fixed order:
+ * mean = (sum of sums) / n, M2 = sum_chunks (M2_c + n_c (mean_c - mean)^2).  M2 is never formed from raw sums.  A constant clip
+ * returns its constant as the mean bit for bit and M2 == 0.
+ *
+ * dwn_mei_update, in place on the window of channel c of x; stat is the [B][4] table above, read on the device:
+ *   DWN_MEI_STEP     x = (float)((double)x + (double)*lr * g * c_b),  c_b = 1 / sqrt(S2_b / n) from the moments of g (channel c_g of
+ *                    g [B][Cin_g][T][H][W]); a clip with S2_b == 0 is not written.  lr is a device scalar.
+ *   DWN_MEI_PROJECT  sd = sqrt(M2 / n), m = has_mean ? mean_target : mu,
+ *                    s = has_contrast ? (FIXED: sd == 0 ? 0 : contrast / sd;  MAX: sd == 0 ? 1 : min(1, contrast / sd)) : 1,
+ *                    x = clamp((float)(m + s * ((double)x - mu)), lo, hi) from the moments (mu, M2) of x itself; a clip with
+ *                    s == 1 and m == mu (as doubles) is only clamped.
+ * A clip whose statistics are not finite becomes NaN inside its window; other clips are untouched.  Pixels outside the window are
+ * never written. */
+#define DWN_BLUR_MAX_RADIUS 16
+#define DWN_BLUR_TAPS_STRIDE (2 * DWN_BLUR_MAX_RADIUS + 1)
+#define DWN_MOMENTS_CHUNK 4096
+enum { DWN_MEI_STEP = 0, DWN_MEI_PROJECT = 1 };
+enum { DWN_MEI_CONTRAST_MAX = 0, DWN_MEI_CONTRAST_FIXED = 1 };
+typedef struct dwn_blur3d_args {
+    int B, T, H, W;
+    int Cin_src, c_src, Cin_dst, c_dst;
+    int Rt, Rh, Rw;
+    int y0, x0, wh, ww;
+    int pad_;
+    const float* src;
+    float* dst;
+    const float* taps;        /* device: float[3][DWN_BLUR_TAPS_STRIDE] */
+    void* ws; size_t ws_bytes;
+} dwn_blur3d_args;
+typedef struct dwn_clip_moments_args {
+    int B, Cin, T, H, W, c;
+    int y0, x0, wh, ww;
+    const float* x;
+    double* stat;             /* [B][4] */
+    void* ws; size_t ws_bytes;
+} dwn_clip_moments_args;
+typedef struct dwn_mei_update_args {
+    int mode;                 /* DWN_MEI_STEP / DWN_MEI_PROJECT */
+    int B, Cin, T, H, W, c;
+    int y0, x0, wh, ww;
+    int Cin_g, c_g;           /* STEP: the layout of g */
+    int has_mean, has_contrast, contrast_mode;
+    float lo, hi;
+    double mean_target, contrast;
+    float* x;
+    const float* g;           /* STEP */
+    const double* stat;       /* [B][4]: of g (STEP), of x (PROJECT) */
+    const float* lr;          /* STEP: device scalar */
+} dwn_mei_update_args;
+size_t dwn_blur3d_ws_bytes(const dwn_blur3d_args* a);
+size_t dwn_clip_moments_ws_bytes(const dwn_clip_moments_args* a);
+int dwn_blur3d(const dwn_blur3d_args* a, int device, void* stream);
+int dwn_clip_moments(const dwn_clip_moments_args* a, int device, void* stream);
+int dwn_mei_update(const dwn_mei_update_args* a, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

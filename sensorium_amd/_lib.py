@@ -209,9 +209,30 @@ class ModulatorArgs(C.Structure):         # behaviour modulator (include/dwn.h d
                 ("ws", c_p), ("ws_bytes", c_sz)]
 
 
+class Blur3dArgs(C.Structure):            # regularised MEI synthesis (include/dwn.h dwn_blur3d_args)
+    _fields_ = [("B", c_i), ("T", c_i), ("H", c_i), ("W", c_i), ("Cin_src", c_i), ("c_src", c_i), ("Cin_dst", c_i), ("c_dst", c_i),
+                ("Rt", c_i), ("Rh", c_i), ("Rw", c_i), ("y0", c_i), ("x0", c_i), ("wh", c_i), ("ww", c_i), ("pad_", c_i),
+                ("src", c_p), ("dst", c_p), ("taps", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
+
+
+class ClipMomentsArgs(C.Structure):       # (include/dwn.h dwn_clip_moments_args)
+    _fields_ = [("B", c_i), ("Cin", c_i), ("T", c_i), ("H", c_i), ("W", c_i), ("c", c_i), ("y0", c_i), ("x0", c_i), ("wh", c_i),
+                ("ww", c_i), ("x", c_p), ("stat", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
+
+
+class MeiUpdateArgs(C.Structure):         # (include/dwn.h dwn_mei_update_args)
+    _fields_ = [("mode", c_i), ("B", c_i), ("Cin", c_i), ("T", c_i), ("H", c_i), ("W", c_i), ("c", c_i), ("y0", c_i), ("x0", c_i),
+                ("wh", c_i), ("ww", c_i), ("Cin_g", c_i), ("c_g", c_i), ("has_mean", c_i), ("has_contrast", c_i),
+                ("contrast_mode", c_i), ("lo", c_f), ("hi", c_f), ("mean_target", C.c_double), ("contrast", C.c_double),
+                ("x", c_p), ("g", c_p), ("stat", c_p), ("lr", c_p)]
+
+
 CORR_STAT_ROWS, CORR_TILE = 8, 16          # DWN_CORR_STAT_ROWS, DWN_CORR_TILE
 CORR_MEAN, CORR_SUM = 0, 1
 GABOR_GAUSSIAN, GABOR_NONE = 0, 1          # DWN_GABOR_*
+BLUR_MAX_RADIUS, BLUR_TAPS_STRIDE, MOMENTS_CHUNK = 16, 33, 4096      # DWN_BLUR_MAX_RADIUS, DWN_BLUR_TAPS_STRIDE, DWN_MOMENTS_CHUNK
+MEI_STEP, MEI_PROJECT = 0, 1               # DWN_MEI_*
+MEI_CONTRAST_MAX, MEI_CONTRAST_FIXED = 0, 1
 MIX_BOX, MIX_BLEND = 0, 1
 VID_U8, VID_F32 = 0, 1
 
@@ -225,6 +246,7 @@ _STRUCTS = {
     "dwn_dw_spatial_rc_fwd_args": DwSpatialRcFwdArgs, "dwn_stem_input_grad_args": StemInputGradArgs,
     "dwn_guarded_entry": GuardedEntry, "dwn_step_guard": StepGuard, "dwn_gaze_args": GazeArgs,
     "dwn_corr_args": CorrArgs, "dwn_gabor_args": GaborArgs, "dwn_modulator_args": ModulatorArgs,
+    "dwn_blur3d_args": Blur3dArgs, "dwn_clip_moments_args": ClipMomentsArgs, "dwn_mei_update_args": MeiUpdateArgs,
 }
 
 # every symbol include/dwn.h declares: (restype, argtypes)
@@ -300,6 +322,11 @@ SYMBOLS = {
     "dwn_modulator_ws_bytes": (c_sz, [_P(ModulatorArgs)]),
     "dwn_modulator_forward": (c_i, [_P(ModulatorArgs), c_i, c_p]),
     "dwn_modulator_backward": (c_i, [_P(ModulatorArgs), c_i, c_p]),
+    "dwn_blur3d_ws_bytes": (c_sz, [_P(Blur3dArgs)]),
+    "dwn_clip_moments_ws_bytes": (c_sz, [_P(ClipMomentsArgs)]),
+    "dwn_blur3d": (c_i, [_P(Blur3dArgs), c_i, c_p]),
+    "dwn_clip_moments": (c_i, [_P(ClipMomentsArgs), c_i, c_p]),
+    "dwn_mei_update": (c_i, [_P(MeiUpdateArgs), c_i, c_p]),
 }
 
 
@@ -310,7 +337,7 @@ class DwnError(RuntimeError):
 # csrc/Makefile HASH_SRCS, in its order
 HASH_SRCS = ("dwn_api.hip", "dwn_gemm.hip", "dwn_gemm_nn_1.hip", "dwn_gemm_nn_2.hip", "dwn_gemm_nn_3.hip", "dwn_gemm_nn_4.hip", "dwn_gemm_nn_5.hip",
              "dwn_gemm_nn_6.hip", "dwn_gemm_tn.hip", "dwn_pw_bwd.hip", "dwn_gemm_xl.hip", "dwn_gemm_kd.hip", "dwn_dwconv.hip", "dwn_dwrc.hip",
-             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
+             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_mei.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
              "dwn_kernels.h", "dwn_launch.h", "dwn_gemm_nn.h",
              "../../include/dwn.h")
 
@@ -337,8 +364,9 @@ def _load():
                            "dwn_plane_mean", "dwn_corr_ws_bytes", "dwn_corr_moments", "dwn_corr_loss_finalize",
                            "dwn_corr_loss_backward", "dwn_gabor_workspace_bytes", "dwn_gabor_forward",
                            "dwn_gabor_backward", "dwn_modulator_ws_bytes", "dwn_modulator_forward",
-                           "dwn_modulator_backward") and not hasattr(lib, name):
-            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator; the plain training step calls none of them)
+                           "dwn_modulator_backward", "dwn_blur3d_ws_bytes", "dwn_clip_moments_ws_bytes", "dwn_blur3d",
+                           "dwn_clip_moments", "dwn_mei_update") and not hasattr(lib, name):
+            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator / the MEI kernels; the plain training step calls none of them)
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -350,7 +378,7 @@ def _load():
                           f"`make -C {LIB_PATH.parent}` — binaries are not in git, so what runs must be what is committed")
     for cname, struct in _STRUCTS.items():
         n = lib.dwn_sizeof(cname.encode())
-        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args"))):      # (A/B: ABI 7 only appended)
+        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args", "dwn_blur3d_args", "dwn_clip_moments_args", "dwn_mei_update_args"))):      # (A/B: ABI 7 only appended)
             raise ImportError(f"struct layout mismatch for {cname}: C {n} bytes vs ctypes {C.sizeof(struct)}")
     return lib
 

@@ -31,6 +31,14 @@ def _response(model, x: torch.Tensor, mouse_index: int, neurons, frames, reduce:
     return sel.sum() if reduce == "sum" else sel.mean()
 
 
+def _set_response(model, x: torch.Tensor, mouse_index: int, idx: torch.Tensor, maskf: torch.Tensor, frames) -> torch.Tensor:
+    """[B] objectives: clip b's predicted responses summed over its own neurons ``idx[b]`` (padded; ``maskf`` marks the real
+    entries) and the chosen frames.  A padded gather and a mask: plain torch, nothing synchronises with the host."""
+    out = model(x, index=mouse_index)                            # [B, N, T]
+    sel = out.gather(1, idx[:, :, None].expand(-1, -1, out.shape[2]))[:, :, frames].float()
+    return (sel * maskf[:, :, None]).sum(dim=(1, 2))
+
+
 def _eval_mode(model):
     class _Scope:
         def __enter__(self):
@@ -49,10 +57,21 @@ def input_gradient(model, inputs: torch.Tensor, mouse_index: int, neurons: Index
 
     ``response`` is the sum (``reduce="sum"``) or mean (``"mean"``) over the batch, the chosen ``neurons`` (indices into the
     mouse's readout; default all) and ``frames`` (default all) of ``model(inputs, index=mouse_index)``.  The model is evaluated
-    in eval mode (restored afterwards); parameter ``.grad`` fields are not touched."""
+    in eval mode (restored afterwards); parameter ``.grad`` fields are not touched.  ``neurons`` may also be one index list per
+    clip (a sequence of ``B`` sequences, possibly ragged, or a 2-D LongTensor; ``reduce="sum"``): the eval-mode clips are
+    independent, so clip ``b`` then holds the gradient of the summed response of its own set."""
     if reduce not in ("sum", "mean"):
         raise ValueError("reduce: 'sum' or 'mean'")
     x = inputs.detach().clone().requires_grad_(True)
+    if _per_clip_sets(neurons):         # one index list per clip: clip b gets the gradient of the response of its own set
+        if reduce != "sum":
+            raise ValueError("per-clip neuron sets: reduce must be 'sum'")
+        idx, maskf = _padded_sets(neurons, x.device)
+        if idx.shape[0] != x.shape[0]:
+            raise ValueError(f"neurons: {idx.shape[0]} index lists for {x.shape[0]} clips")
+        with _eval_mode(model), torch.enable_grad():
+            (grad,) = torch.autograd.grad(_set_response(model, x, mouse_index, idx, maskf, _as_index(frames, x.device)).sum(), x)
+        return grad
     with _eval_mode(model), torch.enable_grad():
         r = _response(model, x, mouse_index, _as_index(neurons, x.device), _as_index(frames, x.device), reduce)
         (grad,) = torch.autograd.grad(r, x)
@@ -63,7 +82,9 @@ def most_exciting_input(model, mouse_index: int, neurons: Index, *, shape: Tuple
                         lr: float, init: Optional[torch.Tensor] = None, video_range: Tuple[float, float] = (0.0, 255.0),
                         norm_budget: Optional[float] = None, behavior: Optional[Sequence[float]] = None,
                         pupil_center: Optional[Sequence[float]] = None, frames: Index = None,
-                        device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                        device=None, blur_sigma=None, mean: Optional[float] = None, contrast: Optional[float] = None,
+                        contrast_mode: str = "max", window: Optional[Sequence[int]] = None,
+                        use_graph: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """Most-exciting-input synthesis by projected gradient ascent on the video channel.
 
     Starts from ``init`` (a full model input [B, 5, T, H, W] or [5, T, H, W]; its channels 1-4 are kept as they are) or, without
@@ -75,7 +96,19 @@ def most_exciting_input(model, mouse_index: int, neurons: Index, *, shape: Tuple
 
     Everything stays on the device and nothing synchronises with the host inside the loop.  Returns ``(inputs, trace)``: the
     final model input (same shape as the start) and the response before each step plus the final one, ``steps + 1`` values on
-    the device."""
+    the device.
+
+    The regularised ascent runs when any of the following is given; without them the plain loop above runs.
+    ``blur_sigma``: the gradient's video part is blurred by a separable Gaussian before the step: three sigmas (frames, pixels,
+    pixels) or a ``[steps][3]`` schedule (the radii come from the largest sigma of each axis).  ``lr`` may be a length-``steps``
+    schedule.  ``mean``: every clip is shifted to this mean luminance after each step.  ``contrast``: the RMS deviation from the
+    clip's mean in grey levels, an upper bound (``contrast_mode="max"``) or an equality (``"fixed"``); not together with
+    ``norm_budget``.  ``window`` = (y0, x0, height, width): blur, statistics and updates see that rectangle of every frame only,
+    pixels outside it never change.  ``neurons`` may be one index list per clip (a sequence of ``B`` sequences, possibly ragged,
+    or a 2-D LongTensor): clip ``b`` then ascends the summed response of its own set and ``trace`` is ``[steps + 1, B]`` (a start
+    of one clip is repeated ``B`` times).  ``use_graph``: one step is captured into a graph and replayed ``steps`` times; between
+    replays only device-to-device copies run (the step's taps, its ``lr``, its response).  Eager and replayed steps make the same
+    calls on the same buffers: the same bits wherever the model's own kernels are reproducible (the ordered-reduction build)."""
     lo, hi = float(video_range[0]), float(video_range[1])
     mid = 0.5 * (lo + hi)
     if device is None:
@@ -99,6 +132,12 @@ def most_exciting_input(model, mouse_index: int, neurons: Index, *, shape: Tuple
                 x[:, base] = float(vals[0])
                 x[:, base + 1] = float(vals[1])
     x = x.contiguous()
+    if (blur_sigma is not None or mean is not None or contrast is not None or contrast_mode != "max" or window is not None
+            or use_graph or not isinstance(lr, (int, float)) or _per_clip_sets(neurons)):
+        x, trace = _mei_regularised(model, mouse_index, neurons, x, steps=steps, lr=lr, video_range=(lo, hi),
+                                    norm_budget=norm_budget, frames=frames, blur_sigma=blur_sigma, mean=mean, contrast=contrast,
+                                    contrast_mode=contrast_mode, window=window, use_graph=use_graph)
+        return (x[0] if squeeze and x.shape[0] == 1 else x), trace
     nsel = _as_index(neurons, device)
     fsel = _as_index(frames, device)
     trace = torch.zeros(steps + 1, dtype=torch.float32, device=device)
@@ -121,6 +160,174 @@ def most_exciting_input(model, mouse_index: int, neurons: Index, *, shape: Tuple
         with torch.enable_grad():       # (input requiring grad: the last entry comes from the same kernels as the others)
             trace[steps] = _response(model, x.detach().requires_grad_(True), mouse_index, nsel, fsel, "sum").detach()
     return (x[0] if squeeze else x), trace
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# regularised pixel-space ascent
+# ------------------------------------------------------------------------------------------------------------------------------
+def _per_clip_sets(neurons) -> bool:
+    """True for one index list per clip: a 2-D tensor or a sequence of sequences."""
+    if isinstance(neurons, torch.Tensor):
+        return neurons.dim() == 2
+    if neurons is None or isinstance(neurons, slice):
+        return False
+    return len(neurons) > 0 and all(isinstance(n, (list, tuple)) or (isinstance(n, torch.Tensor) and n.dim() >= 1) for n in neurons)
+
+
+def _padded_sets(neurons, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-clip index lists -> (indices [B, K] padded with 0, mask [B, K] fp32)."""
+    if isinstance(neurons, torch.Tensor):
+        idx = neurons.to(device=device, dtype=torch.long)
+        return idx.contiguous(), torch.ones(idx.shape, dtype=torch.float32, device=device)
+    sets = [torch.as_tensor(n, dtype=torch.long).flatten() for n in neurons]
+    K = max(int(n.numel()) for n in sets)
+    if K < 1 or any(n.numel() < 1 for n in sets):
+        raise ValueError("neurons: every clip needs at least one neuron")
+    idx = torch.zeros(len(sets), K, dtype=torch.long)
+    mask = torch.zeros(len(sets), K, dtype=torch.float32)
+    for b, n in enumerate(sets):
+        idx[b, :n.numel()] = n
+        mask[b, :n.numel()] = 1.0
+    return idx.to(device), mask.to(device)
+
+
+def mei_schedules(steps: int, lr, blur_sigma):
+    """Host side of the schedules of the regularised ascent: ``(lr [steps] fp32, tables [steps][3][DWN_BLUR_TAPS_STRIDE] fp32 or
+    None, radii or None)`` on the CPU.  The radius of an axis is ``ceil(3 sigma)`` of its largest sigma (capped at
+    ``DWN_BLUR_MAX_RADIUS``), so the geometry of the blur does not change along a schedule."""
+    import math
+    from . import ops
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("steps must not be negative")
+    lr_t = torch.as_tensor(lr, dtype=torch.float32).detach().cpu().flatten()
+    if lr_t.numel() == 1 and not isinstance(lr, (list, tuple, torch.Tensor)):
+        lr_t = lr_t.expand(steps).clone()
+    if lr_t.numel() != steps or not bool(torch.isfinite(lr_t).all()):
+        raise ValueError("lr: a finite float or a schedule of length `steps`")
+    if blur_sigma is None:
+        return lr_t, None, None
+    sig = torch.as_tensor(blur_sigma, dtype=torch.float64).detach().cpu()
+    if sig.dim() == 1 and sig.numel() == 3:
+        sig = sig[None].expand(max(steps, 1), 3)
+    if sig.dim() != 2 or sig.shape != (max(steps, 1), 3) and sig.shape != (steps, 3):
+        raise ValueError("blur_sigma: three floats (frames, pixels, pixels) or a [steps][3] schedule")
+    if not bool((torch.isfinite(sig) & (sig >= 0)).all()):
+        raise ValueError("blur_sigma: finite and not negative")
+    radii = tuple(min(int(math.ceil(3.0 * float(sig[:, a].max()))), ops.L.BLUR_MAX_RADIUS) if sig.shape[0] else 0 for a in range(3))
+    tables = torch.stack([ops.blur_taps_table([ops.gaussian_taps(float(row[a]), radii[a]) for a in range(3)])[0] for row in sig]) \
+        if sig.shape[0] else torch.zeros(0, 3, ops.L.BLUR_TAPS_STRIDE)
+    return lr_t, tables, radii
+
+
+def _mei_regularised(model, mouse_index: int, neurons, x: torch.Tensor, *, steps: int, lr, video_range, norm_budget, frames,
+                     blur_sigma, mean, contrast, contrast_mode, window, use_graph) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The regularised ascent of ``most_exciting_input`` on the start ``x`` [B, C, T, H, W] (changed in place)."""
+    from . import ops
+    device = x.device
+    lo, hi = video_range
+    mid = 0.5 * (lo + hi)
+    if contrast is not None and norm_budget is not None:
+        raise ValueError("contrast and norm_budget are two different budgets: give one")
+    if contrast_mode not in ops.MEI_CONTRAST_MODES:
+        raise ValueError(f"contrast_mode: one of {tuple(ops.MEI_CONTRAST_MODES)} (got {contrast_mode!r})")
+    if contrast is not None and not float(contrast) >= 0.0:
+        raise ValueError("contrast must not be negative")
+    if not lo <= hi:
+        raise ValueError("video_range: lo <= hi")
+    H, W = int(x.shape[3]), int(x.shape[4])
+    if window is not None:
+        if len(window) != 4:
+            raise ValueError("window: (y0, x0, height, width)")
+        y0, x0, wh, ww = (int(n) for n in window)
+        if y0 < 0 or x0 < 0 or wh < 1 or ww < 1 or y0 + wh > H or x0 + ww > W:
+            raise ValueError(f"window {tuple(window)} is not inside the {H} x {W} plane")
+        window = (y0, x0, wh, ww)
+    lr_sched, tables, radii = mei_schedules(steps, lr, blur_sigma)
+    steps = int(steps)
+    sets = _per_clip_sets(neurons)
+    fsel = _as_index(frames, device)
+    if sets:
+        idx, maskf = _padded_sets(neurons, device)
+        if x.shape[0] == 1 and idx.shape[0] > 1:
+            x = x.expand(idx.shape[0], *x.shape[1:]).contiguous()
+        if idx.shape[0] != x.shape[0]:
+            raise ValueError(f"neurons: {idx.shape[0]} index lists for {x.shape[0]} clips")
+    else:
+        nsel = _as_index(neurons, device)
+    B = int(x.shape[0])
+
+    def objective(xg):
+        if not sets:
+            return _response(model, xg, mouse_index, nsel, fsel, "sum")
+        return _set_response(model, xg, mouse_index, idx, maskf, fsel)
+
+    # everything a step reads or writes besides x lives in buffers that exist before the first step: the eager loop and the
+    # captured graph run the same calls on the same memory
+    lr_sched = lr_sched.to(device)
+    lr_cur = torch.zeros(1, dtype=torch.float32, device=device)
+    if tables is not None:
+        tables = tables.to(device)
+        table_cur = torch.zeros(3, ops.L.BLUR_TAPS_STRIDE, dtype=torch.float32, device=device)
+        gb = torch.zeros(B, 1, *x.shape[2:], dtype=torch.float32, device=device)
+        blur_ws = torch.empty(gb.numel(), dtype=torch.float32, device=device)
+    stat_g = torch.zeros(B, 4, dtype=torch.float64, device=device)
+    stat_x = torch.zeros(B, 4, dtype=torch.float64, device=device)
+    mom_ws = torch.empty(ops.clip_moments_ws(x.shape, window), dtype=torch.float64, device=device)
+    r_cur = torch.zeros(B if sets else 1, dtype=torch.float32, device=device)
+    trace = torch.zeros((steps + 1, B) if sets else (steps + 1,), dtype=torch.float32, device=device)
+    wy, wx = (slice(window[0], window[0] + window[2]), slice(window[1], window[1] + window[3])) if window else (slice(None),) * 2
+
+    def step():
+        xg = x.detach().requires_grad_(True)
+        with torch.enable_grad():
+            r = objective(xg)
+            (g,) = torch.autograd.grad(r.sum() if sets else r, xg)
+        r_cur.copy_(r.detach().reshape(-1))
+        g = g.contiguous()
+        if tables is not None:
+            ops.blur3d(g, table_cur, radii, c_src=0, out=gb, window=window, ws=blur_ws)
+            g = gb
+        ops.clip_moments(g, c=0, window=window, out=stat_g, ws=mom_ws)
+        ops.mei_update(x, stat_g, "step", g=g, lr=lr_cur, window=window)
+        if norm_budget is not None:
+            v = x[:, 0, :, wy, wx]
+            dev_ = v - mid
+            n = dev_.flatten(1).norm(dim=1).clamp_min_(1e-20)
+            v.copy_(mid + dev_ * (float(norm_budget) / n).clamp_max_(1.0).view(-1, 1, 1, 1))
+        ops.clip_moments(x, c=0, window=window, out=stat_x, ws=mom_ws)
+        ops.mei_update(x, stat_x, "project", window=window, mean=mean, contrast=contrast, contrast_mode=contrast_mode,
+                       video_range=(lo, hi))
+
+    def load(i):
+        lr_cur.copy_(lr_sched[i:i + 1])
+        if tables is not None:
+            table_cur.copy_(tables[i])
+
+    with _eval_mode(model):
+        graph = None
+        if use_graph and steps > 0:
+            start = x.clone()
+            load(0)
+            side = torch.cuda.Stream(device)
+            side.wait_stream(torch.cuda.current_stream(device))
+            with torch.cuda.stream(side):                          # warm-up outside the capture (allocator, lazy loads)
+                step()
+            torch.cuda.current_stream(device).wait_stream(side)
+            x.copy_(start)                                         # the warm-up stepped x: put the start back
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                step()
+        for i in range(steps):
+            load(i)
+            if graph is not None:
+                graph.replay()
+            else:
+                step()
+            trace[i].copy_(r_cur if sets else r_cur[0])
+        with torch.enable_grad():       # (input requiring grad: the last entry comes from the same kernels as the others)
+            trace[steps] = objective(x.detach().requires_grad_(True)).detach()
+    return x, trace
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -309,6 +309,7 @@ int dwn_sizeof(const char* name) {
     SZ(dwn_tensor_entry); SZ(dwn_clip_src); SZ(dwn_clip_desc); SZ(dwn_pw_bwd_args); SZ(dwn_dw_spatial_rc_fwd_args);
     SZ(dwn_stem_input_grad_args); SZ(dwn_guarded_entry); SZ(dwn_step_guard); SZ(dwn_gaze_args);
     SZ(dwn_corr_args); SZ(dwn_gabor_args); SZ(dwn_modulator_args);
+    SZ(dwn_blur3d_args); SZ(dwn_clip_moments_args); SZ(dwn_mei_update_args);
 #undef SZ
     return -1;
 }
@@ -1327,6 +1328,80 @@ int dwn_modulator_backward(const dwn_modulator_args* a, int device, void* stream
     if (a->ws_bytes < k_modulator_ws_bytes(*a) || ((size_t)a->ws & 7)) return dwn_set_error(-2, "modulator_backward: workspace smaller than dwn_modulator_ws_bytes or not 8-byte aligned");
     ENTER(device);
     return k_modulator_backward(*a, (hipStream_t)stream);
+}
+
+// ---- regularised MEI synthesis: the argument checks need no device
+static int mei_plane(const char* who, int B, int Cin, int T, int H, int W, int c, int y0, int x0, int wh, int ww) {
+    static thread_local char msg[160];
+#define MEI_BAD(text) do { snprintf(msg, sizeof msg, "%s: %s", who, text); return dwn_set_error(-2, msg); } while (0)
+    if (B <= 0 || Cin <= 0 || T <= 0 || H <= 0 || W <= 0) MEI_BAD("B, Cin, T, H, W must be positive");
+    if (c < 0 || c >= Cin) MEI_BAD("channel outside [0, Cin)");
+    if ((long long)H * W > (1ll << 30) || (long long)B * Cin * T >= (1ll << 31)) MEI_BAD("more than 2^30 pixels per plane or 2^31 planes");
+    if (wh == 0 && ww == 0) {
+        if (y0 != 0 || x0 != 0) MEI_BAD("window not inside the plane (an empty window must start at 0, 0)");
+    } else if (y0 < 0 || x0 < 0 || wh <= 0 || ww <= 0 || wh > H - y0 || ww > W - x0) {
+        MEI_BAD("window not inside the plane");
+    }
+    // one clip's window elements are indexed by an int, and every grid stays below 2^31 workgroups
+    if ((long long)T * H * W > (1ll << 30) || (long long)B * T * H * W / 64 >= (1ll << 31)) MEI_BAD("more than 2^30 elements per clip or 2^37 in all");
+#undef MEI_BAD
+    return 0;
+}
+static int blur3d_geometry(const dwn_blur3d_args* a) {
+    TRY(mei_plane("blur3d", a->B, a->Cin_src, a->T, a->H, a->W, a->c_src, a->y0, a->x0, a->wh, a->ww));
+    TRY(mei_plane("blur3d", a->B, a->Cin_dst, a->T, a->H, a->W, a->c_dst, a->y0, a->x0, a->wh, a->ww));
+    if (a->Rt < 0 || a->Rh < 0 || a->Rw < 0 || a->Rt > DWN_BLUR_MAX_RADIUS || a->Rh > DWN_BLUR_MAX_RADIUS || a->Rw > DWN_BLUR_MAX_RADIUS)
+        return dwn_set_error(-2, "blur3d: radius outside [0, DWN_BLUR_MAX_RADIUS]");
+    return 0;
+}
+static int moments_geometry(const dwn_clip_moments_args* a) {
+    return mei_plane("clip_moments", a->B, a->Cin, a->T, a->H, a->W, a->c, a->y0, a->x0, a->wh, a->ww);
+}
+size_t dwn_blur3d_ws_bytes(const dwn_blur3d_args* a) {
+    if (!a || blur3d_geometry(a) != 0) { g_err[0] = 0; return 0; }
+    return k_blur3d_ws_bytes(*a);
+}
+size_t dwn_clip_moments_ws_bytes(const dwn_clip_moments_args* a) {
+    if (!a || moments_geometry(a) != 0) { g_err[0] = 0; return 0; }
+    return k_clip_moments_ws_bytes(*a);
+}
+int dwn_blur3d(const dwn_blur3d_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "blur3d: null arguments");
+    TRY(blur3d_geometry(a));
+    if (!a->src || !a->dst || !a->taps || !a->ws) return dwn_set_error(-1, "blur3d: null pointer (src, dst, taps, ws)");
+    if (a->ws_bytes < k_blur3d_ws_bytes(*a) || ((size_t)a->ws & 3)) return dwn_set_error(-3, "blur3d: workspace smaller than dwn_blur3d_ws_bytes or not 4-byte aligned");
+    ENTER(device);
+    return k_blur3d(*a, (hipStream_t)stream);
+}
+int dwn_clip_moments(const dwn_clip_moments_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "clip_moments: null arguments");
+    TRY(moments_geometry(a));
+    if (!a->x || !a->stat || !a->ws) return dwn_set_error(-1, "clip_moments: null pointer (x, stat, ws)");
+    if (a->ws_bytes < k_clip_moments_ws_bytes(*a) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "clip_moments: workspace smaller than dwn_clip_moments_ws_bytes or not 8-byte aligned");
+    ENTER(device);
+    return k_clip_moments(*a, (hipStream_t)stream);
+}
+int dwn_mei_update(const dwn_mei_update_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "mei_update: null arguments");
+    if (a->mode != DWN_MEI_STEP && a->mode != DWN_MEI_PROJECT) return dwn_set_error(-2, "mei_update: mode must be DWN_MEI_STEP or DWN_MEI_PROJECT");
+    TRY(mei_plane("mei_update", a->B, a->Cin, a->T, a->H, a->W, a->c, a->y0, a->x0, a->wh, a->ww));
+    if (a->mode == DWN_MEI_STEP) {
+        TRY(mei_plane("mei_update", a->B, a->Cin_g, a->T, a->H, a->W, a->c_g, a->y0, a->x0, a->wh, a->ww));
+        if (!a->x || !a->g || !a->stat || !a->lr) return dwn_set_error(-1, "mei_update: null pointer (x, g, stat, lr)");
+    } else {
+        if (!(a->lo <= a->hi)) return dwn_set_error(-2, "mei_update: video range needs lo <= hi");
+        if (a->has_contrast && a->contrast_mode != DWN_MEI_CONTRAST_MAX && a->contrast_mode != DWN_MEI_CONTRAST_FIXED)
+            return dwn_set_error(-2, "mei_update: contrast_mode must be DWN_MEI_CONTRAST_MAX or DWN_MEI_CONTRAST_FIXED");
+        if (a->has_contrast && !(a->contrast >= 0.0 && a->contrast <= 1.7976931348623157e308)) return dwn_set_error(-2, "mei_update: contrast must be finite and not negative");
+        if (a->has_mean && !(a->mean_target >= -1.7976931348623157e308 && a->mean_target <= 1.7976931348623157e308)) return dwn_set_error(-2, "mei_update: mean_target must be finite");
+        if (!a->x || !a->stat) return dwn_set_error(-1, "mei_update: null pointer (x, stat)");
+    }
+    if ((size_t)a->stat & 7) return dwn_set_error(-2, "mei_update: stat must be 8-byte aligned");
+    ENTER(device);
+    return k_mei_update(*a, (hipStream_t)stream);
 }
 
 }  // extern "C"

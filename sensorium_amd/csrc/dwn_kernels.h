@@ -127,6 +127,14 @@ int k_corr_backward(const dwn_corr_args& a, hipStream_t s);
 size_t k_gabor_ws_bytes(const dwn_gabor_args& a);
 int k_gabor_forward(const dwn_gabor_args& a, hipStream_t s);
 int k_gabor_backward(const dwn_gabor_args& a, hipStream_t s);      // partials into a.ws, then the per-clip fold
+
+// regularised MEI synthesis (dwn.h dwn_blur3d_args, dwn_clip_moments_args, dwn_mei_update_args; dwn_mei.hip): arguments checked
+// by the C-ABI layer
+size_t k_blur3d_ws_bytes(const dwn_blur3d_args& a);
+int k_blur3d(const dwn_blur3d_args& a, hipStream_t s);              // in-plane pass into a.ws, then the temporal pass
+size_t k_clip_moments_ws_bytes(const dwn_clip_moments_args& a);
+int k_clip_moments(const dwn_clip_moments_args& a, hipStream_t s);  // partials into a.ws, then the per-clip fold
+int k_mei_update(const dwn_mei_update_args& a, hipStream_t s);
 // behaviour modulator (dwn.h dwn_modulator_args; dwn_modulator.hip): arguments checked by the C-ABI layer
 size_t k_modulator_ws_bytes(const dwn_modulator_args& a);
 int k_modulator_forward(const dwn_modulator_args& a, hipStream_t s);

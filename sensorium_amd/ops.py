@@ -935,3 +935,178 @@ class ModulatorFn(torch.autograd.Function):
         a.ws = ws.data_ptr(); a.ws_bytes = ws.numel() * 8
         L.check(L.lib.dwn_modulator_backward(C.byref(a), dev.index, _stream(dev)), "dwn_modulator_backward")
         return dy, dh, du, dc, None
+
+
+# ------------------------------------------------------------------------------------------------
+# regularised MEI synthesis (sensorium_amd/attribution.py most_exciting_input)
+# ------------------------------------------------------------------------------------------------
+MEI_CONTRAST_MODES = {"max": L.MEI_CONTRAST_MAX, "fixed": L.MEI_CONTRAST_FIXED}
+
+
+def gaussian_taps(sigma: float, radius: Optional[int] = None) -> torch.Tensor:
+    """The ``2 * radius + 1`` taps of a sampled Gaussian: float64 ``exp(-k^2 / (2 sigma^2))`` normalised to sum 1 in float64, then
+    rounded to fp32.  ``radius`` defaults to ``ceil(3 sigma)`` and is capped at ``DWN_BLUR_MAX_RADIUS``; ``sigma == 0`` gives the
+    single tap 1.0 (with a given radius: the centred delta).  Pure host code; returns a CPU tensor."""
+    sigma = float(sigma)
+    if not (sigma >= 0.0 and math.isfinite(sigma)):
+        raise ValueError(f"gaussian_taps: sigma must be finite and not negative (got {sigma})")
+    if radius is None:
+        radius = min(int(math.ceil(3.0 * sigma)), L.BLUR_MAX_RADIUS)
+    radius = int(radius)
+    if radius < 0 or radius > L.BLUR_MAX_RADIUS:
+        raise ValueError(f"gaussian_taps: radius outside [0, {L.BLUR_MAX_RADIUS}]")
+    k = np.arange(-radius, radius + 1, dtype=np.float64)
+    w = np.exp(-(k * k) / (2.0 * sigma * sigma)) if sigma > 0.0 else (k == 0).astype(np.float64)
+    return torch.from_numpy((w / w.sum()).astype(np.float32))
+
+
+def blur_taps_table(taps, device=None):
+    """``taps``: three 1-D sequences of odd length (frames, rows, columns) -> (the table [3][DWN_BLUR_TAPS_STRIDE] fp32 that
+    ``dwn_blur3d`` reads, the radii).  Entries past ``2 * radius`` are zero and never read."""
+    if len(taps) != 3:
+        raise ValueError("taps: three sequences (frames, rows, columns)")
+    table = torch.zeros(3, L.BLUR_TAPS_STRIDE, dtype=torch.float32)
+    radii = []
+    for a, t in enumerate(taps):
+        t = torch.as_tensor(t, dtype=torch.float32).detach().cpu()
+        if t.dim() != 1 or t.numel() % 2 != 1 or t.numel() > L.BLUR_TAPS_STRIDE:
+            raise ValueError(f"taps[{a}]: a 1-D sequence of odd length, at most {L.BLUR_TAPS_STRIDE}")
+        table[a, :t.numel()] = t
+        radii.append(t.numel() // 2)
+    return (table if device is None else table.to(device)), tuple(radii)
+
+
+def _window4(window):
+    if window is None:
+        return (0, 0, 0, 0)
+    if len(window) != 4:
+        raise ValueError("window: (y0, x0, height, width)")
+    return tuple(int(n) for n in window)
+
+
+def _video5(t: torch.Tensor, what: str) -> torch.Tensor:
+    _require_gpu(t, what)
+    if t.dim() != 5 or t.dtype != torch.float32 or not t.is_contiguous():
+        raise RuntimeError(f"sensorium_amd.{what}: a contiguous fp32 tensor [B][C][T][H][W]")
+    return t
+
+
+def blur3d(src: torch.Tensor, table: torch.Tensor, radii, *, c_src: int = 0, out: Optional[torch.Tensor] = None, c_dst: int = 0,
+           window=None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Separable blur of channel ``c_src`` of ``src`` [B][C][T][H][W] into channel ``c_dst`` of ``out`` (default: a new
+    [B][1][T][H][W]) with the DEVICE taps ``table`` [3][DWN_BLUR_TAPS_STRIDE] and the integer ``radii`` (frames, rows, columns);
+    include/dwn.h dwn_blur3d.  ``ws``: a fp32 workspace of at least B T H W elements (allocated when not given)."""
+    src = _video5(src, "blur3d")
+    B, _, T, H, W = src.shape
+    if out is None:
+        out = torch.empty(B, 1, T, H, W, dtype=torch.float32, device=src.device)
+    out = _video5(out, "blur3d")
+    if (out.shape[0], *out.shape[2:]) != (B, T, H, W):
+        raise RuntimeError("sensorium_amd.blur3d: src and out differ in B, T, H or W")
+    _require_gpu(table, "blur3d")
+    if table.shape != (3, L.BLUR_TAPS_STRIDE) or table.dtype != torch.float32 or not table.is_contiguous():
+        raise RuntimeError(f"sensorium_amd.blur3d: table must be contiguous fp32 [3][{L.BLUR_TAPS_STRIDE}]")
+    if ws is None:
+        ws = torch.empty(B * T * H * W, dtype=torch.float32, device=src.device)
+    a = L.Blur3dArgs()
+    a.B, a.T, a.H, a.W = B, T, H, W
+    a.Cin_src, a.c_src, a.Cin_dst, a.c_dst = int(src.shape[1]), int(c_src), int(out.shape[1]), int(c_dst)
+    a.Rt, a.Rh, a.Rw = (int(r) for r in radii)
+    a.y0, a.x0, a.wh, a.ww = _window4(window)
+    a.src = src.data_ptr(); a.dst = out.data_ptr(); a.taps = table.data_ptr()
+    a.ws = ws.data_ptr(); a.ws_bytes = ws.numel() * ws.element_size()
+    L.check(L.lib.dwn_blur3d(C.byref(a), src.device.index, _stream(src.device)), "dwn_blur3d")
+    return out
+
+
+def clip_moments_ws(shape, window=None) -> int:
+    """float64 elements of the workspace of ``clip_moments`` for a tensor of ``shape`` (at least 1)."""
+    a = L.ClipMomentsArgs()
+    a.B, a.Cin, a.T, a.H, a.W = (int(n) for n in shape)
+    a.y0, a.x0, a.wh, a.ww = _window4(window)
+    return max(int(L.lib.dwn_clip_moments_ws_bytes(C.byref(a))) // 8, 1)
+
+
+def clip_moments(x: torch.Tensor, *, c: int = 0, window=None, out: Optional[torch.Tensor] = None,
+                 ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-clip float64 statistics [B][4] = (n, mean, M2, S2) of channel ``c`` of ``x`` [B][C][T][H][W] over the window
+    (include/dwn.h dwn_clip_moments)."""
+    x = _video5(x, "clip_moments")
+    dev = x.device
+    if out is None:
+        out = torch.empty(x.shape[0], 4, dtype=torch.float64, device=dev)
+    if ws is None:
+        ws = torch.empty(clip_moments_ws(x.shape, window), dtype=torch.float64, device=dev)
+    a = L.ClipMomentsArgs()
+    a.B, a.Cin, a.T, a.H, a.W = (int(n) for n in x.shape)
+    a.c = int(c)
+    a.y0, a.x0, a.wh, a.ww = _window4(window)
+    a.x = x.data_ptr(); a.stat = out.data_ptr(); a.ws = ws.data_ptr(); a.ws_bytes = ws.numel() * 8
+    L.check(L.lib.dwn_clip_moments(C.byref(a), dev.index, _stream(dev)), "dwn_clip_moments")
+    return out
+
+
+def mei_update(x: torch.Tensor, stat: torch.Tensor, mode: str, *, c: int = 0, window=None, g: Optional[torch.Tensor] = None,
+               c_g: int = 0, lr: Optional[torch.Tensor] = None, mean: Optional[float] = None, contrast: Optional[float] = None,
+               contrast_mode: str = "max", video_range=(0.0, 255.0)) -> torch.Tensor:
+    """In place on the window of channel ``c`` of ``x`` (include/dwn.h dwn_mei_update).  ``mode="step"``: ``x += lr * g / rms(g)``
+    per clip with ``stat`` the moments of channel ``c_g`` of ``g`` and ``lr`` a one-element fp32 device tensor.
+    ``mode="project"``: the mean / RMS-contrast projection and the clamp to ``video_range`` with ``stat`` the moments of ``x``."""
+    x = _video5(x, "mei_update")
+    dev = x.device
+    _require_gpu(stat, "mei_update")
+    if stat.shape != (x.shape[0], 4) or stat.dtype != torch.float64 or not stat.is_contiguous():
+        raise RuntimeError("sensorium_amd.mei_update: stat must be contiguous float64 [B][4]")
+    if mode not in ("step", "project"):
+        raise ValueError("mode: 'step' or 'project'")
+    if contrast_mode not in MEI_CONTRAST_MODES:
+        raise ValueError(f"contrast_mode: one of {tuple(MEI_CONTRAST_MODES)} (got {contrast_mode!r})")
+    a = L.MeiUpdateArgs()
+    a.B, a.Cin, a.T, a.H, a.W = (int(n) for n in x.shape)
+    a.c = int(c)
+    a.y0, a.x0, a.wh, a.ww = _window4(window)
+    a.x = x.data_ptr(); a.stat = stat.data_ptr()
+    if mode == "step":
+        if g is None or lr is None:
+            raise ValueError("mode 'step' needs g and lr")
+        g = _video5(g, "mei_update")
+        _require_gpu(lr, "mei_update")
+        if (g.shape[0], *g.shape[2:]) != (x.shape[0], *x.shape[2:]) or lr.dtype != torch.float32 or lr.numel() != 1:
+            raise RuntimeError("sensorium_amd.mei_update: g must match x in B, T, H, W and lr be one fp32 element")
+        a.mode, a.Cin_g, a.c_g = L.MEI_STEP, int(g.shape[1]), int(c_g)
+        a.g = g.data_ptr(); a.lr = lr.data_ptr()
+    else:
+        a.mode = L.MEI_PROJECT
+        a.lo, a.hi = float(video_range[0]), float(video_range[1])
+        if mean is not None:
+            a.has_mean, a.mean_target = 1, float(mean)
+        if contrast is not None:
+            a.has_contrast, a.contrast, a.contrast_mode = 1, float(contrast), MEI_CONTRAST_MODES[contrast_mode]
+    L.check(L.lib.dwn_mei_update(C.byref(a), dev.index, _stream(dev)), "dwn_mei_update")
+    return x
+
+
+class GaussianBlur3dFn(torch.autograd.Function):
+    """``GaussianBlur3dFn.apply(x, table, radii, channel, window) -> [B][1][T][H][W]``: ``blur3d`` of one channel of ``x`` with
+    a gradient.  The operator is (window mask) K (window mask), so its adjoint is the same kernel with each axis' taps reversed:
+    the backward blurs the incoming gradient with the reversed table into ``channel`` of a zero tensor shaped like ``x``.  The
+    table gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, table, radii, channel=0, window=None):
+        x = x.contiguous().float()
+        ctx.geom = (tuple(x.shape), tuple(int(r) for r in radii), int(channel), window)
+        ctx.save_for_backward(table)
+        return blur3d(x, table, radii, c_src=channel, window=window)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        (table,) = ctx.saved_tensors
+        shape, radii, channel, window = ctx.geom
+        rev = torch.zeros_like(table)
+        for a, r in enumerate(radii):
+            rev[a, :2 * r + 1] = table[a, :2 * r + 1].flip(0)
+        dx = torch.zeros(shape, dtype=torch.float32, device=dout.device)
+        blur3d(dout.contiguous().float(), rev, radii, c_src=0, out=dx, c_dst=channel, window=window)
+        return dx, None, None, None, None
