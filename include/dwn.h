@@ -830,6 +830,74 @@ int dwn_blur3d(const dwn_blur3d_args* a, int device, void* stream);
 int dwn_clip_moments(const dwn_clip_moments_args* a, int device, void* stream);
 int dwn_mei_update(const dwn_mei_update_args* a, int device, void* stream);
 
+/* ---- trial-level evaluation: per-neuron scores of ONE mouse over whole trials of different length, some of which
+ * repeat the same video.  Trial i has a prediction and a target row per neuron; a row is `frames` contiguous fp32 values that start
+ * `first` elements into a row of stride ld (elements), so a frame cut is an offset and nothing is copied.  Row starts need 4-byte
+ * alignment only: every load is one fp32.  The trials of a group are consecutive in the trial table and have the group's `frames`;
+ * a trial that repeats nothing is a group of repeats = 1.  Both tables live in DEVICE memory and are validated by the caller (every
+ * row they describe must lie inside its allocation); an entry beyond n_trials, max_repeats or max_frames is not followed.
+ *
+ * state: double [DWN_TRIAL_STATE_ROWS][N], zero before the first launch; with d.. deviations from the mean of the row's own set:
+ *   set A, all (trial, frame), count n_all:                 0 mean_p   1 mean_y   2 M2p   3 M2y   4 C = sum dp dy
+ *   set B, the (group, repeat, frame) of groups with repeats >= 2, count n_repeat:
+ *                                                           5 mean_y   6 M2y   7 SSres = sum (y - p)^2
+ *                                                           8 SSwithin = sum_(g,t) [sum_r (y - ybar_gt)^2] / (R_g - 1)
+ *   set C, the (group, frame) averages over repeats, count n_group_frames:
+ *                                                           9 mean_pbar   10 mean_ybar   11 M2pbar   12 M2ybar   13 Cbar
+ *   set D, the leave-one-out mean loo = (R ybar - y) / (R - 1) over the elements of set B (mean_y and M2y are rows 5, 6):
+ *                                                           14 mean_loo   15 M2loo   16 C_y_loo = sum dy dloo
+ * dwn_trial_moments: needs trials, groups, state.  One wave owns one neuron for the whole launch (DWN_TRIAL_TILE neurons per
+ *   workgroup), its lanes run along the frames and loop over the repeats of a frame, so the averages over repeats, the within-frame
+ *   variance and the leave-one-out terms need no traffic between lanes.  Per group: the group means in a first sweep, then in a
+ *   second sweep (from cache) the frame means and the sums of deviations from them and of the frame means from the group mean,
+ *   float64 throughout; the lanes' partials are added by a fixed butterfly.  The groups are taken in table order and merged into the
+ *   state the launch finds with the pairwise (Chan) formulas; an empty side is copied, not divided by.  n_all, n_repeat and
+ *   n_group_frames are the counts of the state BEFORE the launch; the caller advances them by what its tables hold (sum R K, and
+ *   for R >= 2 sum R K and sum K) and passes the advanced counts to the next launch and to dwn_trial_score_finalize.  No atomics, no
+ *   raw sum of squares: launches, splits into several launches at group boundaries, and both builds give the same bits.
+ * dwn_trial_score_finalize: needs state, scores, summary, ws; the counts are those AFTER the last launch.
+ *   scores: double [DWN_TRIAL_SCORE_ROWS][N]; with pearson(Ma, Mb, Cab, n) = (Cab/n) / ((sqrt(Ma/n) + eps)(sqrt(Mb/n) + eps)):
+ *   0 single_trial_corr = pearson(M2p, M2y, C, n_all)            1 corr_to_average = pearson(M2pbar, M2ybar, Cbar, n_group_frames)
+ *   2 fev = (TV - NV) / TV   3 feve = 1 - (MSE - NV) / (TV - NV)   with TV = M2y_B / (n_repeat - 1), NV = SSwithin / n_group_frames,
+ *   MSE = SSres / n_repeat; NaN where TV <= 0 or TV - NV <= 0      4 oracle_corr = pearson(M2y_B, M2loo, C_y_loo, n_repeat)
+ *   A score whose count is 0 is NaN.  summary: double [DWN_TRIAL_SUMMARY] = mean over all N neurons of rows 0, 1, 4 (a NaN neuron
+ *   makes the mean NaN), the mean of feve over the neurons with fev >= fev_threshold, the number of those neurons, n_all, n_repeat,
+ *   n_group_frames: one partial per workgroup into ws (dwn_trial_score_ws_bytes(a) bytes, 8-byte aligned), folded by a
+ *   one-workgroup launch in a fixed order.
+ * Nothing is allocated and nothing is read back.  Argument errors are answered before the device is entered: null pointer -1;
+ * geometry -2 (N, the table sizes, max_repeats, max_frames, counts that are negative or contradict each other, eps <= 0, a NaN
+ * threshold); workspace too small or misaligned -3.  dwn_trial_score_ws_bytes returns 0 for arguments the entries would refuse. */
+#define DWN_TRIAL_STATE_ROWS 17
+#define DWN_TRIAL_SCORE_ROWS 5
+#define DWN_TRIAL_SUMMARY 8
+#define DWN_TRIAL_TILE 4
+typedef struct dwn_trial_desc {
+    const float* pred;
+    const float* target;
+    long long ld_pred, ld_target;     /* elements between consecutive neurons' rows */
+    int first, frames;                /* the kept frames of a row: [first, first + frames) */
+} dwn_trial_desc;
+typedef struct dwn_trial_group {
+    int first_trial, repeats, frames;
+} dwn_trial_group;
+typedef struct dwn_trial_score_args {
+    int N, n_trials, n_groups;
+    int max_repeats, max_frames;      /* upper bounds of the group table's repeats and frames */
+    int pad_;
+    long long n_all, n_repeat, n_group_frames;
+    double eps;                       /* finalize: added to each standard deviation (> 0) */
+    double fev_threshold;             /* finalize */
+    const dwn_trial_desc* trials;     /* device, [n_trials] */
+    const dwn_trial_group* groups;    /* device, [n_groups] */
+    double* state;
+    double* scores;
+    double* summary;
+    void* ws; size_t ws_bytes;
+} dwn_trial_score_args;
+size_t dwn_trial_score_ws_bytes(const dwn_trial_score_args* a);
+int dwn_trial_moments(const dwn_trial_score_args* a, int device, void* stream);
+int dwn_trial_score_finalize(const dwn_trial_score_args* a, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -227,12 +227,27 @@ class MeiUpdateArgs(C.Structure):         # (include/dwn.h dwn_mei_update_args)
                 ("x", c_p), ("g", c_p), ("stat", c_p), ("lr", c_p)]
 
 
+class TrialDesc(C.Structure):             # trial-level evaluation (include/dwn.h dwn_trial_desc: one row of the DEVICE trial table)
+    _fields_ = [("pred", c_p), ("target", c_p), ("ld_pred", c_ll), ("ld_target", c_ll), ("first", c_i), ("frames", c_i)]
+
+
+class TrialGroup(C.Structure):            # (include/dwn.h dwn_trial_group: one row of the DEVICE group table)
+    _fields_ = [("first_trial", c_i), ("repeats", c_i), ("frames", c_i)]
+
+
+class TrialScoreArgs(C.Structure):        # (include/dwn.h dwn_trial_score_args)
+    _fields_ = [("N", c_i), ("n_trials", c_i), ("n_groups", c_i), ("max_repeats", c_i), ("max_frames", c_i), ("pad_", c_i),
+                ("n_all", c_ll), ("n_repeat", c_ll), ("n_group_frames", c_ll), ("eps", c_d), ("fev_threshold", c_d),
+                ("trials", c_p), ("groups", c_p), ("state", c_p), ("scores", c_p), ("summary", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
+
+
 CORR_STAT_ROWS, CORR_TILE = 8, 16          # DWN_CORR_STAT_ROWS, DWN_CORR_TILE
 CORR_MEAN, CORR_SUM = 0, 1
 GABOR_GAUSSIAN, GABOR_NONE = 0, 1          # DWN_GABOR_*
 BLUR_MAX_RADIUS, BLUR_TAPS_STRIDE, MOMENTS_CHUNK = 16, 33, 4096      # DWN_BLUR_MAX_RADIUS, DWN_BLUR_TAPS_STRIDE, DWN_MOMENTS_CHUNK
 MEI_STEP, MEI_PROJECT = 0, 1               # DWN_MEI_*
 MEI_CONTRAST_MAX, MEI_CONTRAST_FIXED = 0, 1
+TRIAL_STATE_ROWS, TRIAL_SCORE_ROWS, TRIAL_SUMMARY, TRIAL_TILE = 17, 5, 8, 4      # DWN_TRIAL_*
 MIX_BOX, MIX_BLEND = 0, 1
 VID_U8, VID_F32 = 0, 1
 
@@ -247,6 +262,7 @@ _STRUCTS = {
     "dwn_guarded_entry": GuardedEntry, "dwn_step_guard": StepGuard, "dwn_gaze_args": GazeArgs,
     "dwn_corr_args": CorrArgs, "dwn_gabor_args": GaborArgs, "dwn_modulator_args": ModulatorArgs,
     "dwn_blur3d_args": Blur3dArgs, "dwn_clip_moments_args": ClipMomentsArgs, "dwn_mei_update_args": MeiUpdateArgs,
+    "dwn_trial_desc": TrialDesc, "dwn_trial_group": TrialGroup, "dwn_trial_score_args": TrialScoreArgs,
 }
 
 # every symbol include/dwn.h declares: (restype, argtypes)
@@ -327,6 +343,9 @@ SYMBOLS = {
     "dwn_blur3d": (c_i, [_P(Blur3dArgs), c_i, c_p]),
     "dwn_clip_moments": (c_i, [_P(ClipMomentsArgs), c_i, c_p]),
     "dwn_mei_update": (c_i, [_P(MeiUpdateArgs), c_i, c_p]),
+    "dwn_trial_score_ws_bytes": (c_sz, [_P(TrialScoreArgs)]),
+    "dwn_trial_moments": (c_i, [_P(TrialScoreArgs), c_i, c_p]),
+    "dwn_trial_score_finalize": (c_i, [_P(TrialScoreArgs), c_i, c_p]),
 }
 
 
@@ -337,7 +356,7 @@ class DwnError(RuntimeError):
 # csrc/Makefile HASH_SRCS, in its order
 HASH_SRCS = ("dwn_api.hip", "dwn_gemm.hip", "dwn_gemm_nn_1.hip", "dwn_gemm_nn_2.hip", "dwn_gemm_nn_3.hip", "dwn_gemm_nn_4.hip", "dwn_gemm_nn_5.hip",
              "dwn_gemm_nn_6.hip", "dwn_gemm_tn.hip", "dwn_pw_bwd.hip", "dwn_gemm_xl.hip", "dwn_gemm_kd.hip", "dwn_dwconv.hip", "dwn_dwrc.hip",
-             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_mei.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
+             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_mei.hip", "dwn_trial_score.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
              "dwn_kernels.h", "dwn_launch.h", "dwn_gemm_nn.h",
              "../../include/dwn.h")
 
@@ -365,8 +384,9 @@ def _load():
                            "dwn_corr_loss_backward", "dwn_gabor_workspace_bytes", "dwn_gabor_forward",
                            "dwn_gabor_backward", "dwn_modulator_ws_bytes", "dwn_modulator_forward",
                            "dwn_modulator_backward", "dwn_blur3d_ws_bytes", "dwn_clip_moments_ws_bytes", "dwn_blur3d",
-                           "dwn_clip_moments", "dwn_mei_update") and not hasattr(lib, name):
-            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator / the MEI kernels; the plain training step calls none of them)
+                           "dwn_clip_moments", "dwn_mei_update", "dwn_trial_score_ws_bytes", "dwn_trial_moments",
+                           "dwn_trial_score_finalize") and not hasattr(lib, name):
+            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator / the MEI kernels / the trial scores; the plain training step calls none of them)
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -378,7 +398,7 @@ def _load():
                           f"`make -C {LIB_PATH.parent}` — binaries are not in git, so what runs must be what is committed")
     for cname, struct in _STRUCTS.items():
         n = lib.dwn_sizeof(cname.encode())
-        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args", "dwn_blur3d_args", "dwn_clip_moments_args", "dwn_mei_update_args"))):      # (A/B: ABI 7 only appended)
+        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args", "dwn_blur3d_args", "dwn_clip_moments_args", "dwn_mei_update_args", "dwn_trial_desc", "dwn_trial_group", "dwn_trial_score_args"))):      # (A/B: ABI 7 only appended)
             raise ImportError(f"struct layout mismatch for {cname}: C {n} bytes vs ctypes {C.sizeof(struct)}")
     return lib
 

@@ -310,6 +310,7 @@ int dwn_sizeof(const char* name) {
     SZ(dwn_stem_input_grad_args); SZ(dwn_guarded_entry); SZ(dwn_step_guard); SZ(dwn_gaze_args);
     SZ(dwn_corr_args); SZ(dwn_gabor_args); SZ(dwn_modulator_args);
     SZ(dwn_blur3d_args); SZ(dwn_clip_moments_args); SZ(dwn_mei_update_args);
+    SZ(dwn_trial_desc); SZ(dwn_trial_group); SZ(dwn_trial_score_args);
 #undef SZ
     return -1;
 }
@@ -1402,6 +1403,43 @@ int dwn_mei_update(const dwn_mei_update_args* a, int device, void* stream) {
     if ((size_t)a->stat & 7) return dwn_set_error(-2, "mei_update: stat must be 8-byte aligned");
     ENTER(device);
     return k_mei_update(*a, (hipStream_t)stream);
+}
+
+// ---- trial-level evaluation: the argument checks need no device
+static int trial_counts(const dwn_trial_score_args* a) {
+    if (a->N <= 0) return dwn_set_error(-2, "trial_score: N must be positive");
+    if (a->n_all < 0 || a->n_repeat < 0 || a->n_group_frames < 0) return dwn_set_error(-2, "trial_score: negative count");
+    if (a->n_all >= (1ll << 52)) return dwn_set_error(-2, "trial_score: n_all must stay below 2^52");
+    // a repeat group adds R K to n_all and n_repeat and K to n_group_frames, R >= 2
+    if (a->n_repeat > a->n_all || 2 * a->n_group_frames > a->n_repeat || (a->n_repeat > 0) != (a->n_group_frames > 0))
+        return dwn_set_error(-2, "trial_score: counts contradict each other (n_repeat <= n_all, 2 n_group_frames <= n_repeat)");
+    return 0;
+}
+size_t dwn_trial_score_ws_bytes(const dwn_trial_score_args* a) { return a && a->N > 0 ? k_trial_score_ws_bytes(a->N) : 0; }
+int dwn_trial_moments(const dwn_trial_score_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "trial_moments: null arguments");
+    TRY(trial_counts(a));
+    if (a->n_trials <= 0 || a->n_groups <= 0 || a->n_groups > a->n_trials) return dwn_set_error(-2, "trial_moments: needs 1 <= n_groups <= n_trials");
+    if (a->max_repeats < 1 || a->max_repeats > a->n_trials) return dwn_set_error(-2, "trial_moments: max_repeats must lie in [1, n_trials]");
+    if (a->max_frames < 1) return dwn_set_error(-2, "trial_moments: max_frames must be positive");
+    if ((long long)a->n_trials * a->max_frames >= (1ll << 52) - a->n_all) return dwn_set_error(-2, "trial_moments: the counts after the launch must stay below 2^52");
+    if (!a->trials || !a->groups || !a->state) return dwn_set_error(-1, "trial_moments: null pointer (trials, groups, state)");
+    if ((size_t)a->state & 7) return dwn_set_error(-2, "trial_moments: state must be 8-byte aligned");
+    ENTER(device);
+    return k_trial_moments(*a, (hipStream_t)stream);
+}
+int dwn_trial_score_finalize(const dwn_trial_score_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "trial_score_finalize: null arguments");
+    TRY(trial_counts(a));
+    if (!(a->eps > 0.0)) return dwn_set_error(-2, "trial_score_finalize: eps must be positive");
+    if (a->fev_threshold != a->fev_threshold) return dwn_set_error(-2, "trial_score_finalize: fev_threshold is NaN");
+    if (!a->state || !a->scores || !a->summary || !a->ws) return dwn_set_error(-1, "trial_score_finalize: null pointer (state, scores, summary, ws)");
+    if (((size_t)a->state & 7) || ((size_t)a->scores & 7) || ((size_t)a->summary & 7)) return dwn_set_error(-2, "trial_score_finalize: state, scores and summary must be 8-byte aligned");
+    if (a->ws_bytes < k_trial_score_ws_bytes(a->N) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "trial_score_finalize: workspace smaller than dwn_trial_score_ws_bytes or not 8-byte aligned");
+    ENTER(device);
+    return k_trial_score_finalize(*a, (hipStream_t)stream);
 }
 
 }  // extern "C"

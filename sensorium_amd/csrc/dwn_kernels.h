@@ -135,6 +135,10 @@ int k_blur3d(const dwn_blur3d_args& a, hipStream_t s);              // in-plane 
 size_t k_clip_moments_ws_bytes(const dwn_clip_moments_args& a);
 int k_clip_moments(const dwn_clip_moments_args& a, hipStream_t s);  // partials into a.ws, then the per-clip fold
 int k_mei_update(const dwn_mei_update_args& a, hipStream_t s);
+// trial-level evaluation (dwn.h dwn_trial_score_args; dwn_trial_score.hip): arguments checked by the C-ABI layer
+size_t k_trial_score_ws_bytes(int N);
+int k_trial_moments(const dwn_trial_score_args& a, hipStream_t s);          // merges the tables' groups into a.state
+int k_trial_score_finalize(const dwn_trial_score_args& a, hipStream_t s);   // scores, partials into a.ws, then the fold
 // behaviour modulator (dwn.h dwn_modulator_args; dwn_modulator.hip): arguments checked by the C-ABI layer
 size_t k_modulator_ws_bytes(const dwn_modulator_args& a);
 int k_modulator_forward(const dwn_modulator_args& a, hipStream_t s);

@@ -1110,3 +1110,97 @@ class GaussianBlur3dFn(torch.autograd.Function):
         dx = torch.zeros(shape, dtype=torch.float32, device=dout.device)
         blur3d(dout.contiguous().float(), rev, radii, c_src=0, out=dx, c_dst=channel, window=window)
         return dx, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------
+# trial-level evaluation (sensorium_amd/evaluation.py)
+# ------------------------------------------------------------------------------------------------
+_TRIAL_DESC = np.dtype([("pred", "<u8"), ("target", "<u8"), ("ld_pred", "<i8"), ("ld_target", "<i8"), ("first", "<i4"),
+                        ("frames", "<i4")])
+_TRIAL_GROUP = np.dtype([("first_trial", "<i4"), ("repeats", "<i4"), ("frames", "<i4")])
+assert _TRIAL_DESC.itemsize == C.sizeof(L.TrialDesc) and _TRIAL_GROUP.itemsize == C.sizeof(L.TrialGroup)
+
+
+def _trial_rows(t: torch.Tensor, N: int, first: int, frames: int, dev, what: str):
+    """The row stride of one side of a trial after the checks the device tables rely on: every row the kernel reads lies inside
+    the tensor."""
+    _require_gpu(t, what)
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"sensorium_amd.{what}: trials must be fp32 (got {t.dtype})")
+    if t.dim() != 2 or t.shape[0] != N or t.device != dev:
+        raise ValueError(f"sensorium_amd.{what}: a trial is an [N = {N}, L] tensor on {dev}, got {tuple(t.shape)} on {t.device}")
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise ValueError(f"sensorium_amd.{what}: frames must have unit stride (got {t.stride(1)})")
+    if frames < 1 or first < 0 or first + frames > t.shape[1]:
+        raise ValueError(f"sensorium_amd.{what}: frames [{first}, {first + frames}) are not inside a trial of length {t.shape[1]}")
+    ld = int(t.stride(0))
+    if ld < 0:
+        raise ValueError(f"sensorium_amd.{what}: negative row stride")
+    return ld
+
+
+def trial_moments(state: torch.Tensor, trials, groups, counts=(0, 0, 0)):
+    """dwn_trial_moments: merges trials into ``state`` (float64 ``[TRIAL_STATE_ROWS, N]``, zero before the first call) in place.
+    ``trials``: a sequence of ``(pred, target, first, frames)`` with ``pred`` / ``target`` GPU fp32 ``[N, L]`` tensors of unit
+    stride along frames and any row stride, of which the frames ``[first, first + frames)`` count; ``groups``: a sequence of
+    ``(first_trial, repeats, frames)`` that covers the trials in order (a trial that repeats nothing is a group of 1).
+    ``counts`` = ``(n_all, n_repeat, n_group_frames)`` of the state before the call; returns them after it.  Builds the two device
+    tables and launches; the tensors must stay alive until the launch has run (stream order)."""
+    _require_gpu(state, "trial_moments")
+    if state.dtype != torch.float64 or state.dim() != 2 or state.shape[0] != L.TRIAL_STATE_ROWS or not state.is_contiguous():
+        raise RuntimeError(f"sensorium_amd.trial_moments: state must be contiguous float64 [{L.TRIAL_STATE_ROWS}, N]")
+    dev, N = state.device, int(state.shape[1])
+    trials, groups = list(trials), list(groups)
+    if not trials or not groups:
+        raise ValueError("sensorium_amd.trial_moments: no trials")
+    td = np.zeros(len(trials), dtype=_TRIAL_DESC)
+    for i, (p, y, first, frames) in enumerate(trials):
+        first, frames = int(first), int(frames)
+        ldp = _trial_rows(p, N, first, frames, dev, "trial_moments")
+        ldy = _trial_rows(y, N, first, frames, dev, "trial_moments")
+        td[i] = (p.data_ptr(), y.data_ptr(), ldp, ldy, first, frames)
+    gd = np.zeros(len(groups), dtype=_TRIAL_GROUP)
+    n_all, n_rep, n_gf = (int(c) for c in counts)
+    at = 0
+    for i, (first_trial, repeats, frames) in enumerate(groups):
+        first_trial, repeats, frames = int(first_trial), int(repeats), int(frames)
+        if first_trial != at or repeats < 1 or at + repeats > len(trials):
+            raise ValueError(f"sensorium_amd.trial_moments: group {i} does not continue the trial table")
+        if any(int(td[k]["frames"]) != frames for k in range(at, at + repeats)):
+            raise ValueError(f"sensorium_amd.trial_moments: group {i}: its trials do not all have {frames} frames")
+        gd[i] = (first_trial, repeats, frames)
+        at += repeats
+        n_all += repeats * frames
+        if repeats >= 2:
+            n_rep += repeats * frames
+            n_gf += frames
+    if at != len(trials):
+        raise ValueError("sensorium_amd.trial_moments: the groups do not cover every trial")
+    tt = torch.from_numpy(td.view(np.uint8)).to(dev)
+    gt = torch.from_numpy(gd.view(np.uint8)).to(dev)
+    a = L.TrialScoreArgs()
+    a.N, a.n_trials, a.n_groups = N, len(trials), len(groups)
+    a.max_repeats, a.max_frames = int(gd["repeats"].max()), int(gd["frames"].max())
+    a.n_all, a.n_repeat, a.n_group_frames = (int(c) for c in counts)
+    a.trials, a.groups, a.state = tt.data_ptr(), gt.data_ptr(), state.data_ptr()
+    L.check(L.lib.dwn_trial_moments(C.byref(a), dev.index, _stream(dev)), "dwn_trial_moments")
+    return n_all, n_rep, n_gf
+
+
+def trial_scores(state: torch.Tensor, counts, eps: float = 1e-8, fev_threshold: float = 0.15):
+    """dwn_trial_score_finalize: ``(scores, summary)`` — float64 ``[TRIAL_SCORE_ROWS, N]`` (single_trial_corr, corr_to_average,
+    fev, feve, oracle_corr) and ``[TRIAL_SUMMARY]`` (include/dwn.h) — from the state and its counts.  No read-back."""
+    _require_gpu(state, "trial_scores")
+    if state.dtype != torch.float64 or state.dim() != 2 or state.shape[0] != L.TRIAL_STATE_ROWS or not state.is_contiguous():
+        raise RuntimeError(f"sensorium_amd.trial_scores: state must be contiguous float64 [{L.TRIAL_STATE_ROWS}, N]")
+    dev, N = state.device, int(state.shape[1])
+    scores = torch.empty(L.TRIAL_SCORE_ROWS, N, dtype=torch.float64, device=dev)
+    summary = torch.empty(L.TRIAL_SUMMARY, dtype=torch.float64, device=dev)
+    a = L.TrialScoreArgs()
+    a.N = N
+    a.n_all, a.n_repeat, a.n_group_frames = (int(c) for c in counts)
+    a.eps, a.fev_threshold = float(eps), float(fev_threshold)
+    ws = torch.empty(max(int(L.lib.dwn_trial_score_ws_bytes(C.byref(a))) // 8, 1), dtype=torch.float64, device=dev)
+    a.state, a.scores, a.summary, a.ws, a.ws_bytes = state.data_ptr(), scores.data_ptr(), summary.data_ptr(), ws.data_ptr(), ws.numel() * 8
+    L.check(L.lib.dwn_trial_score_finalize(C.byref(a), dev.index, _stream(dev)), "dwn_trial_score_finalize")
+    return scores, summary

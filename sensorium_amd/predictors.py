@@ -116,9 +116,10 @@ class Predictor:
 
     @torch.no_grad()
     def predict_trial(self, video, behavior=None, pupil_center=None, mouse_index: Optional[int] = None,
-                      num_neurons: Optional[int] = None) -> np.ndarray:
-        """Returns (N, L) fp32: every window ending at frame ``index`` adds its prediction to the frames it covers, and the
-        sum is divided by the accumulated blend weights (src/predictors.py:43-55; like the reference, the predictions themselves
+                      num_neurons: Optional[int] = None, to_numpy: bool = True):
+        """Returns (N, L) fp32 (``to_numpy=False``: the same values as the fp32 device tensor, without the copy to the host, as
+        sensorium_amd.evaluation consumes them): every window ending at frame ``index`` adds its prediction to the frames it covers,
+        and the sum is divided by the accumulated blend weights (src/predictors.py:43-55; like the reference, the predictions themselves
         are not multiplied by the blend weights).  Accumulation happens on the device, one pass per window position (frames
         are distinct within a pass: the blend itself is order-independent), one device-to-host copy per trial.
         Reproducibility: the eval forward is bit-reproducible from call to call — the SqueezeExcite pooling sums inside the
@@ -149,9 +150,9 @@ class Predictor:
                 counts.index_add_(0, idx[:, j], bw[j].expand(idx.shape[0]))
         if responses is None:
             n = num_neurons if num_neurons is not None else 0
-            return np.zeros((n, length), dtype=np.float32)
+            return np.zeros((n, length), dtype=np.float32) if to_numpy else torch.zeros(n, length, dtype=torch.float32, device=device)
         responses /= counts.clamp(min=1.0)
-        return responses.cpu().numpy()
+        return responses.cpu().numpy() if to_numpy else responses
 
     def _graph_forward(self, windows: torch.Tensor, mouse_index: int) -> torch.Tensor:
         key = (mouse_index, tuple(windows.shape), windows.dtype)

@@ -1,0 +1,320 @@
+"""The trial-score kernels through the C-ABI against the float64 checker tests/trial_score_reference.py, at
+the bounds DERIVED in its docstring (none was fitted to a measurement).  Every trial lies in a buffer of its own with an odd
+offset of the kept frames, an odd row stride (rows are 4-byte aligned only), different strides for prediction and target, and NaN
+everywhere outside the kept frames: a load outside them would show in every score.  Every test prints what it measured before it
+asserts (worst ratio to the bound)."""
+import ctypes as C
+import hashlib
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from tests import trial_score_cases as tc  # noqa: E402
+from tests import trial_score_reference as ref  # noqa: E402
+from tests.gpu_helpers import dev, stream  # noqa: E402
+
+EPS = 1e-8
+
+
+def layout(trials, poison=float("nan")):
+    """[(pred buffer, target buffer, first, frames)] on the device and the units [(first_trial, repeats, frames)] of the table."""
+    bufs, units = [], []
+    for i, (P, Y, g) in enumerate(trials):
+        N, K = P.shape
+        first = 1 + 2 * (i % 3)
+        ld = (first + K + 2 + (i % 2) * 4) | 1
+        sides = []
+        for x, stride in ((P, ld), (Y, ld + 2)):
+            b = torch.full((N, stride), poison, dtype=torch.float32)
+            b[:, first:first + K] = torch.from_numpy(np.ascontiguousarray(x))
+            sides.append(b.to(dev()))
+        bufs.append((sides[0], sides[1], first, K))
+        if g is not None and i > 0 and trials[i - 1][2] == g:
+            units[-1] = (units[-1][0], units[-1][1] + 1, K)
+        else:
+            units.append((i, 1, K))
+    return bufs, units
+
+
+def _device_table(array):
+    return torch.frombuffer(bytearray(bytes(array)), dtype=torch.uint8).to(dev())
+
+
+def run_moments(state, bufs, units, counts=(0, 0, 0)):
+    """dwn_trial_moments on the trials bufs / units; returns the advanced counts."""
+    import sensorium_amd._lib as L
+    descs = (L.TrialDesc * len(bufs))()
+    for d, (p, y, first, frames) in zip(descs, bufs):
+        d.pred, d.target, d.ld_pred, d.ld_target, d.first, d.frames = p.data_ptr(), y.data_ptr(), p.stride(0), y.stride(0), first, frames
+        assert first + frames <= p.shape[1] and first + frames <= y.shape[1] and p.stride(1) == 1 and y.stride(1) == 1
+    groups = (L.TrialGroup * len(units))()
+    base = units[0][0]
+    for gd, (first_trial, repeats, frames) in zip(groups, units):
+        gd.first_trial, gd.repeats, gd.frames = first_trial - base, repeats, frames
+    assert sum(u[1] for u in units) == len(bufs)
+    tt, gt = _device_table(descs), _device_table(groups)
+    a = L.TrialScoreArgs()
+    a.N, a.n_trials, a.n_groups = state.shape[1], len(bufs), len(units)
+    a.max_repeats, a.max_frames = max(u[1] for u in units), max(u[2] for u in units)
+    a.n_all, a.n_repeat, a.n_group_frames = counts
+    a.trials, a.groups, a.state = tt.data_ptr(), gt.data_ptr(), state.data_ptr()
+    rc = L.lib.dwn_trial_moments(C.byref(a), 0, stream())
+    assert rc == 0, L.lib.dwn_last_error()
+    n_all, n_rep, n_gf = counts
+    for _, R, K in units:
+        n_all += R * K
+        if R >= 2:
+            n_rep, n_gf = n_rep + R * K, n_gf + K
+    torch.cuda.synchronize()                     # the tables are freed on return
+    return n_all, n_rep, n_gf
+
+
+def run_finalize(state, counts, eps=EPS, thr=tc.FEV_THRESHOLD):
+    import sensorium_amd._lib as L
+    N = state.shape[1]
+    scores = torch.full((L.TRIAL_SCORE_ROWS, N), 7.0, dtype=torch.float64, device=dev())
+    summary = torch.full((L.TRIAL_SUMMARY,), 7.0, dtype=torch.float64, device=dev())
+    a = L.TrialScoreArgs()
+    a.N = N
+    a.n_all, a.n_repeat, a.n_group_frames = counts
+    a.eps, a.fev_threshold = eps, thr
+    ws = torch.empty(L.lib.dwn_trial_score_ws_bytes(C.byref(a)) // 8, dtype=torch.float64, device=dev())
+    a.state, a.scores, a.summary, a.ws, a.ws_bytes = state.data_ptr(), scores.data_ptr(), summary.data_ptr(), ws.data_ptr(), ws.numel() * 8
+    rc = L.lib.dwn_trial_score_finalize(C.byref(a), 0, stream())
+    assert rc == 0, L.lib.dwn_last_error()
+    torch.cuda.synchronize()
+    return scores, summary
+
+
+def gpu_run(trials, thr=tc.FEV_THRESHOLD, per_unit=False):
+    """(state, scores, summary, counts) of one case; per_unit: one launch per unit of the table instead of one for all."""
+    import sensorium_amd._lib as L
+    bufs, units = layout(trials)
+    state = torch.zeros(L.TRIAL_STATE_ROWS, trials[0][0].shape[0], dtype=torch.float64, device=dev())
+    counts = (0, 0, 0)
+    if per_unit:
+        for u in units:
+            counts = run_moments(state, bufs[u[0]:u[0] + u[1]], [u], counts)
+    else:
+        counts = run_moments(state, bufs, units, counts)
+    scores, summary = run_finalize(state, counts, thr=thr)
+    return state, scores, summary, counts
+
+
+def worst_ratio(got, want, bound):
+    """max |got - want| / bound over the entries with a finite bound; NaN must meet NaN there.  Entries without a bound (inf) are
+    left to the caller."""
+    got, want, bound = (np.asarray(x, dtype=np.float64) for x in (got, want, bound))
+    claim = np.isfinite(bound)
+    assert np.array_equal(np.isnan(got[claim]), np.isnan(want[claim])), (got, want)
+    ok = claim & ~np.isnan(want)
+    if not ok.any():
+        return 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(got[ok] == want[ok], 0.0, np.abs(got[ok] - want[ok]) / bound[ok])
+    return float(ratio.max())
+
+
+def check_case(trials, label, thr=tc.FEV_THRESHOLD, result=None):
+    """State at the moment bounds, scores at the score bounds, counts and summary; returns the worst ratios."""
+    state, scores, summary, counts = result if result is not None else gpu_run(trials, thr)
+    sc, st = ref.scores(trials, EPS), ref.moments(trials)
+    assert counts == (sc["n_all"], sc["n_repeat"], sc["n_group_frames"])
+    sb, bb = ref.state_bounds(trials, st), ref.score_bounds(trials, EPS)
+    r_state = worst_ratio(state.cpu().numpy(), st, sb)
+    got = scores.cpu().numpy()
+    r_score = {name: worst_ratio(got[i], sc[name], bb[name]) for i, name in enumerate(ref.SCORE_NAMES)}
+    print(f"trial_score {label}: counts {counts}, state {r_state:.3g} of its bound, scores "
+          + ", ".join(f"{k} {v:.3g}" for k, v in r_score.items()))
+    assert r_state <= 1.0, (label, r_state)
+    assert all(v <= 1.0 for v in r_score.values()), (label, r_score)
+    if not sc["n_repeat"]:
+        assert np.isnan(got[1:]).all()
+    # summary: plain means of rows 0, 1, 4 (their bound: the mean of the neurons' bounds plus the N-term float64 sum), the counts
+    s, want, N = summary.cpu().numpy(), ref.summary(sc, thr), got.shape[1]
+    assert s[5:].tolist() == [float(c) for c in counts]
+    for k, name in ((0, "single_trial_corr"), (1, "corr_to_average"), (2, "oracle_corr")):
+        if np.isfinite(bb[name]).all() and np.isfinite(want[k]):
+            assert abs(s[k] - want[k]) <= bb[name].mean() + (N + 2) * ref.U, (label, name, s[k], want[k])
+        else:
+            assert np.isnan(s[k]) == np.isnan(want[k]) or not np.isfinite(bb[name]).all()
+    return r_state, r_score
+
+
+@pytest.mark.parametrize("N", tc.NS)
+def test_every_shape_against_the_checker(N):
+    worst = 0.0
+    for K in tc.KS:
+        for R in tc.RS:
+            r_state, r_score = check_case(tc.shape_case(N, K, R), f"N={N} K={K} R={R}")
+            worst = max(worst, r_state, *r_score.values())
+    print(f"trial_score shapes N={N}: worst ratio to a derived bound {worst:.3g}")
+
+
+def test_mixed_table():
+    trials = tc.mixed_case()
+    bufs, units = layout(trials)
+    assert [u[1] for u in units] == [3, 1, 2, 1, 10, 1, 4] and [u[2] for u in units] == [65, 249, 1, 63, 64, 1, 130]
+    assert all(b[0].stride(0) % 2 == 1 and b[1].stride(0) == b[0].stride(0) + 2 and b[2] % 2 == 1 for b in bufs)
+    check_case(trials, "mixed")
+
+
+def test_hard_offsets():
+    """Values 10^6 + k/16: the centred float64 sums lose nothing, so the result sits far inside a bound that a raw sum of squares
+    breaks (tests/test_trial_score_reference_cpu.py shows the latter on the same data)."""
+    trials = tc.hard_case()
+    r_state, r_score = check_case(trials, "hard")
+    st = gpu_run(trials)[0].cpu().numpy()
+    want = ref.moments(trials)
+    rel = np.abs(st - want)[[2, 3, 4, 6, 7, 8, 11, 12, 13, 15, 16]] / np.abs(want[[3]])
+    print(f"trial_score hard: moments off by at most {rel.max():.3g} of M2y (state {r_state:.3g} of its bound)")
+
+
+def test_exact_integers_bit_for_bit():
+    trials = tc.exact_case()
+    state, scores, summary, counts = gpu_run(trials)
+    want = ref.moments(trials)
+    got = state.cpu().numpy()
+    print(f"trial_score exact: counts {counts}, rows that differ: {np.nonzero((got != want).any(axis=1))[0].tolist()}")
+    assert counts == (1024, 256, 128)
+    assert np.array_equal(got, want)
+    check_case(trials, "exact", result=(state, scores, summary, counts))
+
+
+def test_constant_target_neuron():
+    trials = tc.random_case(3, 6, [(3, 65), (1, 70), (2, 33)])
+    plain = gpu_run(trials)[1].cpu().numpy()
+    for _, y, _ in trials:
+        y[2] = 4.25
+    state, scores, summary, counts = gpu_run(trials)
+    got, st = scores.cpu().numpy(), state.cpu().numpy()
+    print(f"trial_score constant neuron: scores {got[:, 2].tolist()}, M2y {st[3, 2]}, SSwithin {st[8, 2]}")
+    assert st[1, 2] == 4.25 and st[3, 2] == 0 and st[6, 2] == 0 and st[8, 2] == 0 and st[15, 2] == 0 and st[4, 2] == 0
+    assert got[0, 2] == 0 and got[1, 2] == 0 and got[4, 2] == 0 and np.isnan(got[2, 2]) and np.isnan(got[3, 2])
+    other = [0, 1, 3, 4, 5]
+    assert np.array_equal(got[:, other], plain[:, other])                         # the neighbours are untouched, bit for bit
+    check_case(trials, "constant", result=(state, scores, summary, counts))
+    assert np.isfinite(summary.cpu().numpy()[:3]).all()
+
+
+def test_a_nan_stays_in_its_neuron():
+    trials = tc.random_case(4, 6, [(3, 65), (1, 70), (2, 33)])
+    plain = gpu_run(trials)
+    trials[1][1][3, 17] = np.nan                                                  # one frame of one repeat of neuron 3's target
+    state, scores, summary, _ = gpu_run(trials)
+    got = scores.cpu().numpy()
+    print(f"trial_score NaN: neuron 3 {got[:, 3].tolist()}, summary {summary.cpu().numpy()[:5].tolist()}")
+    assert np.isnan(got[:, 3]).all()
+    other = [0, 1, 2, 4, 5]
+    assert np.array_equal(got[:, other], plain[1].cpu().numpy()[:, other])
+    assert np.array_equal(state.cpu().numpy()[:, other], plain[0].cpu().numpy()[:, other])
+    s = summary.cpu().numpy()
+    assert np.isnan(s[:3]).all()                                                  # as corr(...).mean() in the reference
+    assert np.isfinite(s[3]) and s[4] == plain[2].cpu().numpy()[4] - (plain[1].cpu().numpy()[2, 3] >= tc.FEV_THRESHOLD)
+    # a NaN prediction in an ungrouped trial reaches the single-trial correlation only
+    trials = tc.random_case(4, 6, [(3, 65), (1, 70), (2, 33)])
+    trials[3][0][0, 5] = np.nan
+    got = gpu_run(trials)[1].cpu().numpy()
+    assert np.isnan(got[0, 0]) and np.isfinite(got[1:, 0]).all() and np.isfinite(got[:, 1:]).all()
+
+
+def test_streaming_gives_the_same_state_bit_for_bit():
+    """One launch per unit of the table merges the same group moments into the same running state in the same order as one launch
+    for all (the state passes through memory as float64, unchanged), so the bits agree by construction."""
+    for trials in (tc.mixed_case(), tc.hard_case(), tc.shape_case(5, 63, 1)):
+        a, b = gpu_run(trials), gpu_run(trials, per_unit=True)
+        same = torch.equal(a[0], b[0])
+        print(f"trial_score streaming: {len(trials)} trials, counts {b[3]}; state equal: {same}")
+        assert a[3] == b[3] and same and torch.equal(a[1].view(torch.int64), b[1].view(torch.int64))
+        assert torch.equal(a[2].view(torch.int64), b[2].view(torch.int64))
+
+
+def test_no_repeat_group():
+    trials = tc.random_case(9, 5, [(1, 65), (1, 1), (1, 249)])
+    trials[1] = (trials[1][0], trials[1][1], "seen once")                         # a group id seen once is no group
+    state, scores, summary, counts = gpu_run(trials)
+    got, s = scores.cpu().numpy(), summary.cpu().numpy()
+    assert counts == (315, 0, 0) and np.isnan(got[1:]).all() and np.isfinite(got[0]).all()
+    assert np.isnan(s[1:4]).all() and s[4] == 0 and np.isfinite(s[0])
+    assert float(state[5:].abs().max()) == 0.0
+    check_case(trials, "no repeats", result=(state, scores, summary, counts))
+
+
+def test_fev_threshold_mask():
+    trials, _ = tc.fev_case()
+    sc = ref.scores(trials, EPS)
+    TV, NV = np.asarray(sc["TV"], dtype=np.float64), np.asarray(sc["NV"], dtype=np.float64)
+    assert (np.abs(sc["fev"] - tc.FEV_THRESHOLD) > 1e-6).all() and (TV - NV >= 0.1 * TV).all()       # the checker's values first
+    state, scores, summary, counts = gpu_run(trials)
+    check_case(trials, "fev", result=(state, scores, summary, counts))
+    want, s, got = ref.summary(sc), summary.cpu().numpy(), scores.cpu().numpy()
+    bb = ref.score_bounds(trials, EPS)
+    assert bb["fev"].max() < 1e-6 and bb["kappa"].max() <= 10.0
+    mask = sc["fev"] >= tc.FEV_THRESHOLD
+    bound = bb["feve"][mask].mean() + (mask.sum() + 2) * ref.U * np.abs(sc["feve"][mask]).max()
+    print(f"trial_score fev mask: {int(s[4])} of {len(mask)} neurons at fev >= {tc.FEV_THRESHOLD} (checker {int(want[4])}), masked "
+          f"feve {s[3]:.15g} vs {want[3]:.15g}: {abs(s[3] - want[3]) / bound:.3g} of its bound")
+    assert s[4] == want[4] == mask.sum() and np.array_equal(got[2] >= tc.FEV_THRESHOLD, mask)
+    assert abs(s[3] - want[3]) <= bound
+    # other thresholds on the same state: everything, nothing
+    _, s_all = run_finalize(state, counts, thr=float("-inf"))
+    _, s_none = run_finalize(state, counts, thr=2.0)
+    assert s_all.cpu().numpy()[4] == len(mask) and s_none.cpu().numpy()[4] == 0 and np.isnan(s_none.cpu().numpy()[3])
+
+
+def test_python_layer_builds_the_same_tables():
+    """sensorium_amd.ops / TrialScorer on the buffers of the mixed case: the same bits as the hand-built tables, trials added in a
+    shuffled order that keeps first appearances, flushed in three parts."""
+    from sensorium_amd import ops
+    from sensorium_amd.evaluation import FrameCut, TrialScorer
+    trials = tc.mixed_case()
+    state, scores, summary, counts = gpu_run(trials)
+    bufs, units = layout(trials)
+    scorer = TrialScorer(67, dev(), cut=FrameCut())
+    views = [(p[:, first:first + K], y[:, first:first + K]) for p, y, first, K in bufs]
+    cuts = (0, 4, 7, len(trials))                                                  # flushes at unit boundaries
+    for lo, hi in zip(cuts, cuts[1:]):
+        for i in range(lo, hi):
+            scorer.add(views[i][0], views[i][1], group=trials[i][2])
+        scorer.flush()
+    res = scorer.compute()
+    assert scorer.counts == counts and torch.equal(scorer.state, state)
+    assert torch.equal(res.scores.view(torch.int64), scores.view(torch.int64))
+    smr = res.summary()
+    assert smr["n_all"] == counts[0] and smr["n_feve_neurons"] == int(summary[4]) and smr["single_trial_corr"] == float(summary[0])
+    assert torch.equal(res.oracle_corr, scores[4]) and res.reliable(0.3).dtype == torch.int64 and res.reliable(0.3).is_cuda
+    assert res.reliable(0.3).tolist() == np.nonzero(scores[4].cpu().numpy() >= 0.3)[0].tolist()
+    with pytest.raises(ValueError, match="already flushed"):
+        scorer.add(views[0][0], views[0][1], group=trials[0][2])
+    # the cut as an offset: the scorer's FrameCut on the whole buffers of trials whose kept frames it selects
+    p, y, first, K = bufs[1]
+    one = TrialScorer(67, dev(), cut=FrameCut(first, first + K + 1, 1))
+    one.add(p, y)
+    st = torch.zeros_like(state)
+    ops.trial_moments(st, [(p, y, first, K)], [(0, 1, K)])
+    one.flush()
+    assert torch.equal(one.state, st) and one.counts == (K, 0, 0)
+    for bad in ([(0, 2, K)], [(0, 1, K), (0, 1, K)], [(0, 1, K - 1)], [(1, 1, K)], [(0, 0, K)], []):
+        with pytest.raises(ValueError):
+            ops.trial_moments(st, [(p, y, first, K)], bad)
+    with pytest.raises(ValueError, match="not inside"):
+        ops.trial_moments(st, [(p, y, first, p.shape[1])], [(0, 1, p.shape[1])])
+
+
+def trial_score_digest():
+    """sha256 over state, scores and summary of the fixed cases (tests/test_gpu_trial_score_det.py, tests/det_trial_score_worker.py)."""
+    h, n = hashlib.sha256(), 0
+    for trials in (tc.mixed_case(), tc.hard_case(), tc.fev_case()[0]):
+        for t in gpu_run(trials)[:3]:
+            h.update(t.cpu().numpy().tobytes())
+            n += 1
+    return n, h.hexdigest()
+
+
+def test_two_launches_agree_bit_for_bit():
+    a, b = trial_score_digest(), trial_score_digest()
+    print(f"trial_score digest of {a[0]} tensors: {a[1]}")
+    assert a == b
