@@ -898,6 +898,46 @@ size_t dwn_trial_score_ws_bytes(const dwn_trial_score_args* a);
 int dwn_trial_moments(const dwn_trial_score_args* a, int device, void* stream);
 int dwn_trial_score_finalize(const dwn_trial_score_args* a, int device, void* stream);
 
+/* ---- retinotopic readout gain: a per-neuron gain on a readout's output, driven by the core map sampled at the
+ * neuron's own learned position.  y, out, dout, dy: [B][N][T] fp32 contiguous; g: [B][T][Hf][Wf][K] channels-last in g_dtype
+ * (DWN_F32 / DWN_BF16); dg: the same shape, always fp32; pos, dpos: [N][2] = (x, y) in normalised coordinates (-1 / +1 are the
+ * centres of the first / last cell); weight, dweight: [N][K]; bias, dbias: [N]; m = max_log_gain.
+ *   px = (clamp(x, -1, 1) + 1) / 2 * (Wf - 1),  x0 = min(floor(px), max(Wf - 2, 0)),  fx = px - x0,  x1 = min(x0 + 1, Wf - 1)
+ *   (y likewise with Hf);  w00 = (1-fy)(1-fx), w01 = (1-fy) fx, w10 = fy (1-fx), w11 = fy fx       (fp32, each product rounded once)
+ *   d_c[b,n,t] = sum_k G[b,t,cell_c,k] weight[n,k]        (fp32 FMAs, k ascending, from 0; c = 00, 01, 10, 11)
+ *   a          = bias[n] + w00 d00 + w01 d01 + w10 d10 + w11 d11                     (4 FMAs in that order, from bias[n])
+ *   out        = y exp(m tanh(a))
+ * which is F.grid_sample(bilinear, border, align_corners=True) followed by the behaviour modulator's gain.  Backward:
+ *   dy = dout gain,  s = dout y gain m sech^2(a)  (sech^2 = 4 e / (1 + e)^2, e = exp(-2 |a|)),
+ *   dbias[n] = sum_{b,t} s,  dweight[n,k] = sum_{b,t} s samp[k],  samp[k] = sum_c w_c G[b,t,cell_c,k],
+ *   dpos[n,0] = (Wf - 1)/2 sum_{b,t} s ((1-fy)(d01 - d00) + fy (d11 - d10)),  dpos[n,1] likewise with Hf and fx,
+ *   dg[b,t,cell,k] = sum over the neurons n one of whose corners c is `cell`, n ascending, of s w_c weight[n,k].
+ * A coordinate strictly outside [-1, 1] is clamped and its dpos entry is exactly 0 (the other coordinate stays live); a one-cell
+ * axis (Hf = 1 or Wf = 1) has a zero position gradient.  One decision per neuron: cells, weights and flags are derived once per call
+ * (the backward writes them into ws and every pass reads that table; the neurons of every cell are bucketed from it, in index order).  The sums over (b, t) run in float64 through per-workgroup
+ * partials in ws and a fixed-order finaliser and are rounded to fp32 once; dg is a float64 sum in ascending neuron order rounded
+ * once, written for every cell (exact zeros where no neuron reaches).  No atomics: the same inputs give the same bits, in both
+ * builds.  A null dy / dg / dpos / dweight / dbias is skipped, and its partials are neither computed nor stored.
+ * A neuron whose position holds a NaN or an Inf gets NaN in its rows of out and dy and in its dweight, dbias and dpos, is left out
+ * of dg, and leaves every other neuron's results bit for bit what they are without it.  weight = bias = 0 returns y (and dout in
+ * dy) bit for bit.  dwn_spatial_gain_forward needs y, g, pos, weight, bias, out (out must not alias y) and no workspace.
+ * dwn_spatial_gain_backward needs y, g, pos, weight, bias, dout, ws (dwn_spatial_gain_ws_bytes(a) bytes, 16-byte aligned; it depends
+ * on the sizes B, N, T, Hf * Wf, K alone) and at least one of dy, dg, dpos, dweight, dbias.  Nothing is allocated and nothing is read back: both
+ * entries can be captured.  Argument errors are answered before the device is entered: null pointer -1; a non-positive size, K
+ * outside [1, 64], Hf * Wf > 256, a g_dtype that is neither DWN_F32 nor DWN_BF16, a max_log_gain that is not finite and positive,
+ * out == y, or a workspace that is too small or misaligned -2. */
+typedef struct dwn_spatial_gain_args {
+    int B, N, T, Hf, Wf, K;
+    int g_dtype; float max_log_gain;
+    const float* y; const void* g; const float* pos; const float* weight; const float* bias;
+    float* out;
+    const float* dout; float* dy; float* dg; float* dpos; float* dweight; float* dbias;
+    void* ws; size_t ws_bytes;
+} dwn_spatial_gain_args;
+size_t dwn_spatial_gain_ws_bytes(const dwn_spatial_gain_args* a);   /* backward only; forward needs none; 0 for refused arguments */
+int dwn_spatial_gain_forward(const dwn_spatial_gain_args* a, int device, void* stream);
+int dwn_spatial_gain_backward(const dwn_spatial_gain_args* a, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

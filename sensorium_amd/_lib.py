@@ -241,6 +241,12 @@ class TrialScoreArgs(C.Structure):        # (include/dwn.h dwn_trial_score_args)
                 ("trials", c_p), ("groups", c_p), ("state", c_p), ("scores", c_p), ("summary", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
 
 
+class SpatialGainArgs(C.Structure):       # retinotopic readout gain (include/dwn.h dwn_spatial_gain_args)
+    _fields_ = [("B", c_i), ("N", c_i), ("T", c_i), ("Hf", c_i), ("Wf", c_i), ("K", c_i), ("g_dtype", c_i), ("max_log_gain", c_f),
+                ("y", c_p), ("g", c_p), ("pos", c_p), ("weight", c_p), ("bias", c_p), ("out", c_p), ("dout", c_p), ("dy", c_p),
+                ("dg", c_p), ("dpos", c_p), ("dweight", c_p), ("dbias", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
+
+
 CORR_STAT_ROWS, CORR_TILE = 8, 16          # DWN_CORR_STAT_ROWS, DWN_CORR_TILE
 CORR_MEAN, CORR_SUM = 0, 1
 GABOR_GAUSSIAN, GABOR_NONE = 0, 1          # DWN_GABOR_*
@@ -263,6 +269,7 @@ _STRUCTS = {
     "dwn_corr_args": CorrArgs, "dwn_gabor_args": GaborArgs, "dwn_modulator_args": ModulatorArgs,
     "dwn_blur3d_args": Blur3dArgs, "dwn_clip_moments_args": ClipMomentsArgs, "dwn_mei_update_args": MeiUpdateArgs,
     "dwn_trial_desc": TrialDesc, "dwn_trial_group": TrialGroup, "dwn_trial_score_args": TrialScoreArgs,
+    "dwn_spatial_gain_args": SpatialGainArgs,
 }
 
 # every symbol include/dwn.h declares: (restype, argtypes)
@@ -346,6 +353,9 @@ SYMBOLS = {
     "dwn_trial_score_ws_bytes": (c_sz, [_P(TrialScoreArgs)]),
     "dwn_trial_moments": (c_i, [_P(TrialScoreArgs), c_i, c_p]),
     "dwn_trial_score_finalize": (c_i, [_P(TrialScoreArgs), c_i, c_p]),
+    "dwn_spatial_gain_ws_bytes": (c_sz, [_P(SpatialGainArgs)]),
+    "dwn_spatial_gain_forward": (c_i, [_P(SpatialGainArgs), c_i, c_p]),
+    "dwn_spatial_gain_backward": (c_i, [_P(SpatialGainArgs), c_i, c_p]),
 }
 
 
@@ -356,8 +366,8 @@ class DwnError(RuntimeError):
 # csrc/Makefile HASH_SRCS, in its order
 HASH_SRCS = ("dwn_api.hip", "dwn_gemm.hip", "dwn_gemm_nn_1.hip", "dwn_gemm_nn_2.hip", "dwn_gemm_nn_3.hip", "dwn_gemm_nn_4.hip", "dwn_gemm_nn_5.hip",
              "dwn_gemm_nn_6.hip", "dwn_gemm_tn.hip", "dwn_pw_bwd.hip", "dwn_gemm_xl.hip", "dwn_gemm_kd.hip", "dwn_dwconv.hip", "dwn_dwrc.hip",
-             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_mei.hip", "dwn_trial_score.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
-             "dwn_kernels.h", "dwn_launch.h", "dwn_gemm_nn.h",
+             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_spatial.hip", "dwn_mei.hip", "dwn_trial_score.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
+             "dwn_kernels.h", "dwn_launch.h", "dwn_gemm_nn.h", "dwn_gain.h",
              "../../include/dwn.h")
 
 
@@ -385,8 +395,9 @@ def _load():
                            "dwn_gabor_backward", "dwn_modulator_ws_bytes", "dwn_modulator_forward",
                            "dwn_modulator_backward", "dwn_blur3d_ws_bytes", "dwn_clip_moments_ws_bytes", "dwn_blur3d",
                            "dwn_clip_moments", "dwn_mei_update", "dwn_trial_score_ws_bytes", "dwn_trial_moments",
-                           "dwn_trial_score_finalize") and not hasattr(lib, name):
-            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator / the MEI kernels / the trial scores; the plain training step calls none of them)
+                           "dwn_trial_score_finalize", "dwn_spatial_gain_ws_bytes", "dwn_spatial_gain_forward",
+                           "dwn_spatial_gain_backward") and not hasattr(lib, name):
+            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator / the MEI kernels / the trial scores / the retinotopic readout gain; the plain training step calls none of them)
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -398,7 +409,7 @@ def _load():
                           f"`make -C {LIB_PATH.parent}` — binaries are not in git, so what runs must be what is committed")
     for cname, struct in _STRUCTS.items():
         n = lib.dwn_sizeof(cname.encode())
-        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args", "dwn_blur3d_args", "dwn_clip_moments_args", "dwn_mei_update_args", "dwn_trial_desc", "dwn_trial_group", "dwn_trial_score_args"))):      # (A/B: ABI 7 only appended)
+        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args", "dwn_blur3d_args", "dwn_clip_moments_args", "dwn_mei_update_args", "dwn_trial_desc", "dwn_trial_group", "dwn_trial_score_args", "dwn_spatial_gain_args"))):      # (A/B: ABI 7 only appended)
             raise ImportError(f"struct layout mismatch for {cname}: C {n} bytes vs ctypes {C.sizeof(struct)}")
     return lib
 

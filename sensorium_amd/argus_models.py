@@ -31,6 +31,7 @@ from .losses import MiceCorrelationLoss, MicePoissonCorrelationLoss, MicePoisson
 from .optim import FusedAdamWEma
 from .modulator import DwiseNeuroBehavior
 from .shifter import DwiseNeuroGaze
+from .spatial import DwiseNeuroSpatial
 
 
 def deep_to(obj, device, non_blocking: bool = False):
@@ -79,7 +80,8 @@ def fill_distill_targets(distill_prediction, target, distill_ratio: float):
 class MouseModel(Model):
     """``fit`` / ``validate`` / ``save`` come from ``engine.Model`` (the argus surface train.py:141-145 uses);
     ``load_model`` finds this class by the ``model_name`` stored in the checkpoint."""
-    nn_module = {"dwiseneuro": DwiseNeuro, "dwiseneuro_gaze": DwiseNeuroGaze, "dwiseneuro_behavior": DwiseNeuroBehavior}
+    nn_module = {"dwiseneuro": DwiseNeuro, "dwiseneuro_gaze": DwiseNeuroGaze, "dwiseneuro_behavior": DwiseNeuroBehavior,
+                 "dwiseneuro_spatial": DwiseNeuroSpatial}
     loss = {"mice_poisson": MicePoissonLoss, "mice_correlation": MiceCorrelationLoss,
             "mice_poisson_correlation": MicePoissonCorrelationLoss}
     optimizer = {"AdamW": FusedAdamWEma}
@@ -170,7 +172,9 @@ class MouseModel(Model):
                 self._model_ema.set(self.nn_module)
         # learnable Softplus beta: a group of its own without weight decay (decoupled decay would pull beta towards 0 all run
         # long), lr / betas as everybody's; params["softplus_optimizer"] overrides.  Without such parameters: one group, as ever
+        # the retinotopic positions (DwiseNeuroSpatial) join that group: decay would pull every neuron towards the screen's centre
         soft = [p for p in getattr(self.nn_module, "softplus_parameters", list)() if p.requires_grad]
+        soft += [p for p in getattr(self.nn_module, "position_parameters", list)() if p.requires_grad]
         if soft:
             ids = {id(p) for p in soft}
             params = [{"params": [p for p in params if id(p) not in ids]},

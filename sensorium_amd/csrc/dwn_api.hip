@@ -308,7 +308,7 @@ int dwn_sizeof(const char* name) {
     SZ(dwn_stem_args); SZ(dwn_block_args); SZ(dwn_pool_args); SZ(dwn_cortex_args); SZ(dwn_readout_args);
     SZ(dwn_tensor_entry); SZ(dwn_clip_src); SZ(dwn_clip_desc); SZ(dwn_pw_bwd_args); SZ(dwn_dw_spatial_rc_fwd_args);
     SZ(dwn_stem_input_grad_args); SZ(dwn_guarded_entry); SZ(dwn_step_guard); SZ(dwn_gaze_args);
-    SZ(dwn_corr_args); SZ(dwn_gabor_args); SZ(dwn_modulator_args);
+    SZ(dwn_corr_args); SZ(dwn_gabor_args); SZ(dwn_modulator_args); SZ(dwn_spatial_gain_args);
     SZ(dwn_blur3d_args); SZ(dwn_clip_moments_args); SZ(dwn_mei_update_args);
     SZ(dwn_trial_desc); SZ(dwn_trial_group); SZ(dwn_trial_score_args);
 #undef SZ
@@ -1440,6 +1440,45 @@ int dwn_trial_score_finalize(const dwn_trial_score_args* a, int device, void* st
     if (a->ws_bytes < k_trial_score_ws_bytes(a->N) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "trial_score_finalize: workspace smaller than dwn_trial_score_ws_bytes or not 8-byte aligned");
     ENTER(device);
     return k_trial_score_finalize(*a, (hipStream_t)stream);
+}
+
+// ---- retinotopic readout gain: the argument checks need no device
+static int spatial_gain_geometry(const dwn_spatial_gain_args* a) {
+    if (a->B <= 0 || a->N <= 0 || a->T <= 0 || a->Hf <= 0 || a->Wf <= 0) return dwn_set_error(-2, "spatial_gain: B, N, T, Hf, Wf must be positive");
+    if (a->K < 1 || a->K > 64) return dwn_set_error(-2, "spatial_gain: K outside [1, 64]");
+    if ((long long)a->Hf * a->Wf > 256) return dwn_set_error(-2, "spatial_gain: Hf * Wf above 256");
+    if (a->g_dtype != DWN_F32 && a->g_dtype != DWN_BF16) return dwn_set_error(-2, "spatial_gain: g_dtype must be DWN_F32 or DWN_BF16");
+    if (!(a->max_log_gain > 0.f) || !(a->max_log_gain <= 3.402823466e38f)) return dwn_set_error(-2, "spatial_gain: max_log_gain must be finite and positive");
+    // one workgroup per (128 neurons, 32 frames, sample) and one wave per (sample, cell, 32 frames; bounded here as if 16): keep the grids below 2^31
+    const long long tiles = ((long long)a->N + 127) / 128 * (((long long)a->T + 31) / 32) * a->B;
+    const long long waves = (long long)a->B * a->Hf * a->Wf * (((long long)a->T + 15) / 16);
+    if (tiles >= (1ll << 31) || waves >= (1ll << 31) || (long long)a->N * a->K >= (1ll << 31))
+        return dwn_set_error(-2, "spatial_gain: more than 2^31 tiles or weights");
+    return 0;
+}
+size_t dwn_spatial_gain_ws_bytes(const dwn_spatial_gain_args* a) {
+    if (!a || spatial_gain_geometry(a) != 0) { g_err[0] = 0; return 0; }
+    return k_spatial_gain_ws_bytes(*a);
+}
+int dwn_spatial_gain_forward(const dwn_spatial_gain_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "spatial_gain_forward: null arguments");
+    TRY(spatial_gain_geometry(a));
+    if (!a->y || !a->g || !a->pos || !a->weight || !a->bias || !a->out) return dwn_set_error(-1, "spatial_gain_forward: null pointer (y, g, pos, weight, bias, out)");
+    if (a->out == a->y) return dwn_set_error(-2, "spatial_gain_forward: out must not alias y");
+    ENTER(device);
+    return k_spatial_gain_forward(*a, (hipStream_t)stream);
+}
+int dwn_spatial_gain_backward(const dwn_spatial_gain_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "spatial_gain_backward: null arguments");
+    TRY(spatial_gain_geometry(a));
+    if (!a->y || !a->g || !a->pos || !a->weight || !a->bias || !a->dout) return dwn_set_error(-1, "spatial_gain_backward: null pointer (y, g, pos, weight, bias, dout)");
+    if (!a->dy && !a->dg && !a->dpos && !a->dweight && !a->dbias) return dwn_set_error(-1, "spatial_gain_backward: dy, dg, dpos, dweight and dbias are all null");
+    if (!a->ws) return dwn_set_error(-1, "spatial_gain_backward: null pointer (ws)");
+    if (a->ws_bytes < k_spatial_gain_ws_bytes(*a) || ((size_t)a->ws & 15)) return dwn_set_error(-2, "spatial_gain_backward: workspace smaller than dwn_spatial_gain_ws_bytes or not 16-byte aligned");
+    ENTER(device);
+    return k_spatial_gain_backward(*a, (hipStream_t)stream);
 }
 
 }  // extern "C"

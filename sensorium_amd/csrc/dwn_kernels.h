@@ -143,6 +143,10 @@ int k_trial_score_finalize(const dwn_trial_score_args& a, hipStream_t s);   // s
 size_t k_modulator_ws_bytes(const dwn_modulator_args& a);
 int k_modulator_forward(const dwn_modulator_args& a, hipStream_t s);
 int k_modulator_backward(const dwn_modulator_args& a, hipStream_t s);      // a.dy, a.dh, a.du, a.dc: each may be null
+// retinotopic readout gain (dwn.h dwn_spatial_gain_args; dwn_spatial.hip): arguments checked by the C-ABI layer
+size_t k_spatial_gain_ws_bytes(const dwn_spatial_gain_args& a);
+int k_spatial_gain_forward(const dwn_spatial_gain_args& a, hipStream_t s);
+int k_spatial_gain_backward(const dwn_spatial_gain_args& a, hipStream_t s); // a.dy, a.dg, a.dpos, a.dweight, a.dbias: each may be null
 int k_pw_bwd_prep(const float* w1, const float* abc, int E, int C, void* bp, float* gacc, float* r3, int dtype,
                   const float* res_abc, int res_C, hipStream_t s);
 // conv_pw weight gradient from the raw products (see pw_bwd_fused_kernel): tacc [(E + C + 8)][C] fp32 = rows T1 = dh1^T a0,

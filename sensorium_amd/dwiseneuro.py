@@ -426,6 +426,14 @@ class DwiseNeuro(nn.Module):
         """core -> pool -> cortex; returns channels-last [B, T, C] features in the compute dtype.
         ``mode_from``: the tensor the eval-mode BatchNorm decision is taken from when ``x`` is not the caller's input but
         something computed from it (a learned front end: ``DwiseNeuroGaze``); ``None`` = ``x`` itself."""
+        return self._trunk(x, mode_from, False)
+
+    def trunk_with_map(self, x: torch.Tensor, mode_from: Optional[torch.Tensor] = None):
+        """``trunk`` that also returns the core's output map [B, T, h, w, C] (channels-last, compute dtype), the tensor the pool
+        averages: ``(features, core_map)``.  For a second consumer of the map (``DwiseNeuroSpatial``); the launches are ``trunk``'s."""
+        return self._trunk(x, mode_from, True)
+
+    def _trunk(self, x: torch.Tensor, mode_from: Optional[torch.Tensor], return_map: bool):
         if x.dim() != 5:
             raise RuntimeError("DwiseNeuro expects (batch, channel, time, height, width)")
         if self.training:
@@ -437,9 +445,10 @@ class DwiseNeuro(nn.Module):
             ops.L.BN_FROZEN if ops.wants_frozen(x if mode_from is None else mode_from,
                                                 getattr(self, "bn_frozen_finetune", False)) else ops.L.BN_EVAL)
         with ops.bn_mode_scope(mode):
-            x = self.core(x, dtype)                               # [B,T,h,w,C]
-            x = ops.PoolFn.apply(x)                               # [B,T,C]
-            return self.cortex(x, dtype)
+            core_map = self.core(x, dtype)                        # [B,T,h,w,C]
+            x = ops.PoolFn.apply(core_map)                        # [B,T,C]
+            feats = self.cortex(x, dtype)
+        return (feats, core_map) if return_map else feats
 
     def forward(self, x: torch.Tensor, index: Optional[int] = None):
         feats = self.trunk(x)

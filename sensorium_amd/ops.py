@@ -1204,3 +1204,68 @@ def trial_scores(state: torch.Tensor, counts, eps: float = 1e-8, fev_threshold: 
     a.state, a.scores, a.summary, a.ws, a.ws_bytes = state.data_ptr(), scores.data_ptr(), summary.data_ptr(), ws.data_ptr(), ws.numel() * 8
     L.check(L.lib.dwn_trial_score_finalize(C.byref(a), dev.index, _stream(dev)), "dwn_trial_score_finalize")
     return scores, summary
+
+
+# ------------------------------------------------------------------------------------------------
+# retinotopic readout gain (sensorium_amd/spatial.py)
+# ------------------------------------------------------------------------------------------------
+def _spatial_gain_args(y, g, pos, weight, bias, max_log_gain: float) -> L.SpatialGainArgs:
+    a = L.SpatialGainArgs()
+    a.B, a.N, a.T = (int(n) for n in y.shape)
+    a.Hf, a.Wf, a.K = (int(n) for n in g.shape[2:])
+    a.g_dtype = _DT[g.dtype]
+    a.max_log_gain = float(max_log_gain)
+    a.y = y.data_ptr(); a.g = g.data_ptr(); a.pos = pos.data_ptr(); a.weight = weight.data_ptr(); a.bias = bias.data_ptr()
+    return a
+
+
+class SpatialGainFn(torch.autograd.Function):
+    """``SpatialGainFn.apply(y, g, pos, weight, bias, max_log_gain) -> y * exp(max_log_gain * tanh(bias[n] + weight[n,:] .
+    sample(g[b,t], pos[n])))`` for a readout's output ``y`` [B][N][T], a channels-last map ``g`` [B][T][Hf][Wf][K] in fp32 or bf16,
+    the per-neuron positions ``pos`` [N][2] = (x, y) in [-1, 1], weights [N][K] and offsets [N] (include/dwn.h
+    dwn_spatial_gain_args).  ``sample`` is ``grid_sample(bilinear, border, align_corners=True)``.  The backward asks the kernels only
+    for the gradients autograd needs; the map's gradient is a fixed-order float64 sum in fp32, cast to the map's dtype here."""
+
+    @staticmethod
+    def forward(ctx, y, g, pos, weight, bias, max_log_gain=1.0):
+        for t in (y, g, pos, weight, bias):
+            _require_gpu(t, "SpatialGainFn")
+        if y.dim() != 3 or g.dim() != 5 or g.shape[:2] != (y.shape[0], y.shape[2]) or pos.shape != (y.shape[1], 2) \
+                or weight.shape != (y.shape[1], g.shape[4]) or bias.shape != (y.shape[1],):
+            raise RuntimeError("sensorium_amd.SpatialGainFn: y must be [B][N][T], g [B][T][Hf][Wf][K], pos [N][2], weight [N][K] "
+                               "and bias [N]")
+        if g.dtype not in _DT:
+            raise RuntimeError("sensorium_amd.SpatialGainFn: the map must be fp32 or bf16")
+        y = y.contiguous().float(); g = g.contiguous()
+        pos = pos.contiguous().float(); weight = weight.contiguous().float(); bias = bias.contiguous().float()
+        dev = y.device
+        out = torch.empty_like(y)
+        a = _spatial_gain_args(y, g, pos, weight, bias, max_log_gain)
+        a.out = out.data_ptr()
+        L.check(L.lib.dwn_spatial_gain_forward(C.byref(a), dev.index, _stream(dev)), "dwn_spatial_gain_forward")
+        ctx.max_log_gain = float(max_log_gain)
+        ctx.save_for_backward(y, g, pos, weight, bias)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        y, g, pos, weight, bias = ctx.saved_tensors
+        need = ctx.needs_input_grad[:5]
+        if not any(need):
+            return None, None, None, None, None, None
+        dev = dout.device
+        dout = dout.contiguous().float()
+        dy, dpos, dweight, dbias = (torch.empty_like(t) if n else None
+                                    for t, n in zip((y, pos, weight, bias), (need[0], need[2], need[3], need[4])))
+        dg = torch.empty(g.shape, dtype=torch.float32, device=dev) if need[1] else None
+        a = _spatial_gain_args(y, g, pos, weight, bias, ctx.max_log_gain)
+        nbytes = L.lib.dwn_spatial_gain_ws_bytes(C.byref(a))
+        ws = torch.empty(max(int(nbytes), 16) // 8, dtype=torch.float64, device=dev)
+        a.dout = dout.data_ptr(); a.dy = _ptr(dy); a.dg = _ptr(dg); a.dpos = _ptr(dpos); a.dweight = _ptr(dweight)
+        a.dbias = _ptr(dbias)
+        a.ws = ws.data_ptr(); a.ws_bytes = ws.numel() * 8
+        L.check(L.lib.dwn_spatial_gain_backward(C.byref(a), dev.index, _stream(dev)), "dwn_spatial_gain_backward")
+        if dg is not None and dg.dtype != g.dtype:
+            dg = dg.to(g.dtype)
+        return dy, dg, dpos, dweight, dbias, None
