@@ -938,6 +938,87 @@ size_t dwn_spatial_gain_ws_bytes(const dwn_spatial_gain_args* a);   /* backward 
 int dwn_spatial_gain_forward(const dwn_spatial_gain_args* a, int device, void* stream);
 int dwn_spatial_gain_backward(const dwn_spatial_gain_args* a, int device, void* stream);
 
+/* ---- receptive-field mapping: a counter-based noise stimulus, the lagged stimulus/response cross-sums of a
+ * batch, and the maps they give.
+ *
+ * dwn_noise_forward: x, out [B][Cin][T][H][W] fp32 contiguous.  Channel `video_channel` is rendered, every other channel is copied
+ * from x bit for bit.  The window (y0, x0, wh, ww) — always explicit — holds gh x gw = (wh / cell) x (ww / cell) cells; cell
+ * q = gy gw + gx of frame t of clip b takes word q & 3 of
+ *   philox4x32-10(counter = (q >> 2, t / hold, first_clip + b, 0), key = (seed & 0xffffffff, seed >> 32))
+ * (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85; round c' = (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2),
+ * hi(M0 c0) ^ c3 ^ k1, lo(M0 c0))).  DWN_NOISE_BINARY: top bit set -> background + contrast, else background - contrast.
+ * DWN_NOISE_SPARSE: thr = floor(density 2^31); word < thr -> background - contrast, word >= 2^32 - thr -> background + contrast,
+ * else background.  The three values are formed once in fp32 and never clamped; pixels outside the window hold `pad`.  A clip
+ * depends on (seed, first_clip + b) alone.  Needs x, out.
+ *
+ * dwn_sta_accumulate: x [B][Cin][T][H][W] fp32 (any stimulus), r [B][N][T] fp32, r0 [N] fp32 or NULL (zeros).  With G = gh gw,
+ *   u[b,n,t] = r[b,n,t] - r0[n]                                                     (fp32)
+ *   v[b,t,g] = (sum of the cell's pixels of channel `channel`, fp32, row-major) * (1 / cell^2) - s0    (each step rounded)
+ *   t0 = max(skip, lags - 1);   for t in [t0, T):
+ *   Cuv[n][l][g] += sum_b sum_t u[b,n,t] v[b,t-l,g]      (an fp32 fma chain over (b, t) ascending, converted once, added in float64)
+ *   U1[n] += sum u, U2[n] += sum u^2;  V1[l][g] += sum v[b,t-l,g], V2[l][g] += sum v^2      (float64 sums in a fixed order)
+ * state: double, zero before the first call: Cuv [N][lags][G], then U1 [N], U2 [N], V1 [lags][G], V2 [lags][G]
+ * (dwn_sta_state_bytes(a) bytes, 8-byte aligned).  Every element has one owner and a fixed order: no atomics, no scratch, the same
+ * bits on every launch and in both builds.  The caller advances its sample count by B (T - t0) per call.  A non-finite response of
+ * a neuron reaches only that neuron's rows and its U1 / U2; a non-finite pixel only that cell's columns and its V1 / V2.
+ * Needs x, r, state.
+ *
+ * dwn_sta_finalize: with K = samples (> 0), per (n, l, g) in float64
+ *   cov = (Cuv - U1 (V1 / K)) / K,   var_u = (U2 - U1 (U1 / K)) / K,   var_v = (V2 - V1 (V1 / K)) / K,
+ *   z = cov sqrt(K) / sqrt(var_u var_v), 0 where either variance is <= 0;
+ * cov, z: fp32 [N][lags][gh][gw] (z may be NULL).  summary: double [N][DWN_STA_SUMMARY]:
+ *   0 peak lag l* = argmax_l E_l, E_l = sum_g cov^2 (lowest lag wins a tie)   1 z at the argmax-|cov| cell of l* (lowest index wins)
+ *   2, 3 cy, cx: centroid in cell units, weights cov^2, over the cells of l* with |cov| >= rel_threshold max_g |cov|
+ *   4, 5 sy, sx: weighted standard deviations about it   6 E_l* / sum_l E_l   7 the number of cells kept
+ * A neuron whose sum_l E_l is not positive gets lag 0, z 0, NaN in columns 2-5, share 0 and count 0.  One wave per neuron, the
+ * lanes' partials added by a fixed butterfly; V1 / K and var_v are formed once into ws (dwn_sta_ws_bytes(a) bytes, 8-byte
+ * aligned) by a launch of their own.  Needs state, cov, summary, ws.
+ *
+ * Nothing is allocated and nothing is read back.  Argument errors are answered before the device is entered: null pointer -1;
+ * geometry -2 (a non-positive size, a channel outside [0, Cin), a window not inside the plane, a cell that does not divide the
+ * window, hold < 1, an unknown kind, density outside [0, 1], first_clip + B > 2^32, lags < 1, skip < 0, t0 >= T, samples < 1, a
+ * rel_threshold outside [0, 1], a misaligned state / summary); workspace too small or misaligned -3.  The size queries return 0 for
+ * arguments the entries would refuse. */
+enum { DWN_NOISE_BINARY = 0, DWN_NOISE_SPARSE = 1 };
+#define DWN_STA_SUMMARY 8
+typedef struct dwn_noise_args {
+    int B, Cin, T, H, W;
+    int video_channel;
+    int kind;                 /* DWN_NOISE_BINARY / DWN_NOISE_SPARSE */
+    int cell, hold;
+    int y0, x0, wh, ww;
+    int pad_;
+    float background, contrast, density, pad;
+    unsigned long long seed;
+    long long first_clip;     /* 0 <= first_clip, first_clip + B <= 2^32 */
+    const float* x;
+    float* out;
+} dwn_noise_args;
+int dwn_noise_forward(const dwn_noise_args* a, int device, void* stream);
+
+typedef struct dwn_sta_args {
+    int B, Cin, T, H, W, N;
+    int channel;
+    int y0, x0, wh, ww, cell;
+    int lags, skip;
+    float s0;
+    int pad_;
+    long long samples;        /* finalize: K */
+    double rel_threshold;     /* finalize */
+    const float* x;
+    const float* r;
+    const float* r0;          /* [N] or NULL */
+    double* state;
+    float* cov;
+    float* z;                 /* may be NULL */
+    double* summary;
+    void* ws; size_t ws_bytes;
+} dwn_sta_args;
+size_t dwn_sta_state_bytes(const dwn_sta_args* a);
+size_t dwn_sta_ws_bytes(const dwn_sta_args* a);
+int dwn_sta_accumulate(const dwn_sta_args* a, int device, void* stream);
+int dwn_sta_finalize(const dwn_sta_args* a, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

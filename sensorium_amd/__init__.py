@@ -10,9 +10,12 @@ from .losses import MiceCorrelationLoss, MicePoissonCorrelationLoss, MicePoisson
 from .shifter import DwiseNeuroGaze, GazeShifter  # noqa: F401
 from .modulator import BehaviorModulator, DwiseNeuroBehavior  # noqa: F401
 from .spatial import DwiseNeuroSpatial, SpatialGain  # noqa: F401
-from .stimuli import PARAM_NAMES, DriftingGabor  # noqa: F401
+from .stimuli import PARAM_NAMES, DriftingGabor, NoiseStimulus  # noqa: F401
 from .attribution import optimal_gabor, tuning_curve  # noqa: F401
+from . import receptive_fields  # noqa: F401
+from .receptive_fields import ReceptiveFields, StaAccumulator  # noqa: F401
 from .evaluation import FrameCut, TrialScorer, evaluate_trials  # noqa: F401
 
 __all__ = ["DwiseNeuro", "DwiseNeuroGaze", "GazeShifter", "DwiseNeuroBehavior", "BehaviorModulator", "DwiseNeuroSpatial", "SpatialGain", "MicePoissonLoss", "MiceCorrelationLoss", "MicePoissonCorrelationLoss",
-           "DriftingGabor", "PARAM_NAMES", "tuning_curve", "optimal_gabor", "FrameCut", "TrialScorer", "evaluate_trials"]
+           "DriftingGabor", "PARAM_NAMES", "tuning_curve", "optimal_gabor", "FrameCut", "TrialScorer", "evaluate_trials",
+           "NoiseStimulus", "receptive_fields", "StaAccumulator", "ReceptiveFields"]

@@ -247,6 +247,20 @@ class SpatialGainArgs(C.Structure):       # retinotopic readout gain (include/dw
                 ("dg", c_p), ("dpos", c_p), ("dweight", c_p), ("dbias", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
 
 
+class NoiseArgs(C.Structure):            # receptive-field mapping (include/dwn.h dwn_noise_args)
+    _fields_ = [("B", c_i), ("Cin", c_i), ("T", c_i), ("H", c_i), ("W", c_i), ("video_channel", c_i), ("kind", c_i), ("cell", c_i),
+                ("hold", c_i), ("y0", c_i), ("x0", c_i), ("wh", c_i), ("ww", c_i), ("pad_", c_i), ("background", c_f),
+                ("contrast", c_f), ("density", c_f), ("pad", c_f), ("seed", C.c_ulonglong), ("first_clip", c_ll), ("x", c_p),
+                ("out", c_p)]
+
+
+class StaArgs(C.Structure):              # (include/dwn.h dwn_sta_args)
+    _fields_ = [("B", c_i), ("Cin", c_i), ("T", c_i), ("H", c_i), ("W", c_i), ("N", c_i), ("channel", c_i), ("y0", c_i), ("x0", c_i),
+                ("wh", c_i), ("ww", c_i), ("cell", c_i), ("lags", c_i), ("skip", c_i), ("s0", c_f), ("pad_", c_i), ("samples", c_ll),
+                ("rel_threshold", c_d), ("x", c_p), ("r", c_p), ("r0", c_p), ("state", c_p), ("cov", c_p), ("z", c_p),
+                ("summary", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
+
+
 CORR_STAT_ROWS, CORR_TILE = 8, 16          # DWN_CORR_STAT_ROWS, DWN_CORR_TILE
 CORR_MEAN, CORR_SUM = 0, 1
 GABOR_GAUSSIAN, GABOR_NONE = 0, 1          # DWN_GABOR_*
@@ -254,6 +268,8 @@ BLUR_MAX_RADIUS, BLUR_TAPS_STRIDE, MOMENTS_CHUNK = 16, 33, 4096      # DWN_BLUR_
 MEI_STEP, MEI_PROJECT = 0, 1               # DWN_MEI_*
 MEI_CONTRAST_MAX, MEI_CONTRAST_FIXED = 0, 1
 TRIAL_STATE_ROWS, TRIAL_SCORE_ROWS, TRIAL_SUMMARY, TRIAL_TILE = 17, 5, 8, 4      # DWN_TRIAL_*
+NOISE_BINARY, NOISE_SPARSE = 0, 1          # DWN_NOISE_*
+STA_SUMMARY = 8                            # DWN_STA_SUMMARY
 MIX_BOX, MIX_BLEND = 0, 1
 VID_U8, VID_F32 = 0, 1
 
@@ -269,7 +285,7 @@ _STRUCTS = {
     "dwn_corr_args": CorrArgs, "dwn_gabor_args": GaborArgs, "dwn_modulator_args": ModulatorArgs,
     "dwn_blur3d_args": Blur3dArgs, "dwn_clip_moments_args": ClipMomentsArgs, "dwn_mei_update_args": MeiUpdateArgs,
     "dwn_trial_desc": TrialDesc, "dwn_trial_group": TrialGroup, "dwn_trial_score_args": TrialScoreArgs,
-    "dwn_spatial_gain_args": SpatialGainArgs,
+    "dwn_spatial_gain_args": SpatialGainArgs, "dwn_noise_args": NoiseArgs, "dwn_sta_args": StaArgs,
 }
 
 # every symbol include/dwn.h declares: (restype, argtypes)
@@ -356,6 +372,11 @@ SYMBOLS = {
     "dwn_spatial_gain_ws_bytes": (c_sz, [_P(SpatialGainArgs)]),
     "dwn_spatial_gain_forward": (c_i, [_P(SpatialGainArgs), c_i, c_p]),
     "dwn_spatial_gain_backward": (c_i, [_P(SpatialGainArgs), c_i, c_p]),
+    "dwn_noise_forward": (c_i, [_P(NoiseArgs), c_i, c_p]),
+    "dwn_sta_state_bytes": (c_sz, [_P(StaArgs)]),
+    "dwn_sta_ws_bytes": (c_sz, [_P(StaArgs)]),
+    "dwn_sta_accumulate": (c_i, [_P(StaArgs), c_i, c_p]),
+    "dwn_sta_finalize": (c_i, [_P(StaArgs), c_i, c_p]),
 }
 
 
@@ -366,7 +387,7 @@ class DwnError(RuntimeError):
 # csrc/Makefile HASH_SRCS, in its order
 HASH_SRCS = ("dwn_api.hip", "dwn_gemm.hip", "dwn_gemm_nn_1.hip", "dwn_gemm_nn_2.hip", "dwn_gemm_nn_3.hip", "dwn_gemm_nn_4.hip", "dwn_gemm_nn_5.hip",
              "dwn_gemm_nn_6.hip", "dwn_gemm_tn.hip", "dwn_pw_bwd.hip", "dwn_gemm_xl.hip", "dwn_gemm_kd.hip", "dwn_dwconv.hip", "dwn_dwrc.hip",
-             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_spatial.hip", "dwn_mei.hip", "dwn_trial_score.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
+             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_spatial.hip", "dwn_mei.hip", "dwn_trial_score.hip", "dwn_rf.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
              "dwn_kernels.h", "dwn_launch.h", "dwn_gemm_nn.h", "dwn_gain.h",
              "../../include/dwn.h")
 
@@ -396,8 +417,9 @@ def _load():
                            "dwn_modulator_backward", "dwn_blur3d_ws_bytes", "dwn_clip_moments_ws_bytes", "dwn_blur3d",
                            "dwn_clip_moments", "dwn_mei_update", "dwn_trial_score_ws_bytes", "dwn_trial_moments",
                            "dwn_trial_score_finalize", "dwn_spatial_gain_ws_bytes", "dwn_spatial_gain_forward",
-                           "dwn_spatial_gain_backward") and not hasattr(lib, name):
-            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator / the MEI kernels / the trial scores / the retinotopic readout gain; the plain training step calls none of them)
+                           "dwn_spatial_gain_backward", "dwn_noise_forward", "dwn_sta_state_bytes", "dwn_sta_ws_bytes",
+                           "dwn_sta_accumulate", "dwn_sta_finalize") and not hasattr(lib, name):
+            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator / the MEI kernels / the trial scores / the retinotopic readout gain / the receptive-field mapping; the plain training step calls none of them)
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -409,7 +431,7 @@ def _load():
                           f"`make -C {LIB_PATH.parent}` — binaries are not in git, so what runs must be what is committed")
     for cname, struct in _STRUCTS.items():
         n = lib.dwn_sizeof(cname.encode())
-        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args", "dwn_blur3d_args", "dwn_clip_moments_args", "dwn_mei_update_args", "dwn_trial_desc", "dwn_trial_group", "dwn_trial_score_args", "dwn_spatial_gain_args"))):      # (A/B: ABI 7 only appended)
+        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args", "dwn_blur3d_args", "dwn_clip_moments_args", "dwn_mei_update_args", "dwn_trial_desc", "dwn_trial_group", "dwn_trial_score_args", "dwn_spatial_gain_args", "dwn_noise_args", "dwn_sta_args"))):      # (A/B: ABI 7 only appended)
             raise ImportError(f"struct layout mismatch for {cname}: C {n} bytes vs ctypes {C.sizeof(struct)}")
     return lib
 

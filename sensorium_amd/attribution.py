@@ -479,3 +479,57 @@ def optimal_gabor(model, mouse_index: int, neurons: Index, *, starts, steps: int
         with torch.enable_grad():       # (an input requiring grad: the last entry comes from the same kernels as the others)
             trace[steps] = objective(z.detach().requires_grad_(True)).detach()
     return (start + scale * z).clamp(lo, hi), trace
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# receptive-field mapping (sensorium_amd/receptive_fields.py)
+# ------------------------------------------------------------------------------------------------------------------------------
+def receptive_fields(model, mouse_index: int, *, clips: int, frames: int, lags: int, batch: int = 32, noise: Optional[dict] = None,
+                     seed: int = 0, neurons: Index = None, skip: Optional[int] = None, size: Tuple[int, int] = (64, 64),
+                     window: Optional[Sequence[int]] = None, behavior: Sequence[float] = (0.0, 0.0),
+                     pupil_center: Sequence[float] = (0.0, 0.0), first_clip: int = 0, accumulator=None):
+    """The spatio-temporal receptive field of every neuron of mouse ``mouse_index`` by reverse correlation.
+
+    ``clips`` noise clips of ``frames`` frames (numbered ``first_clip ..``; a clip is a function of ``(seed, number)`` alone) are
+    rendered on the model's device ``batch`` at a time — the last batch may be smaller —, run through the eval-mode model without
+    grad (restored afterwards) and correlated with its responses at ``lags`` lags.  ``noise``: further ``NoiseStimulus`` arguments
+    (``kind``, ``cell``, ``hold``, ``contrast``, ``density``, ``background``, ``video_range``, ``pad``, ``in_channels``,
+    ``video_channel``); ``size`` / ``window`` / ``behavior`` / ``pupil_center`` as for ``DriftingGabor``.  ``skip``: the frames
+    of every clip left out as the model's warm-up (default ``lags - 1``, the least possible).  ``neurons`` selects rows before the
+    accumulation: the state then has ``len(neurons)`` rows.  The response centre is the per-neuron mean of the first batch's
+    responses, taken on the device; nothing is read back inside the loop.  ``accumulator``: continue an existing
+    ``StaAccumulator`` (its geometry must be the call's) — the way to split an experiment over several calls.
+
+    Returns ``ReceptiveFields`` (``.sta``, ``.z``, ``.summary``, ``.centres()``, ``.significant()``); its ``.accumulator`` is the
+    ``StaAccumulator`` behind it, to continue with."""
+    from .receptive_fields import StaAccumulator
+    from .stimuli import NoiseStimulus
+    clips, batch, lags = int(clips), int(batch), int(lags)
+    if clips < 1 or batch < 1 or lags < 1:
+        raise ValueError("clips, batch and lags must be positive")
+    skip = lags - 1 if skip is None else int(skip)
+    if skip < 0 or max(skip, lags - 1) >= int(frames):
+        raise ValueError(f"clips of {frames} frames hold no valid frame for lags = {lags}, skip = {skip}")
+    noise = dict(noise or {})
+    for k in ("seed", "window", "behavior", "pupil_center", "batch", "frames", "size"):
+        if k in noise:
+            raise ValueError(f"noise: {k!r} is an argument of receptive_fields itself")
+    device = next(model.parameters()).device
+    stim = NoiseStimulus(min(batch, clips), int(frames), size, window=window, behavior=behavior, pupil_center=pupil_center, seed=seed,
+                         **noise).to(device)
+    nsel = _as_index(neurons, device)
+    acc = accumulator
+    with _eval_mode(model), torch.no_grad():
+        for k0 in range(0, clips, batch):
+            x = stim(first_clip=int(first_clip) + k0, batch=min(batch, clips - k0))
+            full = model(x, index=mouse_index).float()
+            out = full[:, nsel]
+            if acc is None:
+                # the centre of a neuron is taken from the whole output: a row's bits do not depend on which rows are selected
+                centre = full.mean(dim=(0, 2))[nsel]
+                acc = StaAccumulator(int(out.shape[1]), lags, stim.size, window=stim.window, cell=stim.cell, channel=stim.video_channel,
+                                     skip=skip, stimulus_centre=stim.background, response_centre=centre, device=device)
+            acc.add(x, out)
+    fields = acc.compute()
+    fields.accumulator = acc
+    return fields

@@ -311,6 +311,7 @@ int dwn_sizeof(const char* name) {
     SZ(dwn_corr_args); SZ(dwn_gabor_args); SZ(dwn_modulator_args); SZ(dwn_spatial_gain_args);
     SZ(dwn_blur3d_args); SZ(dwn_clip_moments_args); SZ(dwn_mei_update_args);
     SZ(dwn_trial_desc); SZ(dwn_trial_group); SZ(dwn_trial_score_args);
+    SZ(dwn_noise_args); SZ(dwn_sta_args);
 #undef SZ
     return -1;
 }
@@ -1479,6 +1480,79 @@ int dwn_spatial_gain_backward(const dwn_spatial_gain_args* a, int device, void* 
     if (a->ws_bytes < k_spatial_gain_ws_bytes(*a) || ((size_t)a->ws & 15)) return dwn_set_error(-2, "spatial_gain_backward: workspace smaller than dwn_spatial_gain_ws_bytes or not 16-byte aligned");
     ENTER(device);
     return k_spatial_gain_backward(*a, (hipStream_t)stream);
+}
+
+// ---- receptive-field mapping: the argument checks need no device
+static int rf_plane(const char* who, int B, int Cin, int T, int H, int W, int c, int y0, int x0, int wh, int ww, int cell) {
+    static thread_local char msg[160];
+#define RF_BAD(text) do { snprintf(msg, sizeof msg, "%s: %s", who, text); return dwn_set_error(-2, msg); } while (0)
+    if (B <= 0 || Cin <= 0 || T <= 0 || H <= 0 || W <= 0) RF_BAD("B, Cin, T, H, W must be positive");
+    if (c < 0 || c >= Cin) RF_BAD("channel outside [0, Cin)");
+    if ((long long)H * W > (1ll << 30) || (long long)B * Cin * T >= (1ll << 31)) RF_BAD("more than 2^30 pixels per plane or 2^31 planes");
+    if (y0 < 0 || x0 < 0 || wh <= 0 || ww <= 0 || wh > H - y0 || ww > W - x0) RF_BAD("window not inside the plane");
+    if (cell < 1 || wh % cell || ww % cell) RF_BAD("cell must be positive and divide both window sides");
+#undef RF_BAD
+    return 0;
+}
+int dwn_noise_forward(const dwn_noise_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "noise_forward: null arguments");
+    TRY(rf_plane("noise", a->B, a->Cin, a->T, a->H, a->W, a->video_channel, a->y0, a->x0, a->wh, a->ww, a->cell));
+    if (a->kind != DWN_NOISE_BINARY && a->kind != DWN_NOISE_SPARSE) return dwn_set_error(-2, "noise: kind must be DWN_NOISE_BINARY or DWN_NOISE_SPARSE");
+    if (a->hold < 1) return dwn_set_error(-2, "noise: hold must be positive");
+    if (!(a->density >= 0.f && a->density <= 1.f)) return dwn_set_error(-2, "noise: density outside [0, 1]");
+    if (a->first_clip < 0 || a->first_clip > (1ll << 32) - a->B) return dwn_set_error(-2, "noise: clip numbers must stay inside [0, 2^32): first_clip + B <= 2^32");
+    if (!a->x || !a->out) return dwn_set_error(-1, "noise_forward: null pointer (x, out)");
+    ENTER(device);
+    return k_noise_forward(*a, (hipStream_t)stream);
+}
+
+// what the state's layout depends on: N, lags and the cell grid
+static int sta_grid(const dwn_sta_args* a) {
+    if (a->N <= 0) return dwn_set_error(-2, "sta: N must be positive");
+    if (a->lags < 1 || a->lags > 65535) return dwn_set_error(-2, "sta: lags outside [1, 65535]");
+    if (a->wh <= 0 || a->ww <= 0) return dwn_set_error(-2, "sta: the window sides must be positive");
+    if (a->cell < 1 || a->wh % a->cell || a->ww % a->cell) return dwn_set_error(-2, "sta: cell must be positive and divide both window sides");
+    const long long G = (long long)(a->wh / a->cell) * (a->ww / a->cell);
+    if (G > (1ll << 22) || (long long)a->N * a->lags > (1ll << 40) / G) return dwn_set_error(-2, "sta: more than 2^22 cells or 2^40 state elements");
+    return 0;
+}
+static int sta_accumulate_geometry(const dwn_sta_args* a) {
+    TRY(sta_grid(a));
+    TRY(rf_plane("sta", a->B, a->Cin, a->T, a->H, a->W, a->channel, a->y0, a->x0, a->wh, a->ww, a->cell));
+    if (a->skip < 0) return dwn_set_error(-2, "sta: skip must not be negative");
+    if ((a->skip > a->lags - 1 ? a->skip : a->lags - 1) >= a->T) return dwn_set_error(-2, "sta: no valid frame (max(skip, lags - 1) >= T)");
+    if ((long long)a->B * a->T >= (1ll << 31)) return dwn_set_error(-2, "sta: more than 2^31 samples per call");
+    return 0;
+}
+size_t dwn_sta_state_bytes(const dwn_sta_args* a) {
+    if (!a || sta_grid(a) != 0) { g_err[0] = 0; return 0; }
+    return k_sta_state_bytes(*a);
+}
+size_t dwn_sta_ws_bytes(const dwn_sta_args* a) {
+    if (!a || sta_grid(a) != 0) { g_err[0] = 0; return 0; }
+    return k_sta_ws_bytes(*a);
+}
+int dwn_sta_accumulate(const dwn_sta_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "sta_accumulate: null arguments");
+    TRY(sta_accumulate_geometry(a));
+    if (!a->x || !a->r || !a->state) return dwn_set_error(-1, "sta_accumulate: null pointer (x, r, state)");
+    if ((size_t)a->state & 7) return dwn_set_error(-2, "sta_accumulate: state must be 8-byte aligned");
+    ENTER(device);
+    return k_sta_accumulate(*a, (hipStream_t)stream);
+}
+int dwn_sta_finalize(const dwn_sta_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "sta_finalize: null arguments");
+    TRY(sta_grid(a));
+    if (a->samples < 1 || a->samples >= (1ll << 52)) return dwn_set_error(-2, "sta_finalize: samples outside [1, 2^52)");
+    if (!(a->rel_threshold >= 0.0 && a->rel_threshold <= 1.0)) return dwn_set_error(-2, "sta_finalize: rel_threshold outside [0, 1]");
+    if (!a->state || !a->cov || !a->summary || !a->ws) return dwn_set_error(-1, "sta_finalize: null pointer (state, cov, summary, ws)");
+    if (((size_t)a->state & 7) || ((size_t)a->summary & 7)) return dwn_set_error(-2, "sta_finalize: state and summary must be 8-byte aligned");
+    if (a->ws_bytes < k_sta_ws_bytes(*a) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "sta_finalize: workspace smaller than dwn_sta_ws_bytes or not 8-byte aligned");
+    ENTER(device);
+    return k_sta_finalize(*a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -147,6 +147,12 @@ int k_modulator_backward(const dwn_modulator_args& a, hipStream_t s);      // a.
 size_t k_spatial_gain_ws_bytes(const dwn_spatial_gain_args& a);
 int k_spatial_gain_forward(const dwn_spatial_gain_args& a, hipStream_t s);
 int k_spatial_gain_backward(const dwn_spatial_gain_args& a, hipStream_t s); // a.dy, a.dg, a.dpos, a.dweight, a.dbias: each may be null
+// receptive-field mapping (dwn.h dwn_noise_args, dwn_sta_args; dwn_stim.hip, dwn_rf.hip): arguments checked by the C-ABI layer
+int k_noise_forward(const dwn_noise_args& a, hipStream_t s);
+size_t k_sta_state_bytes(const dwn_sta_args& a);
+size_t k_sta_ws_bytes(const dwn_sta_args& a);
+int k_sta_accumulate(const dwn_sta_args& a, hipStream_t s);                  // cross term, then the four moment vectors
+int k_sta_finalize(const dwn_sta_args& a, hipStream_t s);                    // V statistics into a.ws, then one wave per neuron
 int k_pw_bwd_prep(const float* w1, const float* abc, int E, int C, void* bp, float* gacc, float* r3, int dtype,
                   const float* res_abc, int res_C, hipStream_t s);
 // conv_pw weight gradient from the raw products (see pw_bwd_fused_kernel): tacc [(E + C + 8)][C] fp32 = rows T1 = dh1^T a0,

@@ -233,6 +233,56 @@ __global__ __launch_bounds__(GB_NT) void gabor_finalize_kernel(const float* __re
     }
 }
 
+// ---- noise stimulus (include/dwn.h dwn_noise_args): every cell of every frame is one word of a Philox4x32-10 block
+// addressed by (cell >> 2, frame / hold, clip number), so a clip is a function of (seed, clip number) alone.  The block is
+// recomputed by each pixel of a cell (ten rounds of two 32 x 32 -> 64 multiplies): the kernel stays a single store stream.
+struct NoiseGeom {
+    int y0, x0, wh, ww, cell, hold, gw, sparse;
+    float v_lo, v_mid, v_hi, pad;              // background - contrast, background, background + contrast: formed once on the host
+    unsigned k0, k1, thr, clip0;               // key, floor(density 2^31), first clip number
+};
+
+__device__ __forceinline__ unsigned philox_word(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, int word) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return word == 0 ? c0 : word == 1 ? c1 : word == 2 ? c2 : c3;
+}
+
+__global__ __launch_bounds__(GB_NT) void noise_stream_kernel(const float* __restrict__ in, float* __restrict__ out, i64 planes, int Cin,
+                                                             int T, int H, int W, int vc, NoiseGeom gm, int vec) {
+    const int HW = H * W;
+    const UDiv32 divW((unsigned)W), divC((unsigned)gm.cell);
+    for (i64 p = blockIdx.x; p < planes; p += gridDim.x) {
+        const i64 bc = p / T;
+        const int t = (int)(p - bc * T);
+        const i64 b = bc / Cin;
+        const int c = (int)(bc - b * Cin);
+        float* dst = out + p * HW;
+        if (c != vc) {
+            copy_plane(in + p * HW, dst, HW, vec);
+            continue;
+        }
+        const unsigned step = (unsigned)(t / gm.hold), clip = gm.clip0 + (unsigned)b;     // first_clip + B <= 2^32: no wrap
+        for (int i = threadIdx.x; i < HW; i += GB_NT) {
+            const int y = (int)divW.div((unsigned)i), x = i - y * W;
+            const bool inside = (unsigned)(y - gm.y0) < (unsigned)gm.wh && (unsigned)(x - gm.x0) < (unsigned)gm.ww;
+            float o = gm.pad;
+            if (inside) {
+                const unsigned q = divC.div((unsigned)(y - gm.y0)) * (unsigned)gm.gw + divC.div((unsigned)(x - gm.x0));
+                const unsigned w = philox_word(q >> 2, step, clip, 0u, gm.k0, gm.k1, (int)(q & 3u));
+                if (gm.sparse) o = w < gm.thr ? gm.v_lo : (gm.thr != 0u && w >= 0u - gm.thr) ? gm.v_hi : gm.v_mid;
+                else o = (w >> 31) ? gm.v_hi : gm.v_lo;
+            }
+            dst[i] = o;
+        }
+    }
+}
+
 inline bool aligned16(const void* p) { return ((size_t)p & 15) == 0; }
 
 inline GaborGeom gabor_geom(const dwn_gabor_args& a) {
@@ -261,6 +311,20 @@ int k_gabor_forward(const dwn_gabor_args& a, hipStream_t s) {
                                a.H, a.W, a.video_channel, gm, vec);
     return launch_resident(gabor_stream_kernel<false>, GB_NT, 0, 4, 1, planes, false, s, a.x, a.params, a.out, planes, a.Cin, a.T,
                            a.H, a.W, a.video_channel, gm, vec);
+}
+
+int k_noise_forward(const dwn_noise_args& a, hipStream_t s) {
+    const i64 planes = (i64)a.B * a.Cin * a.T;
+    const int vec = (((i64)a.H * a.W) % 4 == 0 && aligned16(a.x) && aligned16(a.out)) ? 1 : 0;
+    NoiseGeom gm;
+    gm.y0 = a.y0; gm.x0 = a.x0; gm.wh = a.wh; gm.ww = a.ww; gm.cell = a.cell; gm.hold = a.hold; gm.gw = a.ww / a.cell;
+    gm.sparse = a.kind == DWN_NOISE_SPARSE;
+    gm.v_lo = a.background - a.contrast; gm.v_mid = a.background; gm.v_hi = a.background + a.contrast; gm.pad = a.pad;
+    gm.k0 = (unsigned)(a.seed & 0xffffffffull); gm.k1 = (unsigned)(a.seed >> 32);
+    gm.thr = (unsigned)floor((double)a.density * 2147483648.0);
+    gm.clip0 = (unsigned)a.first_clip;
+    return launch_resident(noise_stream_kernel, GB_NT, 0, 4, 1, planes, false, s, a.x, a.out, planes, a.Cin, a.T, a.H, a.W,
+                           a.video_channel, gm, vec);
 }
 
 int k_gabor_backward(const dwn_gabor_args& a, hipStream_t s) {

@@ -1269,3 +1269,101 @@ class SpatialGainFn(torch.autograd.Function):
         if dg is not None and dg.dtype != g.dtype:
             dg = dg.to(g.dtype)
         return dy, dg, dpos, dweight, dbias, None
+
+
+# ------------------------------------------------------------------------------------------------
+# receptive-field mapping (sensorium_amd/receptive_fields.py, stimuli.NoiseStimulus)
+# ------------------------------------------------------------------------------------------------
+NOISE_KINDS = {"binary": L.NOISE_BINARY, "sparse": L.NOISE_SPARSE}
+
+
+def noise_stimulus(template: torch.Tensor, *, kind: str = "binary", cell: int = 1, hold: int = 1, contrast: float = 64.0,
+                   density: float = 0.1, background: float = 127.5, window=None, pad: float = 0.0, video_channel: int = 0,
+                   seed: int = 0, first_clip: int = 0) -> torch.Tensor:
+    """dwn_noise_forward: a copy of ``template`` [B][C][T][H][W] fp32 whose channel ``video_channel`` holds Philox noise cells
+    inside ``window`` = (y0, x0, height, width) (default: the whole plane) and ``pad`` outside it.  Clip ``b`` is a function of
+    ``(seed, first_clip + b)`` alone (include/dwn.h dwn_noise_args)."""
+    _require_gpu(template, "noise_stimulus")
+    if template.dim() != 5 or template.dtype != torch.float32:
+        raise RuntimeError("sensorium_amd.noise_stimulus: template must be fp32 [B][C][T][H][W]")
+    if kind not in NOISE_KINDS:
+        raise ValueError(f"kind: one of {tuple(NOISE_KINDS)} (got {kind!r})")
+    seed, first_clip = int(seed), int(first_clip)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must lie in [0, 2^64)")
+    template = template.contiguous()
+    dev = template.device
+    a = L.NoiseArgs()
+    a.B, a.Cin, a.T, a.H, a.W = (int(n) for n in template.shape)
+    if first_clip < 0 or first_clip + a.B > 1 << 32:
+        raise ValueError("clip numbers must stay inside [0, 2^32): first_clip + batch <= 2^32")
+    a.video_channel, a.kind, a.cell, a.hold = int(video_channel), NOISE_KINDS[kind], int(cell), int(hold)
+    a.y0, a.x0, a.wh, a.ww = (int(n) for n in window) if window is not None else (0, 0, a.H, a.W)
+    a.background, a.contrast, a.density, a.pad = float(background), float(contrast), float(density), float(pad)
+    a.seed, a.first_clip = seed, first_clip
+    out = torch.empty_like(template)
+    a.x, a.out = template.data_ptr(), out.data_ptr()
+    L.check(L.lib.dwn_noise_forward(C.byref(a), dev.index, _stream(dev)), "dwn_noise_forward")
+    return out
+
+
+def _sta_args(N: int, lags: int, window, cell: int) -> L.StaArgs:
+    a = L.StaArgs()
+    a.N, a.lags, a.cell = int(N), int(lags), int(cell)
+    a.y0, a.x0, a.wh, a.ww = (int(n) for n in window)
+    return a
+
+
+def sta_state_numel(N: int, lags: int, window, cell: int) -> int:
+    """float64 elements of the accumulator's state (dwn_sta_state_bytes / 8); raises for a geometry the entries refuse."""
+    n = int(L.lib.dwn_sta_state_bytes(C.byref(_sta_args(N, lags, window, cell))))
+    if n == 0:
+        raise ValueError(f"sta: N = {N}, lags = {lags}, window = {tuple(window)}, cell = {cell} is not a geometry the kernels take")
+    return n // 8
+
+
+def sta_accumulate(state: torch.Tensor, x: torch.Tensor, r: torch.Tensor, *, lags: int, window, cell: int = 1, channel: int = 0,
+                   skip: int = 0, s0: float = 127.5, r0: Optional[torch.Tensor] = None) -> int:
+    """dwn_sta_accumulate: adds the lagged cross-sums and moments of one batch — ``x`` [B][C][T][H][W] fp32, ``r`` [B][N][T] fp32,
+    ``r0`` [N] fp32 or None — to ``state`` (float64, ``sta_state_numel`` elements, zero before the first call) in place.  Returns
+    the number of samples the call added, ``B * (T - max(skip, lags - 1))``.  No read-back."""
+    for t in (state, x, r):
+        _require_gpu(t, "sta_accumulate")
+    if x.dim() != 5 or r.dim() != 3 or x.dtype != torch.float32 or r.dtype != torch.float32:
+        raise RuntimeError("sensorium_amd.sta_accumulate: x must be fp32 [B][C][T][H][W] and r fp32 [B][N][T]")
+    if r.shape[0] != x.shape[0] or r.shape[2] != x.shape[2]:
+        raise ValueError(f"sensorium_amd.sta_accumulate: x {tuple(x.shape)} and r {tuple(r.shape)} disagree in batch or frames")
+    x, r = x.contiguous(), r.contiguous()
+    dev, N = x.device, int(r.shape[1])
+    a = _sta_args(N, lags, window, cell)
+    a.B, a.Cin, a.T, a.H, a.W = (int(n) for n in x.shape)
+    a.channel, a.skip, a.s0 = int(channel), int(skip), float(s0)
+    if state.dtype != torch.float64 or not state.is_contiguous() or state.numel() != sta_state_numel(N, lags, window, cell):
+        raise RuntimeError("sensorium_amd.sta_accumulate: state must be contiguous float64 of sta_state_numel elements")
+    if r0 is not None:
+        _require_gpu(r0, "sta_accumulate")
+        if r0.dtype != torch.float32 or r0.shape != (N,) or not r0.is_contiguous():
+            raise RuntimeError("sensorium_amd.sta_accumulate: r0 must be contiguous fp32 [N]")
+    a.x, a.r, a.r0, a.state = x.data_ptr(), r.data_ptr(), _ptr(r0), state.data_ptr()
+    L.check(L.lib.dwn_sta_accumulate(C.byref(a), dev.index, _stream(dev)), "dwn_sta_accumulate")
+    return a.B * (a.T - max(a.skip, a.lags - 1))
+
+
+def sta_finalize(state: torch.Tensor, samples: int, *, N: int, lags: int, window, cell: int = 1, rel_threshold: float = 0.5,
+                 z: bool = True):
+    """dwn_sta_finalize: ``(cov, z or None, summary)`` — fp32 ``[N, lags, gh, gw]`` twice and float64 ``[N, STA_SUMMARY]``
+    (include/dwn.h) — from the state and its sample count.  No read-back."""
+    _require_gpu(state, "sta_finalize")
+    if state.dtype != torch.float64 or not state.is_contiguous() or state.numel() != sta_state_numel(N, lags, window, cell):
+        raise RuntimeError("sensorium_amd.sta_finalize: state must be contiguous float64 of sta_state_numel elements")
+    dev = state.device
+    a = _sta_args(N, lags, window, cell)
+    a.samples, a.rel_threshold = int(samples), float(rel_threshold)
+    gh, gw = a.wh // a.cell, a.ww // a.cell
+    cov = torch.empty(N, lags, gh, gw, dtype=torch.float32, device=dev)
+    zz = torch.empty_like(cov) if z else None
+    summary = torch.empty(N, L.STA_SUMMARY, dtype=torch.float64, device=dev)
+    ws = torch.empty(max(int(L.lib.dwn_sta_ws_bytes(C.byref(a))) // 8, 1), dtype=torch.float64, device=dev)
+    a.state, a.cov, a.z, a.summary, a.ws, a.ws_bytes = state.data_ptr(), cov.data_ptr(), _ptr(zz), summary.data_ptr(), ws.data_ptr(), ws.numel() * 8
+    L.check(L.lib.dwn_sta_finalize(C.byref(a), dev.index, _stream(dev)), "dwn_sta_finalize")
+    return cov, zz, summary

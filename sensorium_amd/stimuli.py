@@ -57,6 +57,16 @@ def param_table(batch: int, values: Dict[str, object], defaults: Dict[str, float
     return table
 
 
+def make_template(batch, in_channels, frames, size, video_channel, behavior, pupil_center) -> torch.Tensor:
+    """[batch, in_channels, frames, H, W] fp32 zeros with the non-video channels set, in channel order, to the two ``behavior`` and
+    the two ``pupil_center`` constants (further channels stay zero)."""
+    template = torch.zeros(batch, in_channels, frames, *size, dtype=torch.float32)
+    others = [c for c in range(in_channels) if c != video_channel]
+    for c, v in zip(others, (*behavior, *pupil_center)):
+        template[:, c] = float(v)
+    return template
+
+
 class DriftingGabor(nn.Module):
     """``batch`` drifting Gabors as one ``nn.Parameter`` ``params`` [batch, 8]; ``forward()`` returns the model input
     [batch, in_channels, frames, H, W].
@@ -98,11 +108,8 @@ class DriftingGabor(nn.Module):
         table = param_table(self.batch, dict(init or {}), default_params(self.size, self.window, self.video_range))
         self.params = nn.Parameter(table)
         self.register_buffer("learn_mask", torch.tensor([n in learn for n in PARAM_NAMES]), persistent=False)
-        template = torch.zeros(self.batch, self.in_channels, self.frames, *self.size, dtype=torch.float32)
-        others = [c for c in range(self.in_channels) if c != self.video_channel]
-        for c, v in zip(others, (*behavior, *pupil_center)):
-            template[:, c] = float(v)
-        self.register_buffer("template", template, persistent=False)
+        self.register_buffer("template", make_template(self.batch, self.in_channels, self.frames, self.size, self.video_channel,
+                                                       behavior, pupil_center), persistent=False)
 
     def render(self, params: torch.Tensor) -> torch.Tensor:
         """The model input for explicit ``params`` [batch, 8] (differentiable in all eight columns)."""
@@ -118,6 +125,76 @@ class DriftingGabor(nn.Module):
     def extra_repr(self) -> str:
         return (f"batch={self.batch}, frames={self.frames}, size={self.size}, envelope={self.envelope!r}, "
                 f"window={self.window}, video_range={self.video_range}, learn={self.learn}")
+
+
+NOISE_KINDS = tuple(ops.NOISE_KINDS)
+
+
+class NoiseStimulus(nn.Module):
+    """Counter-based noise for receptive-field mapping: ``stim(first_clip=0)`` returns the model input
+    [batch, in_channels, frames, H, W] of clips ``first_clip .. first_clip + batch - 1``.  A clip is a function of ``(seed, clip
+    number)`` alone, so a long experiment is rendered batch by batch on the device and can be reproduced in any chunking.
+
+    The window is tiled by ``cell`` x ``cell`` squares; each keeps its value for ``hold`` frames.  ``kind="binary"``: every cell is
+    ``background + contrast`` or ``background - contrast`` with equal probability.  ``kind="sparse"``: a cell is dark with
+    probability ``density / 2``, bright with the same probability and ``background`` otherwise.  Nothing is clamped, so
+    ``background +- contrast`` must lie inside ``video_range``.  Geometry arguments are those of ``DriftingGabor``.  The module
+    has no parameters and no gradient."""
+
+    def __init__(self, batch: int, frames: int, size: Tuple[int, int] = (64, 64), *, kind: str = "binary", cell: int = 1,
+                 hold: int = 1, contrast: float = 64.0, density: float = 0.1, background: float = 127.5,
+                 video_range: Optional[Tuple[float, float]] = (0.0, 255.0), window: Optional[Sequence[int]] = None,
+                 pad: float = 0.0, behavior: Sequence[float] = (0.0, 0.0), pupil_center: Sequence[float] = (0.0, 0.0),
+                 in_channels: int = 5, video_channel: int = 0, seed: int = 0):
+        super().__init__()
+        if int(batch) < 1 or int(frames) < 1:
+            raise ValueError("batch and frames must be positive")
+        if len(size) != 2 or int(size[0]) < 1 or int(size[1]) < 1:
+            raise ValueError("size: (height, width), both positive")
+        if kind not in NOISE_KINDS:
+            raise ValueError(f"kind: one of {NOISE_KINDS} (got {kind!r})")
+        if int(in_channels) < 1 or not 0 <= int(video_channel) < int(in_channels):
+            raise ValueError("video_channel must lie in [0, in_channels)")
+        if video_range is not None and (len(video_range) != 2 or not float(video_range[0]) <= float(video_range[1])):
+            raise ValueError("video_range: (lo, hi) with lo <= hi, or None")
+        if len(behavior) != 2 or len(pupil_center) != 2:
+            raise ValueError("behavior / pupil_center: two values each")
+        if int(cell) != cell or int(hold) != hold or int(cell) < 1 or int(hold) < 1:
+            raise ValueError("cell and hold: positive integers")
+        if not float(contrast) >= 0.0 or not 0.0 <= float(density) <= 1.0:
+            raise ValueError("contrast must not be negative and density must lie in [0, 1]")
+        if int(seed) != seed or not 0 <= int(seed) < 1 << 64:
+            raise ValueError("seed: an integer in [0, 2^64)")
+        self.batch, self.frames, self.size = int(batch), int(frames), (int(size[0]), int(size[1]))
+        self.kind, self.cell, self.hold, self.seed = kind, int(cell), int(hold), int(seed)
+        self.contrast, self.density, self.background, self.pad = float(contrast), float(density), float(background), float(pad)
+        self.video_range = None if video_range is None else (float(video_range[0]), float(video_range[1]))
+        self.window = check_window(window, self.size)
+        wh, ww = self.window[2:] if self.window is not None else self.size
+        if wh % self.cell or ww % self.cell:
+            raise ValueError(f"cell = {self.cell} does not divide the {wh} x {ww} window")
+        if self.video_range is not None and not (self.video_range[0] <= self.background - self.contrast
+                                                 and self.background + self.contrast <= self.video_range[1]):
+            raise ValueError(f"background +- contrast = {self.background} +- {self.contrast} leaves video_range {self.video_range}: "
+                             "the noise is never clamped")
+        self.grid = (wh // self.cell, ww // self.cell)
+        self.in_channels, self.video_channel = int(in_channels), int(video_channel)
+        self.register_buffer("template", make_template(self.batch, self.in_channels, self.frames, self.size, self.video_channel,
+                                                       behavior, pupil_center), persistent=False)
+
+    @torch.no_grad()
+    def forward(self, first_clip: int = 0, batch: Optional[int] = None) -> torch.Tensor:
+        """Clips ``first_clip .. first_clip + batch - 1`` (``batch``: at most the module's own, default all of it)."""
+        n = self.batch if batch is None else int(batch)
+        if not 1 <= n <= self.batch:
+            raise ValueError(f"batch must lie in [1, {self.batch}]")
+        return ops.noise_stimulus(self.template[:n], kind=self.kind, cell=self.cell, hold=self.hold, contrast=self.contrast,
+                                  density=self.density, background=self.background, window=self.window, pad=self.pad,
+                                  video_channel=self.video_channel, seed=self.seed, first_clip=first_clip)
+
+    def extra_repr(self) -> str:
+        return (f"batch={self.batch}, frames={self.frames}, size={self.size}, kind={self.kind!r}, cell={self.cell}, "
+                f"hold={self.hold}, window={self.window}, seed={self.seed}")
 
 
 def _column(k):
