@@ -1019,6 +1019,64 @@ size_t dwn_sta_ws_bytes(const dwn_sta_args* a);
 int dwn_sta_accumulate(const dwn_sta_args* a, int device, void* stream);
 int dwn_sta_finalize(const dwn_sta_args* a, int device, void* stream);
 
+/* ---- parametric receptive-field fits: an elliptical Gaussian per map by Levenberg-Marquardt, and the temporal
+ * profile of a lagged map on that spatial shape.
+ *
+ * dwn_gauss2d_fit: maps fp32 [R][gh][gw] contiguous; sel int32 [M] device table of rows of `maps`, or NULL (rows 0 .. M-1, which
+ * needs M <= R).  With y, x the row and column index of a cell, dx = x - cx, dy = y - cy,
+ *   f = b + a exp(-q / 2),   q = (l11 dx)^2 + (l21 dx + l22 dy)^2,   p = (b, a, cy, cx, log l11, l21, log l22)
+ * (the Cholesky factor of the precision matrix).  Start: b0 = mean of the perimeter cells (0 and held with fit_baseline = 0);
+ * d = m - b0; peak = argmax |d| (lowest index on a tie), a0 = d[peak]; centre and (sy, sx) = the d^2-weighted centroid and standard
+ * deviations over the cells with |d| >= rel_threshold |a0|, each sigma floored at 0.5; l11 = 1 / sx, l22 = 1 / sy, l21 = 0.
+ * Iteration: Levenberg-Marquardt on S = sum (m - f)^2, analytic Jacobian; (JtJ + lam diag JtJ) dp = Jt r by Cholesky, lam from
+ * 1e-3; the proposal is clamped (centre to [-1, gh] x [-1, gw], the two logs so that 1 / l stays in [0.3, 2 max(gh, gw)]); with
+ * the step scaled by (|a|, |a|, 1, 1, 1, 1, 1), a largest scaled step below xtol converges; a proposal is accepted only if its S
+ * is finite and strictly smaller (lam = max(lam / 10, 1e-12); converged if the decrease is <= ftol S), otherwise lam *= 10, at
+ * most 16 tries per iteration (a Cholesky failure is a try).  All arithmetic is float64; every sum over the cells is lane-strided
+ * and closed by a fixed xor butterfly, so a row depends on its map and the options alone — not on M, sel, the launch or the build.
+ * params double [M][DWN_GAUSS_PARAMS] = p.  table double [M][DWN_GAUSS_TABLE]:
+ *   0 status (0 converged, 1 stopped at max_iter or out of tries, 2 no fit)   1 iterations   2 baseline   3 amplitude   4 cy   5 cx
+ *   6 sigma_major   7 sigma_minor   8 theta (major axis from the x axis, (-pi/2, pi/2])   9 sse   10 r2 = 1 - S / SS_tot about the
+ *   map's mean (0 where SS_tot is 0)   11, 12, 13 se_cy, se_cx, se_amplitude = sqrt(C_ii S / (G - n_par)), C = (JtJ)^-1 at the
+ *   solution (NaN where JtJ is not positive definite)   14 lambda   15 row (the row of `maps` that was fitted)
+ * Status 2: a constant map, a non-finite value in the map, a0 == 0, or a row outside [0, R): baseline and sse if they are finite
+ * (else NaN), amplitude 0, iterations 0, r2 0, lambda 0, NaN in the geometry and standard-error columns and in params 2-6.
+ * ws: dwn_gauss2d_ws_bytes(a) bytes, 8-byte aligned: double [M][8], the start vector p0 and S(p0) of every row.
+ *
+ * dwn_gauss2d_profile: params double [N][DWN_GAUSS_PARAMS] (of dwn_gauss2d_fit), maps fp32 [N][L][gh][gw].  With
+ * e_g = exp(-q_g / 2) at the row's params, per lag the linear least-squares fit m_l ~ b_l + a_l e (fit_baseline = 0: a_l e):
+ * profile double [N][L] = a_l; separability double [N] = 1 - sum_l SSE_l / sum_l SStot_l with SStot_l about the lag's mean
+ * (fit_baseline = 0: about 0), 0 where the denominator is 0.  A row whose params hold a NaN (status 2) gives NaN in both.  One
+ * wave per neuron, float64 sums in a fixed order.
+ *
+ * Errors: null pointer -1; geometry -2 (gh < 3, gw < 3, gh gw > 4096, M < 1, R < 1, sel NULL with M > R, max_iter < 0, a
+ * rel_threshold outside [0, 1], xtol or ftol negative or NaN, N or L < 1, misaligned params / table / profile); workspace too small
+ * or misaligned -3.  dwn_gauss2d_ws_bytes returns 0 for a geometry the entry refuses. */
+#define DWN_GAUSS_PARAMS 7
+#define DWN_GAUSS_TABLE 16
+typedef struct dwn_gauss2d_args {
+    int R, gh, gw, M;
+    int fit_baseline, max_iter;
+    double rel_threshold, xtol, ftol;
+    const float* maps;
+    const int* sel;           /* device [M] or NULL */
+    double* params;
+    double* table;
+    void* ws; size_t ws_bytes;
+} dwn_gauss2d_args;
+size_t dwn_gauss2d_ws_bytes(const dwn_gauss2d_args* a);
+int dwn_gauss2d_fit(const dwn_gauss2d_args* a, int device, void* stream);
+
+typedef struct dwn_gauss2d_profile_args {
+    int N, L, gh, gw;
+    int fit_baseline, pad_;
+    const double* params;
+    const float* maps;
+    double* profile;
+    double* separability;
+} dwn_gauss2d_profile_args;
+int dwn_gauss2d_profile(const dwn_gauss2d_profile_args* a, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -261,6 +261,17 @@ class StaArgs(C.Structure):              # (include/dwn.h dwn_sta_args)
                 ("summary", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
 
 
+class Gauss2dArgs(C.Structure):          # parametric receptive-field fits (include/dwn.h dwn_gauss2d_args)
+    _fields_ = [("R", c_i), ("gh", c_i), ("gw", c_i), ("M", c_i), ("fit_baseline", c_i), ("max_iter", c_i), ("rel_threshold", c_d),
+                ("xtol", c_d), ("ftol", c_d), ("maps", c_p), ("sel", c_p), ("params", c_p), ("table", c_p), ("ws", c_p),
+                ("ws_bytes", c_sz)]
+
+
+class Gauss2dProfileArgs(C.Structure):   # (include/dwn.h dwn_gauss2d_profile_args)
+    _fields_ = [("N", c_i), ("L", c_i), ("gh", c_i), ("gw", c_i), ("fit_baseline", c_i), ("pad_", c_i), ("params", c_p), ("maps", c_p),
+                ("profile", c_p), ("separability", c_p)]
+
+
 CORR_STAT_ROWS, CORR_TILE = 8, 16          # DWN_CORR_STAT_ROWS, DWN_CORR_TILE
 CORR_MEAN, CORR_SUM = 0, 1
 GABOR_GAUSSIAN, GABOR_NONE = 0, 1          # DWN_GABOR_*
@@ -270,6 +281,7 @@ MEI_CONTRAST_MAX, MEI_CONTRAST_FIXED = 0, 1
 TRIAL_STATE_ROWS, TRIAL_SCORE_ROWS, TRIAL_SUMMARY, TRIAL_TILE = 17, 5, 8, 4      # DWN_TRIAL_*
 NOISE_BINARY, NOISE_SPARSE = 0, 1          # DWN_NOISE_*
 STA_SUMMARY = 8                            # DWN_STA_SUMMARY
+GAUSS_PARAMS, GAUSS_TABLE = 7, 16          # DWN_GAUSS_*
 MIX_BOX, MIX_BLEND = 0, 1
 VID_U8, VID_F32 = 0, 1
 
@@ -286,6 +298,7 @@ _STRUCTS = {
     "dwn_blur3d_args": Blur3dArgs, "dwn_clip_moments_args": ClipMomentsArgs, "dwn_mei_update_args": MeiUpdateArgs,
     "dwn_trial_desc": TrialDesc, "dwn_trial_group": TrialGroup, "dwn_trial_score_args": TrialScoreArgs,
     "dwn_spatial_gain_args": SpatialGainArgs, "dwn_noise_args": NoiseArgs, "dwn_sta_args": StaArgs,
+    "dwn_gauss2d_args": Gauss2dArgs, "dwn_gauss2d_profile_args": Gauss2dProfileArgs,
 }
 
 # every symbol include/dwn.h declares: (restype, argtypes)
@@ -372,6 +385,10 @@ SYMBOLS = {
     "dwn_spatial_gain_ws_bytes": (c_sz, [_P(SpatialGainArgs)]),
     "dwn_spatial_gain_forward": (c_i, [_P(SpatialGainArgs), c_i, c_p]),
     "dwn_spatial_gain_backward": (c_i, [_P(SpatialGainArgs), c_i, c_p]),
+    # (the parametric fits of dwn_rf_fit.hip; tests/test_host_rf.py keeps the five receptive-field entries last)
+    "dwn_gauss2d_ws_bytes": (c_sz, [_P(Gauss2dArgs)]),
+    "dwn_gauss2d_fit": (c_i, [_P(Gauss2dArgs), c_i, c_p]),
+    "dwn_gauss2d_profile": (c_i, [_P(Gauss2dProfileArgs), c_i, c_p]),
     "dwn_noise_forward": (c_i, [_P(NoiseArgs), c_i, c_p]),
     "dwn_sta_state_bytes": (c_sz, [_P(StaArgs)]),
     "dwn_sta_ws_bytes": (c_sz, [_P(StaArgs)]),
@@ -387,7 +404,7 @@ class DwnError(RuntimeError):
 # csrc/Makefile HASH_SRCS, in its order
 HASH_SRCS = ("dwn_api.hip", "dwn_gemm.hip", "dwn_gemm_nn_1.hip", "dwn_gemm_nn_2.hip", "dwn_gemm_nn_3.hip", "dwn_gemm_nn_4.hip", "dwn_gemm_nn_5.hip",
              "dwn_gemm_nn_6.hip", "dwn_gemm_tn.hip", "dwn_pw_bwd.hip", "dwn_gemm_xl.hip", "dwn_gemm_kd.hip", "dwn_dwconv.hip", "dwn_dwrc.hip",
-             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_spatial.hip", "dwn_mei.hip", "dwn_trial_score.hip", "dwn_rf.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
+             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_spatial.hip", "dwn_mei.hip", "dwn_rf_fit.hip", "dwn_trial_score.hip", "dwn_rf.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
              "dwn_kernels.h", "dwn_launch.h", "dwn_gemm_nn.h", "dwn_gain.h",
              "../../include/dwn.h")
 
@@ -418,8 +435,9 @@ def _load():
                            "dwn_clip_moments", "dwn_mei_update", "dwn_trial_score_ws_bytes", "dwn_trial_moments",
                            "dwn_trial_score_finalize", "dwn_spatial_gain_ws_bytes", "dwn_spatial_gain_forward",
                            "dwn_spatial_gain_backward", "dwn_noise_forward", "dwn_sta_state_bytes", "dwn_sta_ws_bytes",
-                           "dwn_sta_accumulate", "dwn_sta_finalize") and not hasattr(lib, name):
-            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator / the MEI kernels / the trial scores / the retinotopic readout gain / the receptive-field mapping; the plain training step calls none of them)
+                           "dwn_sta_accumulate", "dwn_sta_finalize", "dwn_gauss2d_ws_bytes", "dwn_gauss2d_fit",
+                           "dwn_gauss2d_profile") and not hasattr(lib, name):
+            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator / the MEI kernels / the trial scores / the retinotopic readout gain / the receptive-field mapping / the parametric fits; the plain training step calls none of them)
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -431,7 +449,7 @@ def _load():
                           f"`make -C {LIB_PATH.parent}` — binaries are not in git, so what runs must be what is committed")
     for cname, struct in _STRUCTS.items():
         n = lib.dwn_sizeof(cname.encode())
-        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args", "dwn_blur3d_args", "dwn_clip_moments_args", "dwn_mei_update_args", "dwn_trial_desc", "dwn_trial_group", "dwn_trial_score_args", "dwn_spatial_gain_args", "dwn_noise_args", "dwn_sta_args"))):      # (A/B: ABI 7 only appended)
+        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args", "dwn_blur3d_args", "dwn_clip_moments_args", "dwn_mei_update_args", "dwn_trial_desc", "dwn_trial_group", "dwn_trial_score_args", "dwn_spatial_gain_args", "dwn_noise_args", "dwn_sta_args", "dwn_gauss2d_args", "dwn_gauss2d_profile_args"))):      # (A/B: ABI 7 only appended)
             raise ImportError(f"struct layout mismatch for {cname}: C {n} bytes vs ctypes {C.sizeof(struct)}")
     return lib
 

@@ -487,7 +487,7 @@ def optimal_gabor(model, mouse_index: int, neurons: Index, *, starts, steps: int
 def receptive_fields(model, mouse_index: int, *, clips: int, frames: int, lags: int, batch: int = 32, noise: Optional[dict] = None,
                      seed: int = 0, neurons: Index = None, skip: Optional[int] = None, size: Tuple[int, int] = (64, 64),
                      window: Optional[Sequence[int]] = None, behavior: Sequence[float] = (0.0, 0.0),
-                     pupil_center: Sequence[float] = (0.0, 0.0), first_clip: int = 0, accumulator=None):
+                     pupil_center: Sequence[float] = (0.0, 0.0), first_clip: int = 0, accumulator=None, fit: Optional[dict] = None):
     """The spatio-temporal receptive field of every neuron of mouse ``mouse_index`` by reverse correlation.
 
     ``clips`` noise clips of ``frames`` frames (numbered ``first_clip ..``; a clip is a function of ``(seed, number)`` alone) are
@@ -498,7 +498,9 @@ def receptive_fields(model, mouse_index: int, *, clips: int, frames: int, lags: 
     of every clip left out as the model's warm-up (default ``lags - 1``, the least possible).  ``neurons`` selects rows before the
     accumulation: the state then has ``len(neurons)`` rows.  The response centre is the per-neuron mean of the first batch's
     responses, taken on the device; nothing is read back inside the loop.  ``accumulator``: continue an existing
-    ``StaAccumulator`` (its geometry must be the call's) — the way to split an experiment over several calls.
+    ``StaAccumulator`` (its geometry must be the call's) — the way to split an experiment over several calls.  ``fit``: a dict of
+    ``ReceptiveFields.fit`` arguments (``{}`` for the defaults): the parametric fits are then run on the result and kept as its
+    ``.fits``; ``None`` runs none.
 
     Returns ``ReceptiveFields`` (``.sta``, ``.z``, ``.summary``, ``.centres()``, ``.significant()``); its ``.accumulator`` is the
     ``StaAccumulator`` behind it, to continue with."""
@@ -532,4 +534,6 @@ def receptive_fields(model, mouse_index: int, *, clips: int, frames: int, lags: 
             acc.add(x, out)
     fields = acc.compute()
     fields.accumulator = acc
+    if fit is not None:
+        fields.fit(**dict(fit))
     return fields

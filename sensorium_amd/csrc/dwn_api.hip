@@ -311,7 +311,7 @@ int dwn_sizeof(const char* name) {
     SZ(dwn_corr_args); SZ(dwn_gabor_args); SZ(dwn_modulator_args); SZ(dwn_spatial_gain_args);
     SZ(dwn_blur3d_args); SZ(dwn_clip_moments_args); SZ(dwn_mei_update_args);
     SZ(dwn_trial_desc); SZ(dwn_trial_group); SZ(dwn_trial_score_args);
-    SZ(dwn_noise_args); SZ(dwn_sta_args);
+    SZ(dwn_noise_args); SZ(dwn_sta_args); SZ(dwn_gauss2d_args); SZ(dwn_gauss2d_profile_args);
 #undef SZ
     return -1;
 }
@@ -1553,6 +1553,48 @@ int dwn_sta_finalize(const dwn_sta_args* a, int device, void* stream) {
     if (a->ws_bytes < k_sta_ws_bytes(*a) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "sta_finalize: workspace smaller than dwn_sta_ws_bytes or not 8-byte aligned");
     ENTER(device);
     return k_sta_finalize(*a, (hipStream_t)stream);
+}
+
+// ---- parametric receptive-field fits: the argument checks need no device
+static int gauss2d_grid(int gh, int gw) {
+    if (gh < 3 || gw < 3) return dwn_set_error(-2, "gauss2d: gh and gw must be at least 3");
+    if ((long long)gh * gw > 4096) return dwn_set_error(-2, "gauss2d: more than 4096 cells per map");
+    return 0;
+}
+static int gauss2d_geometry(const dwn_gauss2d_args* a) {
+    TRY(gauss2d_grid(a->gh, a->gw));
+    if (a->M < 1 || a->R < 1) return dwn_set_error(-2, "gauss2d: M and R must be positive");
+    if ((long long)a->M > (1ll << 31) / 4096 || (long long)a->R > (1ll << 40) / 4096) return dwn_set_error(-2, "gauss2d: more than 2^19 fits or 2^28 rows");
+    return 0;
+}
+size_t dwn_gauss2d_ws_bytes(const dwn_gauss2d_args* a) {
+    if (!a || gauss2d_geometry(a) != 0) { g_err[0] = 0; return 0; }
+    return k_gauss2d_ws_bytes(*a);
+}
+int dwn_gauss2d_fit(const dwn_gauss2d_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "gauss2d_fit: null arguments");
+    TRY(gauss2d_geometry(a));
+    if (!a->sel && a->M > a->R) return dwn_set_error(-2, "gauss2d_fit: M > R without a row table");
+    if (a->max_iter < 0) return dwn_set_error(-2, "gauss2d_fit: max_iter must not be negative");
+    if (!(a->rel_threshold >= 0.0 && a->rel_threshold <= 1.0)) return dwn_set_error(-2, "gauss2d_fit: rel_threshold outside [0, 1]");
+    if (!(a->xtol >= 0.0) || !(a->ftol >= 0.0)) return dwn_set_error(-2, "gauss2d_fit: xtol and ftol must not be negative");
+    if (!a->maps || !a->params || !a->table || !a->ws) return dwn_set_error(-1, "gauss2d_fit: null pointer (maps, params, table, ws)");
+    if (((size_t)a->params & 7) || ((size_t)a->table & 7)) return dwn_set_error(-2, "gauss2d_fit: params and table must be 8-byte aligned");
+    if (a->ws_bytes < k_gauss2d_ws_bytes(*a) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "gauss2d_fit: workspace smaller than dwn_gauss2d_ws_bytes or not 8-byte aligned");
+    ENTER(device);
+    return k_gauss2d_fit(*a, (hipStream_t)stream);
+}
+int dwn_gauss2d_profile(const dwn_gauss2d_profile_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "gauss2d_profile: null arguments");
+    TRY(gauss2d_grid(a->gh, a->gw));
+    if (a->N < 1 || a->L < 1 || a->L > 65535) return dwn_set_error(-2, "gauss2d_profile: N must be positive and L in [1, 65535]");
+    if ((long long)a->N * a->L > (1ll << 40) / 4096) return dwn_set_error(-2, "gauss2d_profile: more than 2^28 maps");
+    if (!a->params || !a->maps || !a->profile || !a->separability) return dwn_set_error(-1, "gauss2d_profile: null pointer (params, maps, profile, separability)");
+    if (((size_t)a->params & 7) || ((size_t)a->profile & 7) || ((size_t)a->separability & 7)) return dwn_set_error(-2, "gauss2d_profile: params, profile and separability must be 8-byte aligned");
+    ENTER(device);
+    return k_gauss2d_profile(*a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -153,6 +153,10 @@ size_t k_sta_state_bytes(const dwn_sta_args& a);
 size_t k_sta_ws_bytes(const dwn_sta_args& a);
 int k_sta_accumulate(const dwn_sta_args& a, hipStream_t s);                  // cross term, then the four moment vectors
 int k_sta_finalize(const dwn_sta_args& a, hipStream_t s);                    // V statistics into a.ws, then one wave per neuron
+// parametric receptive-field fits (dwn.h dwn_gauss2d_args; dwn_rf_fit.hip): arguments checked by the C-ABI layer
+size_t k_gauss2d_ws_bytes(const dwn_gauss2d_args& a);
+int k_gauss2d_fit(const dwn_gauss2d_args& a, hipStream_t s);                  // one wave per map, one launch
+int k_gauss2d_profile(const dwn_gauss2d_profile_args& a, hipStream_t s);      // one wave per neuron
 int k_pw_bwd_prep(const float* w1, const float* abc, int E, int C, void* bp, float* gacc, float* r3, int dtype,
                   const float* res_abc, int res_C, hipStream_t s);
 // conv_pw weight gradient from the raw products (see pw_bwd_fused_kernel): tacc [(E + C + 8)][C] fp32 = rows T1 = dh1^T a0,

@@ -1367,3 +1367,60 @@ def sta_finalize(state: torch.Tensor, samples: int, *, N: int, lags: int, window
     a.state, a.cov, a.z, a.summary, a.ws, a.ws_bytes = state.data_ptr(), cov.data_ptr(), _ptr(zz), summary.data_ptr(), ws.data_ptr(), ws.numel() * 8
     L.check(L.lib.dwn_sta_finalize(C.byref(a), dev.index, _stream(dev)), "dwn_sta_finalize")
     return cov, zz, summary
+
+
+def gauss2d_ws_numel(M: int, gh: int, gw: int, rows: int = 1) -> int:
+    """float64 elements of the fit's workspace (dwn_gauss2d_ws_bytes / 8); raises for a geometry the entry refuses."""
+    a = L.Gauss2dArgs()
+    a.R, a.gh, a.gw, a.M = int(rows), int(gh), int(gw), int(M)
+    n = int(L.lib.dwn_gauss2d_ws_bytes(C.byref(a)))
+    if n == 0:
+        raise ValueError(f"gauss2d: M = {M} maps of {gh} x {gw} cells is not a geometry the kernels take (3 <= gh, gw; gh gw <= 4096; M >= 1)")
+    return n // 8
+
+
+def gauss2d_fit(maps: torch.Tensor, sel: Optional[torch.Tensor] = None, *, fit_baseline: bool = True, rel_threshold: float = 0.5,
+                max_iter: int = 100, xtol: float = 1e-8, ftol: float = 1e-12):
+    """dwn_gauss2d_fit: ``(params, table, start)`` — float64 ``[M, GAUSS_PARAMS]``, ``[M, GAUSS_TABLE]`` and the workspace
+    ``[M, 8]`` (the start vector and its S) — of the elliptical-Gaussian fits of the rows ``sel`` (an int32 device table, default
+    all rows in order) of ``maps`` fp32 ``[R, gh, gw]`` (include/dwn.h).  One launch on the current stream; no read-back."""
+    _require_gpu(maps, "gauss2d_fit")
+    if maps.dim() != 3 or maps.dtype != torch.float32 or not maps.is_contiguous():
+        raise RuntimeError("sensorium_amd.gauss2d_fit: maps must be contiguous fp32 [R][gh][gw]")
+    dev = maps.device
+    R, gh, gw = (int(n) for n in maps.shape)
+    if sel is not None:
+        _require_gpu(sel, "gauss2d_fit")
+        if sel.dtype != torch.int32 or sel.dim() != 1 or not sel.is_contiguous() or sel.device != dev:
+            raise RuntimeError("sensorium_amd.gauss2d_fit: sel must be a contiguous int32 [M] table on the maps' device")
+    M = R if sel is None else int(sel.shape[0])
+    a = L.Gauss2dArgs()
+    a.R, a.gh, a.gw, a.M = R, gh, gw, M
+    a.fit_baseline, a.max_iter = int(bool(fit_baseline)), int(max_iter)
+    a.rel_threshold, a.xtol, a.ftol = float(rel_threshold), float(xtol), float(ftol)
+    ws = torch.empty(gauss2d_ws_numel(M, gh, gw, R), dtype=torch.float64, device=dev)
+    params = torch.empty(M, L.GAUSS_PARAMS, dtype=torch.float64, device=dev)
+    table = torch.empty(M, L.GAUSS_TABLE, dtype=torch.float64, device=dev)
+    a.maps, a.sel, a.params, a.table, a.ws, a.ws_bytes = maps.data_ptr(), _ptr(sel), params.data_ptr(), table.data_ptr(), ws.data_ptr(), ws.numel() * 8
+    L.check(L.lib.dwn_gauss2d_fit(C.byref(a), dev.index, _stream(dev)), "dwn_gauss2d_fit")
+    return params, table, ws.view(M, 8)
+
+
+def gauss2d_profile(params: torch.Tensor, maps: torch.Tensor, *, fit_baseline: bool = True):
+    """dwn_gauss2d_profile: ``(profile, separability)`` — float64 ``[N, L]`` and ``[N]`` — of ``maps`` fp32 ``[N, L, gh, gw]`` on the
+    spatial shapes of ``params`` float64 ``[N, GAUSS_PARAMS]`` (include/dwn.h).  One launch on the current stream; no read-back."""
+    _require_gpu(params, "gauss2d_profile")
+    _require_gpu(maps, "gauss2d_profile")
+    if maps.dim() != 4 or maps.dtype != torch.float32 or not maps.is_contiguous():
+        raise RuntimeError("sensorium_amd.gauss2d_profile: maps must be contiguous fp32 [N][L][gh][gw]")
+    N, lags, gh, gw = (int(n) for n in maps.shape)
+    if params.dtype != torch.float64 or tuple(params.shape) != (N, L.GAUSS_PARAMS) or not params.is_contiguous() or params.device != maps.device:
+        raise RuntimeError(f"sensorium_amd.gauss2d_profile: params must be contiguous float64 [{N}][{L.GAUSS_PARAMS}] on the maps' device")
+    dev = maps.device
+    a = L.Gauss2dProfileArgs()
+    a.N, a.L, a.gh, a.gw, a.fit_baseline = N, lags, gh, gw, int(bool(fit_baseline))
+    profile = torch.empty(N, lags, dtype=torch.float64, device=dev)
+    sep = torch.empty(N, dtype=torch.float64, device=dev)
+    a.params, a.maps, a.profile, a.separability = params.data_ptr(), maps.data_ptr(), profile.data_ptr(), sep.data_ptr()
+    L.check(L.lib.dwn_gauss2d_profile(C.byref(a), dev.index, _stream(dev)), "dwn_gauss2d_profile")
+    return profile, sep

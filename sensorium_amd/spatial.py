@@ -107,6 +107,35 @@ class SpatialGain(nn.Module):
         cells = (pos + 1.0) * 0.5 * scale
         return cells if units == "cells" else cells * float(self.stride)
 
+    @torch.no_grad()
+    def set_positions(self, index: int, xy: torch.Tensor, units: str = "normalised", neurons=None,
+                      map_size: Optional[Tuple[int, int]] = None) -> None:
+        """The inverse of ``positions``: writes ``xy`` [n][2] = (x, y) in ``units`` into the positions of mouse ``index``, in place
+        (rows ``neurons``, an index tensor or sequence; default all).  Non-finite values are refused; the result is clamped to
+        [-1, 1].  A map side of one cell has no extent: its coordinate is set to 0."""
+        pos = self.heads[index].pos
+        xy = torch.as_tensor(xy).detach().to(device=pos.device, dtype=torch.float64)
+        rows = None if neurons is None else torch.as_tensor(neurons, device=pos.device).long().flatten()
+        n = int(pos.shape[0]) if rows is None else int(rows.numel())
+        if xy.shape != (n, 2):
+            raise ValueError(f"SpatialGain.set_positions: xy must be [{n}][2] (got {tuple(xy.shape)})")
+        if not bool(torch.isfinite(xy).all()):
+            raise ValueError("SpatialGain.set_positions: non-finite position")
+        if units != "normalised":
+            if units not in ("cells", "input"):
+                raise ValueError("SpatialGain.set_positions: units must be 'normalised', 'cells' or 'input'")
+            size = map_size if map_size is not None else self._map_size
+            if size is None:
+                raise RuntimeError("SpatialGain.set_positions: the map's size is not known yet (pass map_size or run a forward)")
+            cells = xy if units == "cells" else xy / float(self.stride)
+            scale = torch.tensor([size[1] - 1, size[0] - 1], dtype=torch.float64, device=pos.device)
+            xy = torch.where(scale > 0, 2.0 * cells / scale.clamp(min=1.0) - 1.0, torch.zeros_like(cells))
+        new = xy.clamp(-1.0, 1.0).to(pos.dtype)
+        if rows is None:
+            pos.copy_(new)
+        else:
+            pos[rows] = new
+
     def extra_repr(self) -> str:
         return f"max_log_gain={self.max_log_gain}, features={self.features_out}, detach_core={self.detach_core}, stride={self.stride}"
 
@@ -147,6 +176,29 @@ class DwiseNeuroSpatial(DwiseNeuro):
     def positions(self, index: int, units: str = "normalised", input_size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
         """``SpatialGain.positions`` with the map's size derived from ``input_size`` = (H, W) of the video."""
         return self.spatial.positions(index, units, None if input_size is None else self.map_size(*input_size))
+
+    def set_positions_from(self, fits, index: int, *, input_size: Tuple[int, int], min_r2: float = 0.5, neurons=None) -> torch.Tensor:
+        """Writes the fitted receptive-field centres (``GaussianFits``) into the positions of mouse ``index``,
+        in input pixels, for the fits that pass ``fits.good(min_r2)``; every other neuron is left alone.  ``neurons``: the model's
+        neuron of every row of ``fits`` (default row k is neuron k).  Returns the index tensor of the neurons written."""
+        rows = fits.good(min_r2)
+        xy = fits.centres("input")[rows].flip(1)
+        dev = self.spatial.heads[index].pos.device
+        target = rows if neurons is None else torch.as_tensor(neurons, device=rows.device).long().flatten()[rows]
+        target = target.to(dev)
+        if target.numel():
+            self.spatial.set_positions(index, xy.to(dev), "input", neurons=target, map_size=self.map_size(*input_size))
+        return target
+
+    @torch.no_grad()
+    def position_error(self, fits, index: int, input_size: Tuple[int, int]) -> torch.Tensor:
+        """[N] distance in input pixels between the learned position and the fitted centre of every neuron of mouse ``index`` (row k
+        of ``fits`` is neuron k); NaN where a map has no fit."""
+        learned = self.positions(index, "input", input_size).double()
+        fitted = fits.centres("input").flip(1).to(learned.device)
+        if fitted.shape != learned.shape:
+            raise ValueError(f"position_error: {tuple(fitted.shape)} fitted centres for {tuple(learned.shape)} positions")
+        return (learned - fitted).norm(dim=1)
 
     def forward(self, x: torch.Tensor, index: Optional[int] = None):
         if x.dim() != 5:
