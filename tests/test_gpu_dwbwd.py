@@ -3,8 +3,8 @@ src/models/dwiseneuro.py:90-102) through the C-ABI entry dwn_dw_spatial_bwd, in 
 
 * the row-walk kernels on a stored y1 against the library's second implementation (dwn_dw_spatial_bwd_args.impl = 1: the pair /
   generic kernels): dh1 BIT-identical at stride 1 (same dot2 order) and within an ulp on a per-mille share at stride 2, dW and the
-  BatchNorm-backward sums to summation order / bf16 rounding of z1 (kernel against kernel: what the two share is pinned to the
-  oracle by tests/test_gpu_block.py);
+  BatchNorm-backward sums to summation order / bf16 rounding of z1 (kernel against kernel: what the two share is pinned to
+  float64, element by element on every dispatch path, by tests/test_gpu_dws3_paths.py);
 * the rebuilt-y1 kernels (y1 recomputed from the block input on the matrix cores) against the float64 backward of
   conv_pw -> BatchNorm-1 + SiLU -> 3x3 stencil (tests/dw_reference.py, pinned to the oracle by tests/test_dw_reference_cpu.py),
   beside the stored-y1 form on the same data: dh1, the 9-tap weight gradient and the two sums, both strides, Cin 64 and 128, band

@@ -3,7 +3,8 @@ the C-ABI entry dwn_dw_spatial_fwd, in two parts:
 
 * the chained row-walk kernels on a stored y1 against the library's second implementation, the pair kernel
   (dwn_dw_spatial_fwd_args.impl = 1): y2 BIT-identical, BatchNorm-2 sums to summation order, both strides, every band height
-  (kernel against kernel: what the two share is pinned to the oracle by tests/test_gpu_block.py);
+  (kernel against kernel: what the two share is pinned to float64, element by element on every dispatch path, by
+  tests/test_gpu_dws3_paths.py);
 * the rebuilt-input kernels (y1 = a0 . W1^T recomputed on the matrix cores, never stored) against the float64 reference of
   conv_pw -> BatchNorm-1 + SiLU -> 3x3 stencil (tests/dw_reference.py, pinned to the oracle by tests/test_dw_reference_cpu.py),
   beside the stored-y1 form on the same data: both strides, Cin 64 and 128, chunk heights, and 200 repeated launches."""
