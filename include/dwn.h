@@ -1077,6 +1077,96 @@ typedef struct dwn_gauss2d_profile_args {
 } dwn_gauss2d_profile_args;
 int dwn_gauss2d_profile(const dwn_gauss2d_profile_args* a, int device, void* stream);
 
+/* ---- population structure: the N x N correlation matrices of ONE mouse over whole trials, and their comparison.
+ * The frame cut and the grouping are those of the trial scores above: segment i is one fp32 row per neuron, `frames` contiguous
+ * values that start `first` elements into a row of stride ld (4-byte alignment only, every load is one fp32); the segments of a
+ * group are consecutive in the segment table and have the group's `frames`; the group table is a dwn_trial_group table (a trial
+ * that repeats nothing is a group of repeats = 1).  Both tables live in DEVICE memory and are validated by the caller; an entry
+ * beyond n_segs, max_repeats or max_frames is not followed.  With ybar[g][f] = (1/R) sum_r y[r][f] (float64, repeats in table
+ * order) the three sample sets are
+ *   DWN_PAIR_TOTAL   every (trial, frame), value y;                              a CHUNK is one trial, K values
+ *   DWN_PAIR_SIGNAL  the (group, frame) of groups with R >= 2, value ybar;       a chunk is one group, K values
+ *   DWN_PAIR_NOISE   the (group, repeat, frame) of those groups, value y - ybar; a chunk is one group, R K values (repeat-major)
+ * The noise set takes NO degrees-of-freedom correction: its co-moment is divided by its sample count R K like the others.
+ *
+ * state: double [N][N] C, then double [N] mean (dwn_pair_state_bytes(a) bytes, 8-byte aligned, zero before the first launch):
+ * C_ij = sum (x_i - mean_i)(x_j - mean_j) over the samples so far, stored full and bit-symmetric.  The caller keeps the sample
+ * count n (the state's BEFORE a stage launch, AFTER the last one for finalize) and advances it by what its tables hold.
+ *
+ * dwn_pair_stage: needs segs, groups, state, ws.  Writes Z = double [cols][ldz] into ws, k-major: column k holds ldz =
+ *   dwn_pair_ldz(N) = N rounded up to DWN_PAIR_TILE neurons, contiguous, zero beyond N.  Per chunk, in table order: the chunk's
+ *   mean m_b (a first sweep in a fixed order, float64), its n_b values centred about m_b (a second sweep; never a raw sum), one
+ *   merge column sqrt(n_a n_b / (n_a + n_b)) (m_b - m_a) with m_a, n_a the running mean and count (0 for an empty state, whose
+ *   mean becomes m_b), zero columns up to the next multiple of DWN_PAIR_KSTEP, and mean += (m_b - m_a) n_b / (n_a + n_b).  So
+ *   Z Z^T is exactly the pairwise (Chan) merge of the chunks and the product knows nothing about chunks.  cols = the sum over
+ *   the chunks of (n_b + 1) rounded up to DWN_PAIR_KSTEP; a chunk that would pass `cols` is not followed.
+ * dwn_pair_syrk: needs state, ws (Z as staged).  C += Z Z^T in float64 on v_mfma_f64_16x16x4_f64.  Only the tiles on and below
+ *   the diagonal are computed and their owner writes the mirror; every element has one accumulator that starts from C and walks
+ *   the columns in ascending order, K is never split: given the same chunks the state's bits do not depend on how the caller
+ *   cuts them into launches.
+ * dwn_pair_corr_finalize: needs state, out.  out[i][j] = (C_ij / n) / ((sqrt(C_ii / n) + eps)(sqrt(C_jj / n) + eps)) in float64,
+ *   stored as double or (out_f32) rounded once to fp32; [N][N] contiguous, apart from the state.  n == 0 gives NaN everywhere, a
+ *   constant neuron a row and a column of exact zeros.
+ * A non-finite value of neuron i reaches only row i and column i of C and of out (and mean[i]).
+ *
+ * dwn_pair_compare: A (model), B (data) double [N][N] with leading dimensions lda, ldb; sel int32 [M] device table of neurons or
+ *   NULL (neurons 0 .. M-1, which needs M <= N).  per_neuron double [M]: for the selected neuron i the Pearson correlation (the
+ *   convention above, with eps) of A[i][j] with B[i][j] over the selected j != i: one wave per row, centred float64 moments in
+ *   two sweeps closed by a fixed butterfly.  summary double [DWN_PAIR_SUMMARY]: 0 the number of ordered pairs, 1 the Pearson
+ *   correlation over all of them, 2, 3 mean of A, B, 4, 5 their standard deviations, 6 mean |A - B|, 7 RMS of A - B; the row
+ *   moments (DWN_PAIR_ROW_STATS doubles per row in ws, dwn_pair_compare_ws_bytes(a) bytes, 8-byte aligned) are merged in row
+ *   order with the pairwise formulas by one workgroup.  A NaN entry makes its row's score and the summary NaN, as does a sel
+ *   entry outside [0, N); nothing is skipped silently.  M = 1 has no pair: NaN.
+ *
+ * Nothing is allocated and nothing is read back; no atomics, no scratch; both builds give the same bits.  Argument errors are
+ * answered before the device is entered: null pointer -1; geometry -2 (N outside [1, 65535], an unknown kind, table sizes,
+ * max_repeats, max_frames, cols not a positive multiple of DWN_PAIR_KSTEP, a negative count or one at or above 2^52, eps <= 0, M
+ * outside [1, N] (sel NULL) or [1, 2^20], a leading dimension below N, a misaligned state / out / matrix); workspace too small or
+ * misaligned (16 bytes for Z) -3.  The size queries return 0 for arguments the entries would refuse. */
+enum { DWN_PAIR_TOTAL = 0, DWN_PAIR_SIGNAL = 1, DWN_PAIR_NOISE = 2 };
+#define DWN_PAIR_TILE 64
+#define DWN_PAIR_KSTEP 4
+#define DWN_PAIR_SUMMARY 8
+#define DWN_PAIR_ROW_STATS 8
+typedef struct dwn_pair_seg {
+    const float* x;
+    long long ld;                     /* elements between consecutive neurons' rows */
+    int first, frames;                /* the kept frames of a row: [first, first + frames) */
+} dwn_pair_seg;
+typedef struct dwn_pair_args {
+    int N, kind;                      /* DWN_PAIR_TOTAL / _SIGNAL / _NOISE (stage) */
+    int n_segs, n_groups;
+    int max_repeats, max_frames;      /* upper bounds of the group table's repeats and frames */
+    int cols;                         /* columns of Z */
+    int out_f32;                      /* finalize: out is fp32 */
+    long long n;                      /* samples of the state: before the launch (stage), after the last one (finalize) */
+    double eps;                       /* finalize: added to each standard deviation (> 0) */
+    const dwn_pair_seg* segs;         /* device, [n_segs] */
+    const dwn_trial_group* groups;    /* device, [n_groups] */
+    double* state;
+    void* out;
+    void* ws; size_t ws_bytes;
+} dwn_pair_args;
+typedef struct dwn_pair_compare_args {
+    int N, M;
+    long long lda, ldb;
+    double eps;
+    const double* A;
+    const double* B;
+    const int* sel;                   /* device [M] or NULL */
+    double* per_neuron;
+    double* summary;
+    void* ws; size_t ws_bytes;
+} dwn_pair_compare_args;
+long long dwn_pair_ldz(int N);                                   /* 0 for an N the entries refuse */
+size_t dwn_pair_state_bytes(const dwn_pair_args* a);
+size_t dwn_pair_ws_bytes(const dwn_pair_args* a);                /* Z: cols * dwn_pair_ldz(N) doubles */
+size_t dwn_pair_compare_ws_bytes(const dwn_pair_compare_args* a);
+int dwn_pair_stage(const dwn_pair_args* a, int device, void* stream);
+int dwn_pair_syrk(const dwn_pair_args* a, int device, void* stream);
+int dwn_pair_corr_finalize(const dwn_pair_args* a, int device, void* stream);
+int dwn_pair_compare(const dwn_pair_compare_args* a, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -241,6 +241,21 @@ class TrialScoreArgs(C.Structure):        # (include/dwn.h dwn_trial_score_args)
                 ("trials", c_p), ("groups", c_p), ("state", c_p), ("scores", c_p), ("summary", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
 
 
+class PairSeg(C.Structure):               # population structure (include/dwn.h dwn_pair_seg: one row of the DEVICE segment table)
+    _fields_ = [("x", c_p), ("ld", c_ll), ("first", c_i), ("frames", c_i)]
+
+
+class PairArgs(C.Structure):              # (include/dwn.h dwn_pair_args)
+    _fields_ = [("N", c_i), ("kind", c_i), ("n_segs", c_i), ("n_groups", c_i), ("max_repeats", c_i), ("max_frames", c_i),
+                ("cols", c_i), ("out_f32", c_i), ("n", c_ll), ("eps", c_d), ("segs", c_p), ("groups", c_p), ("state", c_p),
+                ("out", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
+
+
+class PairCompareArgs(C.Structure):       # (include/dwn.h dwn_pair_compare_args)
+    _fields_ = [("N", c_i), ("M", c_i), ("lda", c_ll), ("ldb", c_ll), ("eps", c_d), ("A", c_p), ("B", c_p), ("sel", c_p),
+                ("per_neuron", c_p), ("summary", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
+
+
 class SpatialGainArgs(C.Structure):       # retinotopic readout gain (include/dwn.h dwn_spatial_gain_args)
     _fields_ = [("B", c_i), ("N", c_i), ("T", c_i), ("Hf", c_i), ("Wf", c_i), ("K", c_i), ("g_dtype", c_i), ("max_log_gain", c_f),
                 ("y", c_p), ("g", c_p), ("pos", c_p), ("weight", c_p), ("bias", c_p), ("out", c_p), ("dout", c_p), ("dy", c_p),
@@ -282,6 +297,8 @@ TRIAL_STATE_ROWS, TRIAL_SCORE_ROWS, TRIAL_SUMMARY, TRIAL_TILE = 17, 5, 8, 4     
 NOISE_BINARY, NOISE_SPARSE = 0, 1          # DWN_NOISE_*
 STA_SUMMARY = 8                            # DWN_STA_SUMMARY
 GAUSS_PARAMS, GAUSS_TABLE = 7, 16          # DWN_GAUSS_*
+PAIR_TOTAL, PAIR_SIGNAL, PAIR_NOISE = 0, 1, 2                  # DWN_PAIR_*
+PAIR_TILE, PAIR_KSTEP, PAIR_SUMMARY, PAIR_ROW_STATS = 64, 4, 8, 8
 MIX_BOX, MIX_BLEND = 0, 1
 VID_U8, VID_F32 = 0, 1
 
@@ -299,6 +316,7 @@ _STRUCTS = {
     "dwn_trial_desc": TrialDesc, "dwn_trial_group": TrialGroup, "dwn_trial_score_args": TrialScoreArgs,
     "dwn_spatial_gain_args": SpatialGainArgs, "dwn_noise_args": NoiseArgs, "dwn_sta_args": StaArgs,
     "dwn_gauss2d_args": Gauss2dArgs, "dwn_gauss2d_profile_args": Gauss2dProfileArgs,
+    "dwn_pair_seg": PairSeg, "dwn_pair_args": PairArgs, "dwn_pair_compare_args": PairCompareArgs,
 }
 
 # every symbol include/dwn.h declares: (restype, argtypes)
@@ -385,6 +403,15 @@ SYMBOLS = {
     "dwn_spatial_gain_ws_bytes": (c_sz, [_P(SpatialGainArgs)]),
     "dwn_spatial_gain_forward": (c_i, [_P(SpatialGainArgs), c_i, c_p]),
     "dwn_spatial_gain_backward": (c_i, [_P(SpatialGainArgs), c_i, c_p]),
+    # (the population structure of dwn_pairwise.hip)
+    "dwn_pair_ldz": (c_ll, [c_i]),
+    "dwn_pair_state_bytes": (c_sz, [_P(PairArgs)]),
+    "dwn_pair_ws_bytes": (c_sz, [_P(PairArgs)]),
+    "dwn_pair_compare_ws_bytes": (c_sz, [_P(PairCompareArgs)]),
+    "dwn_pair_stage": (c_i, [_P(PairArgs), c_i, c_p]),
+    "dwn_pair_syrk": (c_i, [_P(PairArgs), c_i, c_p]),
+    "dwn_pair_corr_finalize": (c_i, [_P(PairArgs), c_i, c_p]),
+    "dwn_pair_compare": (c_i, [_P(PairCompareArgs), c_i, c_p]),
     # (the parametric fits of dwn_rf_fit.hip; tests/test_host_rf.py keeps the five receptive-field entries last)
     "dwn_gauss2d_ws_bytes": (c_sz, [_P(Gauss2dArgs)]),
     "dwn_gauss2d_fit": (c_i, [_P(Gauss2dArgs), c_i, c_p]),
@@ -404,7 +431,7 @@ class DwnError(RuntimeError):
 # csrc/Makefile HASH_SRCS, in its order
 HASH_SRCS = ("dwn_api.hip", "dwn_gemm.hip", "dwn_gemm_nn_1.hip", "dwn_gemm_nn_2.hip", "dwn_gemm_nn_3.hip", "dwn_gemm_nn_4.hip", "dwn_gemm_nn_5.hip",
              "dwn_gemm_nn_6.hip", "dwn_gemm_tn.hip", "dwn_pw_bwd.hip", "dwn_gemm_xl.hip", "dwn_gemm_kd.hip", "dwn_dwconv.hip", "dwn_dwrc.hip",
-             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_spatial.hip", "dwn_mei.hip", "dwn_rf_fit.hip", "dwn_trial_score.hip", "dwn_rf.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
+             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_spatial.hip", "dwn_mei.hip", "dwn_rf_fit.hip", "dwn_pairwise.hip", "dwn_trial_score.hip", "dwn_rf.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
              "dwn_kernels.h", "dwn_launch.h", "dwn_gemm_nn.h", "dwn_gain.h",
              "../../include/dwn.h")
 
@@ -436,8 +463,10 @@ def _load():
                            "dwn_trial_score_finalize", "dwn_spatial_gain_ws_bytes", "dwn_spatial_gain_forward",
                            "dwn_spatial_gain_backward", "dwn_noise_forward", "dwn_sta_state_bytes", "dwn_sta_ws_bytes",
                            "dwn_sta_accumulate", "dwn_sta_finalize", "dwn_gauss2d_ws_bytes", "dwn_gauss2d_fit",
-                           "dwn_gauss2d_profile") and not hasattr(lib, name):
-            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator / the MEI kernels / the trial scores / the retinotopic readout gain / the receptive-field mapping / the parametric fits; the plain training step calls none of them)
+                           "dwn_gauss2d_profile", "dwn_pair_ldz", "dwn_pair_state_bytes", "dwn_pair_ws_bytes",
+                           "dwn_pair_compare_ws_bytes", "dwn_pair_stage", "dwn_pair_syrk", "dwn_pair_corr_finalize",
+                           "dwn_pair_compare") and not hasattr(lib, name):
+            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator / the MEI kernels / the trial scores / the retinotopic readout gain / the receptive-field mapping / the parametric fits / the population structure; the plain training step calls none of them)
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -449,7 +478,7 @@ def _load():
                           f"`make -C {LIB_PATH.parent}` — binaries are not in git, so what runs must be what is committed")
     for cname, struct in _STRUCTS.items():
         n = lib.dwn_sizeof(cname.encode())
-        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args", "dwn_blur3d_args", "dwn_clip_moments_args", "dwn_mei_update_args", "dwn_trial_desc", "dwn_trial_group", "dwn_trial_score_args", "dwn_spatial_gain_args", "dwn_noise_args", "dwn_sta_args", "dwn_gauss2d_args", "dwn_gauss2d_profile_args"))):      # (A/B: ABI 7 only appended)
+        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args", "dwn_blur3d_args", "dwn_clip_moments_args", "dwn_mei_update_args", "dwn_trial_desc", "dwn_trial_group", "dwn_trial_score_args", "dwn_spatial_gain_args", "dwn_noise_args", "dwn_sta_args", "dwn_gauss2d_args", "dwn_gauss2d_profile_args", "dwn_pair_seg", "dwn_pair_args", "dwn_pair_compare_args"))):      # (A/B: ABI 7 only appended)
             raise ImportError(f"struct layout mismatch for {cname}: C {n} bytes vs ctypes {C.sizeof(struct)}")
     return lib
 

@@ -312,6 +312,7 @@ int dwn_sizeof(const char* name) {
     SZ(dwn_blur3d_args); SZ(dwn_clip_moments_args); SZ(dwn_mei_update_args);
     SZ(dwn_trial_desc); SZ(dwn_trial_group); SZ(dwn_trial_score_args);
     SZ(dwn_noise_args); SZ(dwn_sta_args); SZ(dwn_gauss2d_args); SZ(dwn_gauss2d_profile_args);
+    SZ(dwn_pair_seg); SZ(dwn_pair_args); SZ(dwn_pair_compare_args);
 #undef SZ
     return -1;
 }
@@ -1441,6 +1442,81 @@ int dwn_trial_score_finalize(const dwn_trial_score_args* a, int device, void* st
     if (a->ws_bytes < k_trial_score_ws_bytes(a->N) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "trial_score_finalize: workspace smaller than dwn_trial_score_ws_bytes or not 8-byte aligned");
     ENTER(device);
     return k_trial_score_finalize(*a, (hipStream_t)stream);
+}
+
+// ---- population structure: the argument checks need no device
+static int pair_state(const dwn_pair_args* a, const char* who) {
+    static char msg[96];
+    const char* what = nullptr;
+    if (a->N <= 0 || a->N > 65535) what = "N outside [1, 65535]";
+    else if (a->n < 0 || a->n >= (1ll << 52)) what = "the sample count must lie in [0, 2^52)";
+    if (!what) return 0;
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return dwn_set_error(-2, msg);
+}
+static bool pair_cols_ok(const dwn_pair_args* a) { return a->cols > 0 && a->cols % DWN_PAIR_KSTEP == 0; }
+long long dwn_pair_ldz(int N) { return N > 0 && N <= 65535 ? k_pair_ldz(N) : 0; }
+size_t dwn_pair_state_bytes(const dwn_pair_args* a) {
+    return a && a->N > 0 && a->N <= 65535 ? ((size_t)a->N * a->N + (size_t)a->N) * sizeof(double) : 0;
+}
+size_t dwn_pair_ws_bytes(const dwn_pair_args* a) {
+    return a && a->N > 0 && a->N <= 65535 && pair_cols_ok(a) ? (size_t)a->cols * (size_t)k_pair_ldz(a->N) * sizeof(double) : 0;
+}
+size_t dwn_pair_compare_ws_bytes(const dwn_pair_compare_args* a) {
+    if (!a || a->N <= 0 || a->N > 65535 || a->M < 1 || a->M > (1 << 20) || (!a->sel && a->M > a->N)) return 0;
+    return k_pair_compare_ws_bytes(a->M);
+}
+int dwn_pair_stage(const dwn_pair_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "pair_stage: null arguments");
+    TRY(pair_state(a, "pair_stage"));
+    if (a->kind != DWN_PAIR_TOTAL && a->kind != DWN_PAIR_SIGNAL && a->kind != DWN_PAIR_NOISE) return dwn_set_error(-2, "pair_stage: unknown kind");
+    if (a->n_segs <= 0 || a->n_groups <= 0 || a->n_groups > a->n_segs) return dwn_set_error(-2, "pair_stage: needs 1 <= n_groups <= n_segs");
+    if (a->max_repeats < 1 || a->max_repeats > a->n_segs) return dwn_set_error(-2, "pair_stage: max_repeats must lie in [1, n_segs]");
+    if (a->max_frames < 1) return dwn_set_error(-2, "pair_stage: max_frames must be positive");
+    if ((long long)a->n_segs * a->max_frames >= (1ll << 52) - a->n) return dwn_set_error(-2, "pair_stage: the count after the launch must stay below 2^52");
+    if (!pair_cols_ok(a)) return dwn_set_error(-2, "pair_stage: cols must be a positive multiple of DWN_PAIR_KSTEP");
+    if (!a->segs || !a->groups || !a->state || !a->ws) return dwn_set_error(-1, "pair_stage: null pointer (segs, groups, state, ws)");
+    if ((size_t)a->state & 7) return dwn_set_error(-2, "pair_stage: state must be 8-byte aligned");
+    if (a->ws_bytes < dwn_pair_ws_bytes(a) || ((size_t)a->ws & 15)) return dwn_set_error(-3, "pair_stage: workspace smaller than dwn_pair_ws_bytes or not 16-byte aligned");
+    ENTER(device);
+    return k_pair_stage(*a, (hipStream_t)stream);
+}
+int dwn_pair_syrk(const dwn_pair_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "pair_syrk: null arguments");
+    TRY(pair_state(a, "pair_syrk"));
+    if (!pair_cols_ok(a)) return dwn_set_error(-2, "pair_syrk: cols must be a positive multiple of DWN_PAIR_KSTEP");
+    if (!a->state || !a->ws) return dwn_set_error(-1, "pair_syrk: null pointer (state, ws)");
+    if ((size_t)a->state & 7) return dwn_set_error(-2, "pair_syrk: state must be 8-byte aligned");
+    if (a->ws_bytes < dwn_pair_ws_bytes(a) || ((size_t)a->ws & 15)) return dwn_set_error(-3, "pair_syrk: workspace smaller than dwn_pair_ws_bytes or not 16-byte aligned");
+    ENTER(device);
+    return k_pair_syrk(*a, (hipStream_t)stream);
+}
+int dwn_pair_corr_finalize(const dwn_pair_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "pair_corr_finalize: null arguments");
+    TRY(pair_state(a, "pair_corr_finalize"));
+    if (!(a->eps > 0.0)) return dwn_set_error(-2, "pair_corr_finalize: eps must be positive");
+    if (!a->state || !a->out) return dwn_set_error(-1, "pair_corr_finalize: null pointer (state, out)");
+    if (((size_t)a->state & 7) || ((size_t)a->out & (a->out_f32 ? 3 : 7))) return dwn_set_error(-2, "pair_corr_finalize: state or out misaligned");
+    ENTER(device);
+    return k_pair_corr_finalize(*a, (hipStream_t)stream);
+}
+int dwn_pair_compare(const dwn_pair_compare_args* a, int device, void* stream) {
+    g_err[0] = 0;
+    if (!a) return dwn_set_error(-1, "pair_compare: null arguments");
+    if (a->N <= 0 || a->N > 65535) return dwn_set_error(-2, "pair_compare: N outside [1, 65535]");
+    if (a->M < 1 || a->M > (1 << 20)) return dwn_set_error(-2, "pair_compare: M outside [1, 2^20]");
+    if (!a->sel && a->M > a->N) return dwn_set_error(-2, "pair_compare: without sel M must not exceed N");
+    if (a->lda < a->N || a->ldb < a->N) return dwn_set_error(-2, "pair_compare: a leading dimension below N");
+    if (!(a->eps > 0.0)) return dwn_set_error(-2, "pair_compare: eps must be positive");
+    if (!a->A || !a->B || !a->per_neuron || !a->summary || !a->ws) return dwn_set_error(-1, "pair_compare: null pointer (A, B, per_neuron, summary, ws)");
+    if (((size_t)a->A & 7) || ((size_t)a->B & 7) || ((size_t)a->per_neuron & 7) || ((size_t)a->summary & 7) || ((size_t)a->sel & 3))
+        return dwn_set_error(-2, "pair_compare: A, B, per_neuron, summary or sel misaligned");
+    if (a->ws_bytes < k_pair_compare_ws_bytes(a->M) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "pair_compare: workspace smaller than dwn_pair_compare_ws_bytes or not 8-byte aligned");
+    ENTER(device);
+    return k_pair_compare(*a, (hipStream_t)stream);
 }
 
 // ---- retinotopic readout gain: the argument checks need no device

@@ -157,6 +157,13 @@ int k_sta_finalize(const dwn_sta_args& a, hipStream_t s);                    // 
 size_t k_gauss2d_ws_bytes(const dwn_gauss2d_args& a);
 int k_gauss2d_fit(const dwn_gauss2d_args& a, hipStream_t s);                  // one wave per map, one launch
 int k_gauss2d_profile(const dwn_gauss2d_profile_args& a, hipStream_t s);      // one wave per neuron
+// population structure (dwn.h dwn_pair_args, dwn_pair_compare_args; dwn_pairwise.hip): arguments checked by the C-ABI layer
+long long k_pair_ldz(int N);
+size_t k_pair_compare_ws_bytes(int M);
+int k_pair_stage(const dwn_pair_args& a, hipStream_t s);                      // Z into a.ws, advances the state's mean
+int k_pair_syrk(const dwn_pair_args& a, hipStream_t s);                       // C += Z Z^T
+int k_pair_corr_finalize(const dwn_pair_args& a, hipStream_t s);
+int k_pair_compare(const dwn_pair_compare_args& a, hipStream_t s);            // row moments into a.ws, then the one-workgroup merge
 int k_pw_bwd_prep(const float* w1, const float* abc, int E, int C, void* bp, float* gacc, float* r3, int dtype,
                   const float* res_abc, int res_C, hipStream_t s);
 // conv_pw weight gradient from the raw products (see pw_bwd_fused_kernel): tacc [(E + C + 8)][C] fp32 = rows T1 = dh1^T a0,

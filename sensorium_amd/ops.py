@@ -1207,6 +1207,140 @@ def trial_scores(state: torch.Tensor, counts, eps: float = 1e-8, fev_threshold: 
 
 
 # ------------------------------------------------------------------------------------------------
+# population structure (sensorium_amd/population.py)
+# ------------------------------------------------------------------------------------------------
+_PAIR_SEG = np.dtype([("x", "<u8"), ("ld", "<i8"), ("first", "<i4"), ("frames", "<i4")])
+assert _PAIR_SEG.itemsize == C.sizeof(L.PairSeg)
+PAIR_KINDS = {"total": L.PAIR_TOTAL, "signal": L.PAIR_SIGNAL, "noise": L.PAIR_NOISE}
+
+
+def pair_chunk_cols(kind: str, repeats: int, frames: int) -> int:
+    """The columns of Z the chunks of one group take (include/dwn.h): per chunk its values and the merge column, rounded up to
+    the k-step.  ``total``: one chunk per trial; ``signal`` / ``noise``: one per group of at least two repeats."""
+    up = lambda n: -(-(n + 1) // L.PAIR_KSTEP) * L.PAIR_KSTEP      # noqa: E731
+    if kind == "total":
+        return repeats * up(frames)
+    if repeats < 2:
+        return 0
+    return up(frames) if kind == "signal" else up(repeats * frames)
+
+
+def pair_samples(kind: str, repeats: int, frames: int) -> int:
+    """The samples the chunks of one group add to the state of ``kind``."""
+    if kind == "total":
+        return repeats * frames
+    if repeats < 2:
+        return 0
+    return frames if kind == "signal" else repeats * frames
+
+
+def _pair_state(state: torch.Tensor, what: str):
+    _require_gpu(state, what)
+    if state.dtype != torch.float64 or state.dim() != 2 or state.shape[0] != state.shape[1] + 1 or not state.is_contiguous():
+        raise RuntimeError(f"sensorium_amd.{what}: state must be contiguous float64 [N + 1, N] (the co-moments, then the mean)")
+    return state.device, int(state.shape[1])
+
+
+def pair_tables(trials, groups, N: int, dev, what: str = "pair_accumulate"):
+    """The device segment and group tables of ``trials`` (``(x, first, frames)`` with ``x`` a GPU fp32 ``[N, L]`` tensor of unit
+    stride along frames) and ``groups`` (``(first_trial, repeats, frames)`` covering the trials in order), after the checks the
+    kernels rely on.  Returns ``(segs, groups, host group table)``."""
+    trials, groups = list(trials), list(groups)
+    if not trials or not groups:
+        raise ValueError(f"sensorium_amd.{what}: no trials")
+    sd = np.zeros(len(trials), dtype=_PAIR_SEG)
+    for i, (x, first, frames) in enumerate(trials):
+        first, frames = int(first), int(frames)
+        sd[i] = (x.data_ptr(), _trial_rows(x, N, first, frames, dev, what), first, frames)
+    gd = np.zeros(len(groups), dtype=_TRIAL_GROUP)
+    at = 0
+    for i, (first_trial, repeats, frames) in enumerate(groups):
+        first_trial, repeats, frames = int(first_trial), int(repeats), int(frames)
+        if first_trial != at or repeats < 1 or at + repeats > len(trials):
+            raise ValueError(f"sensorium_amd.{what}: group {i} does not continue the trial table")
+        if any(int(sd[k]["frames"]) != frames for k in range(at, at + repeats)):
+            raise ValueError(f"sensorium_amd.{what}: group {i}: its trials do not all have {frames} frames")
+        gd[i] = (first_trial, repeats, frames)
+        at += repeats
+    if at != len(trials):
+        raise ValueError(f"sensorium_amd.{what}: the groups do not cover every trial")
+    return torch.from_numpy(sd.view(np.uint8)).to(dev), torch.from_numpy(gd.view(np.uint8)).to(dev), gd
+
+
+def pair_accumulate(state: torch.Tensor, kind: str, tables, count: int = 0, ws: Optional[torch.Tensor] = None,
+                    return_staged: bool = False):
+    """dwn_pair_stage + dwn_pair_syrk: merges the chunks of ``tables`` (of ``pair_tables``) into ``state`` (float64 ``[N + 1, N]``:
+    the centred co-moments ``C`` and, last row, the mean; zero before the first call) in place.  ``kind``: ``total`` / ``signal``
+    / ``noise``; ``count``: the samples of the state before the call; returns the count after it.  ``ws``: a float64 tensor to
+    stage ``Z`` in (at least ``cols * dwn_pair_ldz(N)`` elements), allocated when absent.  Tables without a chunk of this kind
+    launch nothing.  ``return_staged`` also returns ``Z`` as a ``[cols, ldz]`` view (for measurements and tests)."""
+    dev, N = _pair_state(state, "pair_accumulate")
+    if kind not in PAIR_KINDS:
+        raise ValueError(f"sensorium_amd.pair_accumulate: kind must be one of {tuple(PAIR_KINDS)}, got {kind!r}")
+    segs, grps, gd = tables
+    cols = sum(pair_chunk_cols(kind, int(g["repeats"]), int(g["frames"])) for g in gd)
+    added = sum(pair_samples(kind, int(g["repeats"]), int(g["frames"])) for g in gd)
+    if cols == 0:
+        return (int(count), None) if return_staged else int(count)
+    ldz = int(L.lib.dwn_pair_ldz(N))
+    if ws is None:
+        ws = torch.empty(cols * ldz, dtype=torch.float64, device=dev)
+    _require_gpu(ws, "pair_accumulate")
+    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() < cols * ldz or ws.device != dev:
+        raise ValueError(f"sensorium_amd.pair_accumulate: ws must be a contiguous float64 tensor of at least {cols * ldz} elements on {dev}")
+    a = L.PairArgs()
+    a.N, a.kind, a.n_segs, a.n_groups = N, PAIR_KINDS[kind], int(segs.numel()) // _PAIR_SEG.itemsize, len(gd)
+    a.max_repeats, a.max_frames, a.cols, a.n = int(gd["repeats"].max()), int(gd["frames"].max()), cols, int(count)
+    a.segs, a.groups, a.state, a.ws, a.ws_bytes = segs.data_ptr(), grps.data_ptr(), state.data_ptr(), ws.data_ptr(), ws.numel() * 8
+    L.check(L.lib.dwn_pair_stage(C.byref(a), dev.index, _stream(dev)), "dwn_pair_stage")
+    L.check(L.lib.dwn_pair_syrk(C.byref(a), dev.index, _stream(dev)), "dwn_pair_syrk")
+    if return_staged:
+        return int(count) + added, ws[:cols * ldz].view(cols, ldz)
+    return int(count) + added
+
+
+def pair_corr(state: torch.Tensor, count: int, eps: float = 1e-8, dtype: torch.dtype = torch.float64) -> torch.Tensor:
+    """dwn_pair_corr_finalize: the ``[N, N]`` correlation matrix of a state and its sample count, float64 or (rounded once)
+    fp32.  The state is left as it is.  No read-back."""
+    dev, N = _pair_state(state, "pair_corr")
+    if dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"sensorium_amd.pair_corr: dtype must be float64 or float32, got {dtype}")
+    out = torch.empty(N, N, dtype=dtype, device=dev)
+    a = L.PairArgs()
+    a.N, a.n, a.eps, a.out_f32 = N, int(count), float(eps), int(dtype == torch.float32)
+    a.state, a.out = state.data_ptr(), out.data_ptr()
+    L.check(L.lib.dwn_pair_corr_finalize(C.byref(a), dev.index, _stream(dev)), "dwn_pair_corr_finalize")
+    return out
+
+
+def pair_compare(A: torch.Tensor, B: torch.Tensor, sel: Optional[torch.Tensor] = None, eps: float = 1e-8):
+    """dwn_pair_compare: ``(per_neuron [M], summary [PAIR_SUMMARY])`` float64 device tensors for two float64 ``[N, N]`` matrices
+    (unit stride along columns, any row stride) and an optional int32 device selection ``sel [M]``.  No read-back."""
+    for t in (A, B):
+        _require_gpu(t, "pair_compare")
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[0] != t.shape[1] or t.shape != A.shape or t.device != A.device:
+            raise ValueError("sensorium_amd.pair_compare: A and B must be float64 [N, N] matrices of one size on one device")
+        if t.shape[1] > 1 and t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+            raise ValueError("sensorium_amd.pair_compare: rows must have unit stride and must not overlap")
+    dev, N = A.device, int(A.shape[0])
+    M = N
+    if sel is not None:
+        _require_gpu(sel, "pair_compare")
+        if sel.dtype != torch.int32 or sel.dim() != 1 or not sel.is_contiguous() or sel.numel() < 1 or sel.device != dev:
+            raise ValueError("sensorium_amd.pair_compare: sel must be a non-empty contiguous 1-D int32 tensor on the matrices' device")
+        M = int(sel.numel())
+    per = torch.empty(M, dtype=torch.float64, device=dev)
+    summary = torch.empty(L.PAIR_SUMMARY, dtype=torch.float64, device=dev)
+    a = L.PairCompareArgs()
+    a.N, a.M, a.lda, a.ldb, a.eps = N, M, int(A.stride(0)), int(B.stride(0)), float(eps)
+    ws = torch.empty(max(int(L.lib.dwn_pair_compare_ws_bytes(C.byref(a))) // 8, 1), dtype=torch.float64, device=dev)
+    a.A, a.B, a.sel = A.data_ptr(), B.data_ptr(), (sel.data_ptr() if sel is not None else None)
+    a.per_neuron, a.summary, a.ws, a.ws_bytes = per.data_ptr(), summary.data_ptr(), ws.data_ptr(), ws.numel() * 8
+    L.check(L.lib.dwn_pair_compare(C.byref(a), dev.index, _stream(dev)), "dwn_pair_compare")
+    return per, summary
+
+
+# ------------------------------------------------------------------------------------------------
 # retinotopic readout gain (DESIGN.md 12p; sensorium_amd/spatial.py)
 # ------------------------------------------------------------------------------------------------
 def _spatial_gain_args(y, g, pos, weight, bias, max_log_gain: float) -> L.SpatialGainArgs:
