@@ -302,14 +302,19 @@ PAIR_TILE, PAIR_KSTEP, PAIR_SUMMARY, PAIR_ROW_STATS = 64, 4, 8, 8
 MIX_BOX, MIX_BLEND = 0, 1
 VID_U8, VID_F32 = 0, 1
 
-_STRUCTS = {
+_OLD_STRUCTS = {
     "dwn_load_desc": LoadDesc, "dwn_gemm_nn_args": GemmNNArgs, "dwn_gemm_tn_args": GemmTNArgs,
     "dwn_dw_spatial_fwd_args": DwSpatialFwdArgs, "dwn_dw_spatial_bwd_args": DwSpatialBwdArgs,
     "dwn_dw_temporal_fwd_args": DwTemporalFwdArgs, "dwn_dw_temporal_bwd_args": DwTemporalBwdArgs,
     "dwn_bn": BN, "dwn_stem_args": StemArgs, "dwn_block_args": BlockArgs, "dwn_pool_args": PoolArgs,
     "dwn_cortex_args": CortexArgs, "dwn_readout_args": ReadoutArgs, "dwn_tensor_entry": TensorEntry,
     "dwn_clip_src": ClipSrc, "dwn_clip_desc": ClipDesc, "dwn_pw_bwd_args": PwBwdArgs,
-    "dwn_dw_spatial_rc_fwd_args": DwSpatialRcFwdArgs, "dwn_stem_input_grad_args": StemInputGradArgs,
+    "dwn_dw_spatial_rc_fwd_args": DwSpatialRcFwdArgs,
+}
+# structs appended after the oldest library an A/B run (DWN_LIB_PATH) may load: that library may not know them.  A new struct
+# goes at the end of this dict.
+_NEW_STRUCTS = {
+    "dwn_stem_input_grad_args": StemInputGradArgs,
     "dwn_guarded_entry": GuardedEntry, "dwn_step_guard": StepGuard, "dwn_gaze_args": GazeArgs,
     "dwn_corr_args": CorrArgs, "dwn_gabor_args": GaborArgs, "dwn_modulator_args": ModulatorArgs,
     "dwn_blur3d_args": Blur3dArgs, "dwn_clip_moments_args": ClipMomentsArgs, "dwn_mei_update_args": MeiUpdateArgs,
@@ -318,6 +323,15 @@ _STRUCTS = {
     "dwn_gauss2d_args": Gauss2dArgs, "dwn_gauss2d_profile_args": Gauss2dProfileArgs,
     "dwn_pair_seg": PairSeg, "dwn_pair_args": PairArgs, "dwn_pair_compare_args": PairCompareArgs,
 }
+_STRUCTS = {**_OLD_STRUCTS, **_NEW_STRUCTS}
+
+
+class _new(tuple):
+    """(restype, argtypes) of an entry appended after the oldest library an A/B run (DWN_LIB_PATH) may load: that library may
+    lack it (the plain training step calls none of them).  A new entry is written _new(...)."""
+    def __new__(cls, restype, argtypes):
+        return super().__new__(cls, (restype, argtypes))
+
 
 # every symbol include/dwn.h declares: (restype, argtypes)
 _P = C.POINTER
@@ -336,16 +350,16 @@ SYMBOLS = {
     "dwn_dw_spatial_fwd_rc_supported": (c_i, [_P(DwSpatialFwdArgs), c_i]),
     "dwn_dw_temporal_fwd": (c_i, [_P(DwTemporalFwdArgs), c_i, c_i, c_p]),
     "dwn_dw_temporal_bwd": (c_i, [_P(DwTemporalBwdArgs), c_i, c_i, c_p]),
-    "dwn_dw_temporal_wide_fwd": (c_i, [_P(DwTemporalFwdArgs), c_i, c_i, c_p]),
-    "dwn_dw_temporal_wide_bwd": (c_i, [_P(DwTemporalBwdArgs), c_i, c_i, c_p]),
+    "dwn_dw_temporal_wide_fwd": _new(c_i, [_P(DwTemporalFwdArgs), c_i, c_i, c_p]),
+    "dwn_dw_temporal_wide_bwd": _new(c_i, [_P(DwTemporalBwdArgs), c_i, c_i, c_p]),
     "dwn_bn_finalize": (c_i, [c_p, c_i, c_d, _P(BN), c_i, c_i, c_f, c_f, c_i, c_p]),
     "dwn_bn_bwd_finalize": (c_i, [c_p, c_d, _P(BN), c_p, c_i, c_i, c_p]),
     "dwn_pack_weight": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "dwn_stem_workspace_bytes": (c_sz, [_P(StemArgs)]),
     "dwn_stem_forward": (c_i, [_P(StemArgs), c_i, c_p]),
     "dwn_stem_backward": (c_i, [_P(StemArgs), c_i, c_p]),
-    "dwn_stem_input_grad": (c_i, [_P(StemInputGradArgs), c_i, c_p]),
-    "dwn_stem_backward_input": (c_i, [_P(StemArgs), c_p, c_i, c_p]),
+    "dwn_stem_input_grad": _new(c_i, [_P(StemInputGradArgs), c_i, c_p]),
+    "dwn_stem_backward_input": _new(c_i, [_P(StemArgs), c_p, c_i, c_p]),
     "dwn_block_workspace_bytes": (c_sz, [_P(BlockArgs), c_i]),
     "dwn_block_forward": (c_i, [_P(BlockArgs), c_i, c_p]),
     "dwn_block_backward": (c_i, [_P(BlockArgs), c_i, c_p]),
@@ -364,10 +378,10 @@ SYMBOLS = {
     "dwn_f64_to_f32": (c_i, [c_p, c_p, c_i, c_i, c_p]),
     "dwn_adamw_ema_multi": (c_i, [c_p, c_i, c_i, c_d, c_d, c_d, c_d, c_d, c_ll, c_d, c_d, c_i, c_p]),
     "dwn_ema_lerp_multi": (c_i, [c_p, c_i, c_i, c_d, c_i, c_p]),
-    "dwn_grad_guard_workspace_bytes": (c_sz, [c_i, c_i]),
-    "dwn_grad_sumsq_multi": (c_i, [c_p, c_i, c_i, c_d, c_p, c_sz, c_p, c_i, c_p]),
-    "dwn_step_guard_finalize": (c_i, [c_p, c_p, c_d, c_i, c_p, c_i, c_p, c_i, c_p]),
-    "dwn_adamw_ema_multi_guarded": (c_i, [c_p, c_i, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_d, c_p, c_i, c_p]),
+    "dwn_grad_guard_workspace_bytes": _new(c_sz, [c_i, c_i]),
+    "dwn_grad_sumsq_multi": _new(c_i, [c_p, c_i, c_i, c_d, c_p, c_sz, c_p, c_i, c_p]),
+    "dwn_step_guard_finalize": _new(c_i, [c_p, c_p, c_d, c_i, c_p, c_i, c_p, c_i, c_p]),
+    "dwn_adamw_ema_multi_guarded": _new(c_i, [c_p, c_i, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_d, c_p, c_i, c_p]),
     "dwn_conv_pw_bn_stats_workspace_bytes": (c_sz, [c_i]),
     "dwn_conv_pw_bn_stats": (c_i, [c_p, c_ll, c_ll, c_p, c_i, c_i, _P(BN), c_f, c_f, c_p, c_p, c_sz, c_i, c_i, c_p]),
     "dwn_pw_bwd_fused_supported": (c_i, [c_i, c_ll, c_i, c_i]),
@@ -379,48 +393,48 @@ SYMBOLS = {
     "dwn_dw_spatial_fwd_rc": (c_i, [_P(DwSpatialRcFwdArgs), c_i, c_p]),
     "dwn_assemble_inputs": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_i, c_p]),
     "dwn_assemble_targets": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_p]),
-    "dwn_gaze_shift_forward": (c_i, [_P(GazeArgs), c_i, c_p]),
-    "dwn_gaze_shift_backward": (c_i, [_P(GazeArgs), c_i, c_p]),
-    "dwn_plane_mean": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p]),
-    "dwn_corr_ws_bytes": (c_sz, [_P(CorrArgs)]),
-    "dwn_corr_moments": (c_i, [_P(CorrArgs), c_i, c_p]),
-    "dwn_corr_loss_finalize": (c_i, [_P(CorrArgs), c_i, c_p]),
-    "dwn_corr_loss_backward": (c_i, [_P(CorrArgs), c_i, c_p]),
-    "dwn_gabor_workspace_bytes": (c_sz, [_P(GaborArgs)]),
-    "dwn_gabor_forward": (c_i, [_P(GaborArgs), c_i, c_p]),
-    "dwn_gabor_backward": (c_i, [_P(GaborArgs), c_i, c_p]),
-    "dwn_modulator_ws_bytes": (c_sz, [_P(ModulatorArgs)]),
-    "dwn_modulator_forward": (c_i, [_P(ModulatorArgs), c_i, c_p]),
-    "dwn_modulator_backward": (c_i, [_P(ModulatorArgs), c_i, c_p]),
-    "dwn_blur3d_ws_bytes": (c_sz, [_P(Blur3dArgs)]),
-    "dwn_clip_moments_ws_bytes": (c_sz, [_P(ClipMomentsArgs)]),
-    "dwn_blur3d": (c_i, [_P(Blur3dArgs), c_i, c_p]),
-    "dwn_clip_moments": (c_i, [_P(ClipMomentsArgs), c_i, c_p]),
-    "dwn_mei_update": (c_i, [_P(MeiUpdateArgs), c_i, c_p]),
-    "dwn_trial_score_ws_bytes": (c_sz, [_P(TrialScoreArgs)]),
-    "dwn_trial_moments": (c_i, [_P(TrialScoreArgs), c_i, c_p]),
-    "dwn_trial_score_finalize": (c_i, [_P(TrialScoreArgs), c_i, c_p]),
-    "dwn_spatial_gain_ws_bytes": (c_sz, [_P(SpatialGainArgs)]),
-    "dwn_spatial_gain_forward": (c_i, [_P(SpatialGainArgs), c_i, c_p]),
-    "dwn_spatial_gain_backward": (c_i, [_P(SpatialGainArgs), c_i, c_p]),
+    "dwn_gaze_shift_forward": _new(c_i, [_P(GazeArgs), c_i, c_p]),
+    "dwn_gaze_shift_backward": _new(c_i, [_P(GazeArgs), c_i, c_p]),
+    "dwn_plane_mean": _new(c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p]),
+    "dwn_corr_ws_bytes": _new(c_sz, [_P(CorrArgs)]),
+    "dwn_corr_moments": _new(c_i, [_P(CorrArgs), c_i, c_p]),
+    "dwn_corr_loss_finalize": _new(c_i, [_P(CorrArgs), c_i, c_p]),
+    "dwn_corr_loss_backward": _new(c_i, [_P(CorrArgs), c_i, c_p]),
+    "dwn_gabor_workspace_bytes": _new(c_sz, [_P(GaborArgs)]),
+    "dwn_gabor_forward": _new(c_i, [_P(GaborArgs), c_i, c_p]),
+    "dwn_gabor_backward": _new(c_i, [_P(GaborArgs), c_i, c_p]),
+    "dwn_modulator_ws_bytes": _new(c_sz, [_P(ModulatorArgs)]),
+    "dwn_modulator_forward": _new(c_i, [_P(ModulatorArgs), c_i, c_p]),
+    "dwn_modulator_backward": _new(c_i, [_P(ModulatorArgs), c_i, c_p]),
+    "dwn_blur3d_ws_bytes": _new(c_sz, [_P(Blur3dArgs)]),
+    "dwn_clip_moments_ws_bytes": _new(c_sz, [_P(ClipMomentsArgs)]),
+    "dwn_blur3d": _new(c_i, [_P(Blur3dArgs), c_i, c_p]),
+    "dwn_clip_moments": _new(c_i, [_P(ClipMomentsArgs), c_i, c_p]),
+    "dwn_mei_update": _new(c_i, [_P(MeiUpdateArgs), c_i, c_p]),
+    "dwn_trial_score_ws_bytes": _new(c_sz, [_P(TrialScoreArgs)]),
+    "dwn_trial_moments": _new(c_i, [_P(TrialScoreArgs), c_i, c_p]),
+    "dwn_trial_score_finalize": _new(c_i, [_P(TrialScoreArgs), c_i, c_p]),
+    "dwn_spatial_gain_ws_bytes": _new(c_sz, [_P(SpatialGainArgs)]),
+    "dwn_spatial_gain_forward": _new(c_i, [_P(SpatialGainArgs), c_i, c_p]),
+    "dwn_spatial_gain_backward": _new(c_i, [_P(SpatialGainArgs), c_i, c_p]),
     # (the population structure of dwn_pairwise.hip)
-    "dwn_pair_ldz": (c_ll, [c_i]),
-    "dwn_pair_state_bytes": (c_sz, [_P(PairArgs)]),
-    "dwn_pair_ws_bytes": (c_sz, [_P(PairArgs)]),
-    "dwn_pair_compare_ws_bytes": (c_sz, [_P(PairCompareArgs)]),
-    "dwn_pair_stage": (c_i, [_P(PairArgs), c_i, c_p]),
-    "dwn_pair_syrk": (c_i, [_P(PairArgs), c_i, c_p]),
-    "dwn_pair_corr_finalize": (c_i, [_P(PairArgs), c_i, c_p]),
-    "dwn_pair_compare": (c_i, [_P(PairCompareArgs), c_i, c_p]),
+    "dwn_pair_ldz": _new(c_ll, [c_i]),
+    "dwn_pair_state_bytes": _new(c_sz, [_P(PairArgs)]),
+    "dwn_pair_ws_bytes": _new(c_sz, [_P(PairArgs)]),
+    "dwn_pair_compare_ws_bytes": _new(c_sz, [_P(PairCompareArgs)]),
+    "dwn_pair_stage": _new(c_i, [_P(PairArgs), c_i, c_p]),
+    "dwn_pair_syrk": _new(c_i, [_P(PairArgs), c_i, c_p]),
+    "dwn_pair_corr_finalize": _new(c_i, [_P(PairArgs), c_i, c_p]),
+    "dwn_pair_compare": _new(c_i, [_P(PairCompareArgs), c_i, c_p]),
     # (the parametric fits of dwn_rf_fit.hip; tests/test_host_rf.py keeps the five receptive-field entries last)
-    "dwn_gauss2d_ws_bytes": (c_sz, [_P(Gauss2dArgs)]),
-    "dwn_gauss2d_fit": (c_i, [_P(Gauss2dArgs), c_i, c_p]),
-    "dwn_gauss2d_profile": (c_i, [_P(Gauss2dProfileArgs), c_i, c_p]),
-    "dwn_noise_forward": (c_i, [_P(NoiseArgs), c_i, c_p]),
-    "dwn_sta_state_bytes": (c_sz, [_P(StaArgs)]),
-    "dwn_sta_ws_bytes": (c_sz, [_P(StaArgs)]),
-    "dwn_sta_accumulate": (c_i, [_P(StaArgs), c_i, c_p]),
-    "dwn_sta_finalize": (c_i, [_P(StaArgs), c_i, c_p]),
+    "dwn_gauss2d_ws_bytes": _new(c_sz, [_P(Gauss2dArgs)]),
+    "dwn_gauss2d_fit": _new(c_i, [_P(Gauss2dArgs), c_i, c_p]),
+    "dwn_gauss2d_profile": _new(c_i, [_P(Gauss2dProfileArgs), c_i, c_p]),
+    "dwn_noise_forward": _new(c_i, [_P(NoiseArgs), c_i, c_p]),
+    "dwn_sta_state_bytes": _new(c_sz, [_P(StaArgs)]),
+    "dwn_sta_ws_bytes": _new(c_sz, [_P(StaArgs)]),
+    "dwn_sta_accumulate": _new(c_i, [_P(StaArgs), c_i, c_p]),
+    "dwn_sta_finalize": _new(c_i, [_P(StaArgs), c_i, c_p]),
 }
 
 
@@ -432,7 +446,7 @@ class DwnError(RuntimeError):
 HASH_SRCS = ("dwn_api.hip", "dwn_gemm.hip", "dwn_gemm_nn_1.hip", "dwn_gemm_nn_2.hip", "dwn_gemm_nn_3.hip", "dwn_gemm_nn_4.hip", "dwn_gemm_nn_5.hip",
              "dwn_gemm_nn_6.hip", "dwn_gemm_tn.hip", "dwn_pw_bwd.hip", "dwn_gemm_xl.hip", "dwn_gemm_kd.hip", "dwn_dwconv.hip", "dwn_dwrc.hip",
              "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_spatial.hip", "dwn_mei.hip", "dwn_rf_fit.hip", "dwn_pairwise.hip", "dwn_trial_score.hip", "dwn_rf.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
-             "dwn_kernels.h", "dwn_launch.h", "dwn_gemm_nn.h", "dwn_gain.h",
+             "dwn_kernels.h", "dwn_launch.h", "dwn_gemm_nn.h", "dwn_gain.h", "dwn_reduce.h",
              "../../include/dwn.h")
 
 
@@ -451,22 +465,10 @@ def _load():
             f"(or `make -C {LIB_PATH.parent}`).  sensorium_amd has no fallback path.")
     lib = C.CDLL(str(LIB_PATH), mode=getattr(os, "RTLD_NOW", 2))
     ab = bool(os.environ.get("DWN_LIB_PATH"))      # an explicitly chosen other build: a same-box A/B run of an older library
-    for name, (restype, argtypes) in SYMBOLS.items():
-        if ab and name in ("dwn_stem_input_grad", "dwn_stem_backward_input", "dwn_grad_guard_workspace_bytes", "dwn_grad_sumsq_multi",
-                           "dwn_step_guard_finalize", "dwn_adamw_ema_multi_guarded", "dwn_dw_temporal_wide_fwd",
-                           "dwn_dw_temporal_wide_bwd", "dwn_gaze_shift_forward", "dwn_gaze_shift_backward",
-                           "dwn_plane_mean", "dwn_corr_ws_bytes", "dwn_corr_moments", "dwn_corr_loss_finalize",
-                           "dwn_corr_loss_backward", "dwn_gabor_workspace_bytes", "dwn_gabor_forward",
-                           "dwn_gabor_backward", "dwn_modulator_ws_bytes", "dwn_modulator_forward",
-                           "dwn_modulator_backward", "dwn_blur3d_ws_bytes", "dwn_clip_moments_ws_bytes", "dwn_blur3d",
-                           "dwn_clip_moments", "dwn_mei_update", "dwn_trial_score_ws_bytes", "dwn_trial_moments",
-                           "dwn_trial_score_finalize", "dwn_spatial_gain_ws_bytes", "dwn_spatial_gain_forward",
-                           "dwn_spatial_gain_backward", "dwn_noise_forward", "dwn_sta_state_bytes", "dwn_sta_ws_bytes",
-                           "dwn_sta_accumulate", "dwn_sta_finalize", "dwn_gauss2d_ws_bytes", "dwn_gauss2d_fit",
-                           "dwn_gauss2d_profile", "dwn_pair_ldz", "dwn_pair_state_bytes", "dwn_pair_ws_bytes",
-                           "dwn_pair_compare_ws_bytes", "dwn_pair_stage", "dwn_pair_syrk", "dwn_pair_corr_finalize",
-                           "dwn_pair_compare") and not hasattr(lib, name):
-            continue                     # (A/B: a library from before the input gradients / the guarded step / the wide temporal entries / the gaze shifter / the correlation objective / the stimuli / the behaviour modulator / the MEI kernels / the trial scores / the retinotopic readout gain / the receptive-field mapping / the parametric fits / the population structure; the plain training step calls none of them)
+    for name, proto in SYMBOLS.items():
+        if ab and isinstance(proto, _new) and not hasattr(lib, name):
+            continue                     # (A/B: a library from before this entry)
+        restype, argtypes = proto
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -478,7 +480,7 @@ def _load():
                           f"`make -C {LIB_PATH.parent}` — binaries are not in git, so what runs must be what is committed")
     for cname, struct in _STRUCTS.items():
         n = lib.dwn_sizeof(cname.encode())
-        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in ("dwn_stem_input_grad_args", "dwn_guarded_entry", "dwn_step_guard", "dwn_gaze_args", "dwn_corr_args", "dwn_gabor_args", "dwn_modulator_args", "dwn_blur3d_args", "dwn_clip_moments_args", "dwn_mei_update_args", "dwn_trial_desc", "dwn_trial_group", "dwn_trial_score_args", "dwn_spatial_gain_args", "dwn_noise_args", "dwn_sta_args", "dwn_gauss2d_args", "dwn_gauss2d_profile_args", "dwn_pair_seg", "dwn_pair_args", "dwn_pair_compare_args"))):      # (A/B: ABI 7 only appended)
+        if n != C.sizeof(struct) and not (ab and (0 < n < C.sizeof(struct) or cname in _NEW_STRUCTS)):      # (A/B: ABI 7 only appended)
             raise ImportError(f"struct layout mismatch for {cname}: C {n} bytes vs ctypes {C.sizeof(struct)}")
     return lib
 

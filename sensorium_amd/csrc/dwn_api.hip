@@ -1184,25 +1184,58 @@ int dwn_assemble_targets(const dwn_clip_desc* descs, int B, int T, float* const*
     return k_assemble_targets(descs, B, T, targets, n_neurons, n_mice, max_neurons, mice_weights, (hipStream_t)stream);
 }
 
-// ---- gaze shifter: the argument checks need no device
+// ---- the analysis entries below share three openings and one video-plane check; no argument check needs a device
+// the prologue: clear the error, reject a null argument struct
+#define ARGS(a, who) do { g_err[0] = 0; if (!(a)) return dwn_set_error(-1, who ": null arguments"); } while (0)
+// the workspace a->ws / a->ws_bytes against `need` bytes (what `getter` answers) and an alignment.  The code is -3 everywhere but
+// in the two *_backward entries of the gains (-2), and the alignment is the entry's own: both are part of the interface.
+#define WS_CHECK(a, code, who, need, getter, align) do { \
+    if ((a)->ws_bytes < (need) || ((size_t)(a)->ws & ((align) - 1))) \
+        return dwn_set_error(code, who ": workspace smaller than " getter " or not " #align "-byte aligned"); } while (0)
+// a *_ws_bytes entry: 0 and no error left behind when the arguments are null or their geometry is bad
+#define WS_BYTES_OR_0(a, geometry, bytes) do { if (!(a) || geometry(a) != 0) { g_err[0] = 0; return 0; } return (bytes); } while (0)
+
+// One plane of a [B][Cin][T][H][W] video, the channels [c, c + nc) and a window in it.  `parts` picks what is checked, always in
+// this order: the plane (sizes, channels, counts), the window, the cell, the per-clip element bounds of the MEI entries.
+enum { PL_PLANE = 1, PL_WINDOW = 2, PL_EMPTY_OK = 4, PL_CELL = 8, PL_CLIP = 16 };      // PL_EMPTY_OK: wh == ww == 0 at 0, 0 is the whole plane
+struct PlaneArgs { int B, Cin, T, H, W, c, nc; const char* chan; int y0, x0, wh, ww, cell; };
+static int plane_check(const char* who, unsigned parts, const PlaneArgs& p) {
+    const char* bad = nullptr;
+    const long long HW = (long long)p.H * p.W;
+    if (parts & PL_PLANE) {
+        if (p.B <= 0 || p.Cin <= 0 || p.T <= 0 || p.H <= 0 || p.W <= 0) bad = "B, Cin, T, H, W must be positive";
+        else if (p.nc <= 0 || p.c < 0 || p.c >= p.Cin || p.nc > p.Cin - p.c) bad = p.chan;
+        else if (HW > (1ll << 30) || (long long)p.B * p.Cin * p.T >= (1ll << 31)) bad = "more than 2^30 pixels per plane or 2^31 planes";
+    }
+    if (!bad && (parts & PL_WINDOW)) {
+        if ((parts & PL_EMPTY_OK) && p.wh == 0 && p.ww == 0) {
+            if (p.y0 != 0 || p.x0 != 0) bad = "window not inside the plane (an empty window must start at 0, 0)";
+        } else if (p.y0 < 0 || p.x0 < 0 || p.wh <= 0 || p.ww <= 0 || p.wh > p.H - p.y0 || p.ww > p.W - p.x0) {
+            bad = "window not inside the plane";
+        }
+    }
+    if (!bad && (parts & PL_CELL) && (p.cell < 1 || p.wh % p.cell || p.ww % p.cell)) bad = "cell must be positive and divide both window sides";
+    // one clip's window elements are indexed by an int, and every grid stays below 2^31 workgroups
+    if (!bad && (parts & PL_CLIP) && (p.T * HW > (1ll << 30) || (long long)p.B * p.T * HW / 64 >= (1ll << 31))) bad = "more than 2^30 elements per clip or 2^37 in all";
+    if (!bad) return 0;
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s", who, bad);
+    return dwn_set_error(-2, msg);
+}
+
+// ---- gaze shifter
 static int gaze_geometry(const dwn_gaze_args* a) {
-    if (a->B <= 0 || a->Cin <= 0 || a->T <= 0 || a->H <= 0 || a->W <= 0) return dwn_set_error(-2, "gaze_shift: B, Cin, T, H, W must be positive");
-    if (a->video_channel < 0 || a->video_channel >= a->Cin) return dwn_set_error(-2, "gaze_shift: video_channel outside [0, Cin)");
-    if ((long long)a->H * a->W > (1ll << 30) || (long long)a->B * a->Cin * a->T >= (1ll << 31))
-        return dwn_set_error(-2, "gaze_shift: more than 2^30 pixels per plane or 2^31 planes");
-    return 0;
+    return plane_check("gaze_shift", PL_PLANE, {a->B, a->Cin, a->T, a->H, a->W, a->video_channel, 1, "video_channel outside [0, Cin)"});
 }
 int dwn_gaze_shift_forward(const dwn_gaze_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "gaze_shift_forward: null arguments");
+    ARGS(a, "gaze_shift_forward");
     TRY(gaze_geometry(a));
     if (!a->x || !a->shift || !a->out) return dwn_set_error(-1, "gaze_shift_forward: null pointer (x, shift, out)");
     ENTER(device);
     return k_gaze_forward(*a, (hipStream_t)stream);
 }
 int dwn_gaze_shift_backward(const dwn_gaze_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "gaze_shift_backward: null arguments");
+    ARGS(a, "gaze_shift_backward");
     TRY(gaze_geometry(a));
     if (!a->dx && !a->dshift) return dwn_set_error(-1, "gaze_shift_backward: dx and dshift are both null");
     if (!a->shift || !a->dout) return dwn_set_error(-1, "gaze_shift_backward: null pointer (shift, dout)");
@@ -1213,10 +1246,7 @@ int dwn_gaze_shift_backward(const dwn_gaze_args* a, int device, void* stream) {
 int dwn_plane_mean(const float* x, int B, int Cin, int T, int H, int W, int c0, int nc, float* mean, int device, void* stream) {
     g_err[0] = 0;
     if (!x || !mean) return dwn_set_error(-1, "plane_mean: null pointer (x, mean)");
-    if (B <= 0 || Cin <= 0 || T <= 0 || H <= 0 || W <= 0) return dwn_set_error(-2, "plane_mean: B, Cin, T, H, W must be positive");
-    if (nc <= 0 || c0 < 0 || c0 >= Cin || nc > Cin - c0) return dwn_set_error(-2, "plane_mean: channels [c0, c0 + nc) outside [0, Cin)");
-    if ((long long)H * W > (1ll << 30) || (long long)B * Cin * T >= (1ll << 31))
-        return dwn_set_error(-2, "plane_mean: more than 2^30 pixels per plane or 2^31 planes");
+    TRY(plane_check("plane_mean", PL_PLANE, {B, Cin, T, H, W, c0, nc, "channels [c0, c0 + nc) outside [0, Cin)"}));
     ENTER(device);
     return k_plane_mean(x, B, Cin, T, H, W, c0, nc, mean, (hipStream_t)stream);
 }
@@ -1232,43 +1262,34 @@ static int corr_geometry(const dwn_corr_args* a) {
 }
 size_t dwn_corr_ws_bytes(const dwn_corr_args* a) { return a && a->N > 0 ? k_corr_ws_bytes(a->N) : 0; }
 int dwn_corr_moments(const dwn_corr_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "corr_moments: null arguments");
+    ARGS(a, "corr_moments");
     TRY(corr_geometry(a));
     if (!a->pred || !a->target || !a->w || !a->stat || !a->count) return dwn_set_error(-1, "corr_moments: null pointer (pred, target, w, stat, count)");
     ENTER(device);
     return k_corr_moments(*a, (hipStream_t)stream);
 }
 int dwn_corr_loss_finalize(const dwn_corr_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "corr_loss_finalize: null arguments");
+    ARGS(a, "corr_loss_finalize");
     TRY(corr_geometry(a));
     if (!a->stat || !a->count || !a->share || !a->loss_acc || !a->ws) return dwn_set_error(-1, "corr_loss_finalize: null pointer (stat, count, share, loss_acc, ws)");
-    if (a->ws_bytes < k_corr_ws_bytes(a->N) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "corr_loss_finalize: workspace smaller than dwn_corr_ws_bytes or not 8-byte aligned");
+    WS_CHECK(a, -3, "corr_loss_finalize", k_corr_ws_bytes(a->N), "dwn_corr_ws_bytes", 8);
     ENTER(device);
     return k_corr_finalize(*a, (hipStream_t)stream);
 }
 int dwn_corr_loss_backward(const dwn_corr_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "corr_loss_backward: null arguments");
+    ARGS(a, "corr_loss_backward");
     TRY(corr_geometry(a));
     if (!a->pred || !a->target || !a->w || !a->stat || !a->share || !a->dpred) return dwn_set_error(-1, "corr_loss_backward: null pointer (pred, target, w, stat, share, dpred)");
     ENTER(device);
     return k_corr_backward(*a, (hipStream_t)stream);
 }
 
-// ---- in-silico stimuli: the argument checks need no device
+// ---- in-silico stimuli
 static int gabor_geometry(const dwn_gabor_args* a) {
-    if (a->B <= 0 || a->Cin <= 0 || a->T <= 0 || a->H <= 0 || a->W <= 0) return dwn_set_error(-2, "gabor: B, Cin, T, H, W must be positive");
-    if (a->video_channel < 0 || a->video_channel >= a->Cin) return dwn_set_error(-2, "gabor: video_channel outside [0, Cin)");
-    if ((long long)a->H * a->W > (1ll << 30) || (long long)a->B * a->Cin * a->T >= (1ll << 31))
-        return dwn_set_error(-2, "gabor: more than 2^30 pixels per plane or 2^31 planes");
+    const PlaneArgs p = {a->B, a->Cin, a->T, a->H, a->W, a->video_channel, 1, "video_channel outside [0, Cin)", a->y0, a->x0, a->wh, a->ww};
+    TRY(plane_check("gabor", PL_PLANE, p));
     if (a->envelope != DWN_GABOR_GAUSSIAN && a->envelope != DWN_GABOR_NONE) return dwn_set_error(-2, "gabor: envelope must be DWN_GABOR_GAUSSIAN or DWN_GABOR_NONE");
-    if (a->wh == 0 && a->ww == 0) {
-        if (a->y0 != 0 || a->x0 != 0) return dwn_set_error(-2, "gabor: window not inside the plane (an empty window must start at 0, 0)");
-    } else if (a->y0 < 0 || a->x0 < 0 || a->wh <= 0 || a->ww <= 0 || a->wh > a->H - a->y0 || a->ww > a->W - a->x0) {
-        return dwn_set_error(-2, "gabor: window not inside the plane");
-    }
+    TRY(plane_check("gabor", PL_WINDOW | PL_EMPTY_OK, p));      // (the envelope answers before the window)
     if (a->clamp != 0 && a->clamp != 1) return dwn_set_error(-2, "gabor: clamp must be 0 or 1");
     if (a->clamp && !(a->lo <= a->hi)) return dwn_set_error(-2, "gabor: video range needs lo <= hi");
     const long long wpix = a->wh ? (long long)a->wh * a->ww : (long long)a->H * a->W;
@@ -1276,23 +1297,20 @@ static int gabor_geometry(const dwn_gabor_args* a) {
     return 0;
 }
 size_t dwn_gabor_workspace_bytes(const dwn_gabor_args* a) {
-    if (!a || gabor_geometry(a) != 0) { g_err[0] = 0; return 0; }
-    return k_gabor_ws_bytes(*a);
+    WS_BYTES_OR_0(a, gabor_geometry, k_gabor_ws_bytes(*a));
 }
 int dwn_gabor_forward(const dwn_gabor_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "gabor_forward: null arguments");
+    ARGS(a, "gabor_forward");
     TRY(gabor_geometry(a));
     if (!a->x || !a->params || !a->out) return dwn_set_error(-1, "gabor_forward: null pointer (x, params, out)");
     ENTER(device);
     return k_gabor_forward(*a, (hipStream_t)stream);
 }
 int dwn_gabor_backward(const dwn_gabor_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "gabor_backward: null arguments");
+    ARGS(a, "gabor_backward");
     TRY(gabor_geometry(a));
     if (!a->params || !a->dout || !a->dparams || !a->ws) return dwn_set_error(-1, "gabor_backward: null pointer (params, dout, dparams, ws)");
-    if (a->ws_bytes < k_gabor_ws_bytes(*a) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "gabor_backward: workspace smaller than dwn_gabor_workspace_bytes or not 8-byte aligned");
+    WS_CHECK(a, -3, "gabor_backward", k_gabor_ws_bytes(*a), "dwn_gabor_workspace_bytes", 8);
     ENTER(device);
     return k_gabor_backward(*a, (hipStream_t)stream);
 }
@@ -1309,12 +1327,10 @@ static int modulator_geometry(const dwn_modulator_args* a) {
     return 0;
 }
 size_t dwn_modulator_ws_bytes(const dwn_modulator_args* a) {
-    if (!a || modulator_geometry(a) != 0) { g_err[0] = 0; return 0; }
-    return k_modulator_ws_bytes(*a);
+    WS_BYTES_OR_0(a, modulator_geometry, k_modulator_ws_bytes(*a));
 }
 int dwn_modulator_forward(const dwn_modulator_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "modulator_forward: null arguments");
+    ARGS(a, "modulator_forward");
     TRY(modulator_geometry(a));
     if (!a->y || !a->h || !a->u || !a->c || !a->out) return dwn_set_error(-1, "modulator_forward: null pointer (y, h, u, c, out)");
     if (a->out == a->y) return dwn_set_error(-2, "modulator_forward: out must not alias y");
@@ -1322,33 +1338,19 @@ int dwn_modulator_forward(const dwn_modulator_args* a, int device, void* stream)
     return k_modulator_forward(*a, (hipStream_t)stream);
 }
 int dwn_modulator_backward(const dwn_modulator_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "modulator_backward: null arguments");
+    ARGS(a, "modulator_backward");
     TRY(modulator_geometry(a));
     if (!a->y || !a->h || !a->u || !a->c || !a->dout) return dwn_set_error(-1, "modulator_backward: null pointer (y, h, u, c, dout)");
     if (!a->dy && !a->dh && !a->du && !a->dc) return dwn_set_error(-1, "modulator_backward: dy, dh, du and dc are all null");
     if (!a->ws) return dwn_set_error(-1, "modulator_backward: null pointer (ws)");
-    if (a->ws_bytes < k_modulator_ws_bytes(*a) || ((size_t)a->ws & 7)) return dwn_set_error(-2, "modulator_backward: workspace smaller than dwn_modulator_ws_bytes or not 8-byte aligned");
+    WS_CHECK(a, -2, "modulator_backward", k_modulator_ws_bytes(*a), "dwn_modulator_ws_bytes", 8);
     ENTER(device);
     return k_modulator_backward(*a, (hipStream_t)stream);
 }
 
-// ---- regularised MEI synthesis: the argument checks need no device
+// ---- regularised MEI synthesis
 static int mei_plane(const char* who, int B, int Cin, int T, int H, int W, int c, int y0, int x0, int wh, int ww) {
-    static thread_local char msg[160];
-#define MEI_BAD(text) do { snprintf(msg, sizeof msg, "%s: %s", who, text); return dwn_set_error(-2, msg); } while (0)
-    if (B <= 0 || Cin <= 0 || T <= 0 || H <= 0 || W <= 0) MEI_BAD("B, Cin, T, H, W must be positive");
-    if (c < 0 || c >= Cin) MEI_BAD("channel outside [0, Cin)");
-    if ((long long)H * W > (1ll << 30) || (long long)B * Cin * T >= (1ll << 31)) MEI_BAD("more than 2^30 pixels per plane or 2^31 planes");
-    if (wh == 0 && ww == 0) {
-        if (y0 != 0 || x0 != 0) MEI_BAD("window not inside the plane (an empty window must start at 0, 0)");
-    } else if (y0 < 0 || x0 < 0 || wh <= 0 || ww <= 0 || wh > H - y0 || ww > W - x0) {
-        MEI_BAD("window not inside the plane");
-    }
-    // one clip's window elements are indexed by an int, and every grid stays below 2^31 workgroups
-    if ((long long)T * H * W > (1ll << 30) || (long long)B * T * H * W / 64 >= (1ll << 31)) MEI_BAD("more than 2^30 elements per clip or 2^37 in all");
-#undef MEI_BAD
-    return 0;
+    return plane_check(who, PL_PLANE | PL_WINDOW | PL_EMPTY_OK | PL_CLIP, {B, Cin, T, H, W, c, 1, "channel outside [0, Cin)", y0, x0, wh, ww});
 }
 static int blur3d_geometry(const dwn_blur3d_args* a) {
     TRY(mei_plane("blur3d", a->B, a->Cin_src, a->T, a->H, a->W, a->c_src, a->y0, a->x0, a->wh, a->ww));
@@ -1361,34 +1363,29 @@ static int moments_geometry(const dwn_clip_moments_args* a) {
     return mei_plane("clip_moments", a->B, a->Cin, a->T, a->H, a->W, a->c, a->y0, a->x0, a->wh, a->ww);
 }
 size_t dwn_blur3d_ws_bytes(const dwn_blur3d_args* a) {
-    if (!a || blur3d_geometry(a) != 0) { g_err[0] = 0; return 0; }
-    return k_blur3d_ws_bytes(*a);
+    WS_BYTES_OR_0(a, blur3d_geometry, k_blur3d_ws_bytes(*a));
 }
 size_t dwn_clip_moments_ws_bytes(const dwn_clip_moments_args* a) {
-    if (!a || moments_geometry(a) != 0) { g_err[0] = 0; return 0; }
-    return k_clip_moments_ws_bytes(*a);
+    WS_BYTES_OR_0(a, moments_geometry, k_clip_moments_ws_bytes(*a));
 }
 int dwn_blur3d(const dwn_blur3d_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "blur3d: null arguments");
+    ARGS(a, "blur3d");
     TRY(blur3d_geometry(a));
     if (!a->src || !a->dst || !a->taps || !a->ws) return dwn_set_error(-1, "blur3d: null pointer (src, dst, taps, ws)");
-    if (a->ws_bytes < k_blur3d_ws_bytes(*a) || ((size_t)a->ws & 3)) return dwn_set_error(-3, "blur3d: workspace smaller than dwn_blur3d_ws_bytes or not 4-byte aligned");
+    WS_CHECK(a, -3, "blur3d", k_blur3d_ws_bytes(*a), "dwn_blur3d_ws_bytes", 4);
     ENTER(device);
     return k_blur3d(*a, (hipStream_t)stream);
 }
 int dwn_clip_moments(const dwn_clip_moments_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "clip_moments: null arguments");
+    ARGS(a, "clip_moments");
     TRY(moments_geometry(a));
     if (!a->x || !a->stat || !a->ws) return dwn_set_error(-1, "clip_moments: null pointer (x, stat, ws)");
-    if (a->ws_bytes < k_clip_moments_ws_bytes(*a) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "clip_moments: workspace smaller than dwn_clip_moments_ws_bytes or not 8-byte aligned");
+    WS_CHECK(a, -3, "clip_moments", k_clip_moments_ws_bytes(*a), "dwn_clip_moments_ws_bytes", 8);
     ENTER(device);
     return k_clip_moments(*a, (hipStream_t)stream);
 }
 int dwn_mei_update(const dwn_mei_update_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "mei_update: null arguments");
+    ARGS(a, "mei_update");
     if (a->mode != DWN_MEI_STEP && a->mode != DWN_MEI_PROJECT) return dwn_set_error(-2, "mei_update: mode must be DWN_MEI_STEP or DWN_MEI_PROJECT");
     TRY(mei_plane("mei_update", a->B, a->Cin, a->T, a->H, a->W, a->c, a->y0, a->x0, a->wh, a->ww));
     if (a->mode == DWN_MEI_STEP) {
@@ -1419,8 +1416,7 @@ static int trial_counts(const dwn_trial_score_args* a) {
 }
 size_t dwn_trial_score_ws_bytes(const dwn_trial_score_args* a) { return a && a->N > 0 ? k_trial_score_ws_bytes(a->N) : 0; }
 int dwn_trial_moments(const dwn_trial_score_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "trial_moments: null arguments");
+    ARGS(a, "trial_moments");
     TRY(trial_counts(a));
     if (a->n_trials <= 0 || a->n_groups <= 0 || a->n_groups > a->n_trials) return dwn_set_error(-2, "trial_moments: needs 1 <= n_groups <= n_trials");
     if (a->max_repeats < 1 || a->max_repeats > a->n_trials) return dwn_set_error(-2, "trial_moments: max_repeats must lie in [1, n_trials]");
@@ -1432,14 +1428,13 @@ int dwn_trial_moments(const dwn_trial_score_args* a, int device, void* stream) {
     return k_trial_moments(*a, (hipStream_t)stream);
 }
 int dwn_trial_score_finalize(const dwn_trial_score_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "trial_score_finalize: null arguments");
+    ARGS(a, "trial_score_finalize");
     TRY(trial_counts(a));
     if (!(a->eps > 0.0)) return dwn_set_error(-2, "trial_score_finalize: eps must be positive");
     if (a->fev_threshold != a->fev_threshold) return dwn_set_error(-2, "trial_score_finalize: fev_threshold is NaN");
     if (!a->state || !a->scores || !a->summary || !a->ws) return dwn_set_error(-1, "trial_score_finalize: null pointer (state, scores, summary, ws)");
     if (((size_t)a->state & 7) || ((size_t)a->scores & 7) || ((size_t)a->summary & 7)) return dwn_set_error(-2, "trial_score_finalize: state, scores and summary must be 8-byte aligned");
-    if (a->ws_bytes < k_trial_score_ws_bytes(a->N) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "trial_score_finalize: workspace smaller than dwn_trial_score_ws_bytes or not 8-byte aligned");
+    WS_CHECK(a, -3, "trial_score_finalize", k_trial_score_ws_bytes(a->N), "dwn_trial_score_ws_bytes", 8);
     ENTER(device);
     return k_trial_score_finalize(*a, (hipStream_t)stream);
 }
@@ -1467,8 +1462,7 @@ size_t dwn_pair_compare_ws_bytes(const dwn_pair_compare_args* a) {
     return k_pair_compare_ws_bytes(a->M);
 }
 int dwn_pair_stage(const dwn_pair_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "pair_stage: null arguments");
+    ARGS(a, "pair_stage");
     TRY(pair_state(a, "pair_stage"));
     if (a->kind != DWN_PAIR_TOTAL && a->kind != DWN_PAIR_SIGNAL && a->kind != DWN_PAIR_NOISE) return dwn_set_error(-2, "pair_stage: unknown kind");
     if (a->n_segs <= 0 || a->n_groups <= 0 || a->n_groups > a->n_segs) return dwn_set_error(-2, "pair_stage: needs 1 <= n_groups <= n_segs");
@@ -1478,24 +1472,22 @@ int dwn_pair_stage(const dwn_pair_args* a, int device, void* stream) {
     if (!pair_cols_ok(a)) return dwn_set_error(-2, "pair_stage: cols must be a positive multiple of DWN_PAIR_KSTEP");
     if (!a->segs || !a->groups || !a->state || !a->ws) return dwn_set_error(-1, "pair_stage: null pointer (segs, groups, state, ws)");
     if ((size_t)a->state & 7) return dwn_set_error(-2, "pair_stage: state must be 8-byte aligned");
-    if (a->ws_bytes < dwn_pair_ws_bytes(a) || ((size_t)a->ws & 15)) return dwn_set_error(-3, "pair_stage: workspace smaller than dwn_pair_ws_bytes or not 16-byte aligned");
+    WS_CHECK(a, -3, "pair_stage", dwn_pair_ws_bytes(a), "dwn_pair_ws_bytes", 16);
     ENTER(device);
     return k_pair_stage(*a, (hipStream_t)stream);
 }
 int dwn_pair_syrk(const dwn_pair_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "pair_syrk: null arguments");
+    ARGS(a, "pair_syrk");
     TRY(pair_state(a, "pair_syrk"));
     if (!pair_cols_ok(a)) return dwn_set_error(-2, "pair_syrk: cols must be a positive multiple of DWN_PAIR_KSTEP");
     if (!a->state || !a->ws) return dwn_set_error(-1, "pair_syrk: null pointer (state, ws)");
     if ((size_t)a->state & 7) return dwn_set_error(-2, "pair_syrk: state must be 8-byte aligned");
-    if (a->ws_bytes < dwn_pair_ws_bytes(a) || ((size_t)a->ws & 15)) return dwn_set_error(-3, "pair_syrk: workspace smaller than dwn_pair_ws_bytes or not 16-byte aligned");
+    WS_CHECK(a, -3, "pair_syrk", dwn_pair_ws_bytes(a), "dwn_pair_ws_bytes", 16);
     ENTER(device);
     return k_pair_syrk(*a, (hipStream_t)stream);
 }
 int dwn_pair_corr_finalize(const dwn_pair_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "pair_corr_finalize: null arguments");
+    ARGS(a, "pair_corr_finalize");
     TRY(pair_state(a, "pair_corr_finalize"));
     if (!(a->eps > 0.0)) return dwn_set_error(-2, "pair_corr_finalize: eps must be positive");
     if (!a->state || !a->out) return dwn_set_error(-1, "pair_corr_finalize: null pointer (state, out)");
@@ -1504,8 +1496,7 @@ int dwn_pair_corr_finalize(const dwn_pair_args* a, int device, void* stream) {
     return k_pair_corr_finalize(*a, (hipStream_t)stream);
 }
 int dwn_pair_compare(const dwn_pair_compare_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "pair_compare: null arguments");
+    ARGS(a, "pair_compare");
     if (a->N <= 0 || a->N > 65535) return dwn_set_error(-2, "pair_compare: N outside [1, 65535]");
     if (a->M < 1 || a->M > (1 << 20)) return dwn_set_error(-2, "pair_compare: M outside [1, 2^20]");
     if (!a->sel && a->M > a->N) return dwn_set_error(-2, "pair_compare: without sel M must not exceed N");
@@ -1514,7 +1505,7 @@ int dwn_pair_compare(const dwn_pair_compare_args* a, int device, void* stream) {
     if (!a->A || !a->B || !a->per_neuron || !a->summary || !a->ws) return dwn_set_error(-1, "pair_compare: null pointer (A, B, per_neuron, summary, ws)");
     if (((size_t)a->A & 7) || ((size_t)a->B & 7) || ((size_t)a->per_neuron & 7) || ((size_t)a->summary & 7) || ((size_t)a->sel & 3))
         return dwn_set_error(-2, "pair_compare: A, B, per_neuron, summary or sel misaligned");
-    if (a->ws_bytes < k_pair_compare_ws_bytes(a->M) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "pair_compare: workspace smaller than dwn_pair_compare_ws_bytes or not 8-byte aligned");
+    WS_CHECK(a, -3, "pair_compare", k_pair_compare_ws_bytes(a->M), "dwn_pair_compare_ws_bytes", 8);
     ENTER(device);
     return k_pair_compare(*a, (hipStream_t)stream);
 }
@@ -1534,12 +1525,10 @@ static int spatial_gain_geometry(const dwn_spatial_gain_args* a) {
     return 0;
 }
 size_t dwn_spatial_gain_ws_bytes(const dwn_spatial_gain_args* a) {
-    if (!a || spatial_gain_geometry(a) != 0) { g_err[0] = 0; return 0; }
-    return k_spatial_gain_ws_bytes(*a);
+    WS_BYTES_OR_0(a, spatial_gain_geometry, k_spatial_gain_ws_bytes(*a));
 }
 int dwn_spatial_gain_forward(const dwn_spatial_gain_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "spatial_gain_forward: null arguments");
+    ARGS(a, "spatial_gain_forward");
     TRY(spatial_gain_geometry(a));
     if (!a->y || !a->g || !a->pos || !a->weight || !a->bias || !a->out) return dwn_set_error(-1, "spatial_gain_forward: null pointer (y, g, pos, weight, bias, out)");
     if (a->out == a->y) return dwn_set_error(-2, "spatial_gain_forward: out must not alias y");
@@ -1547,32 +1536,22 @@ int dwn_spatial_gain_forward(const dwn_spatial_gain_args* a, int device, void* s
     return k_spatial_gain_forward(*a, (hipStream_t)stream);
 }
 int dwn_spatial_gain_backward(const dwn_spatial_gain_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "spatial_gain_backward: null arguments");
+    ARGS(a, "spatial_gain_backward");
     TRY(spatial_gain_geometry(a));
     if (!a->y || !a->g || !a->pos || !a->weight || !a->bias || !a->dout) return dwn_set_error(-1, "spatial_gain_backward: null pointer (y, g, pos, weight, bias, dout)");
     if (!a->dy && !a->dg && !a->dpos && !a->dweight && !a->dbias) return dwn_set_error(-1, "spatial_gain_backward: dy, dg, dpos, dweight and dbias are all null");
     if (!a->ws) return dwn_set_error(-1, "spatial_gain_backward: null pointer (ws)");
-    if (a->ws_bytes < k_spatial_gain_ws_bytes(*a) || ((size_t)a->ws & 15)) return dwn_set_error(-2, "spatial_gain_backward: workspace smaller than dwn_spatial_gain_ws_bytes or not 16-byte aligned");
+    WS_CHECK(a, -2, "spatial_gain_backward", k_spatial_gain_ws_bytes(*a), "dwn_spatial_gain_ws_bytes", 16);
     ENTER(device);
     return k_spatial_gain_backward(*a, (hipStream_t)stream);
 }
 
-// ---- receptive-field mapping: the argument checks need no device
+// ---- receptive-field mapping
 static int rf_plane(const char* who, int B, int Cin, int T, int H, int W, int c, int y0, int x0, int wh, int ww, int cell) {
-    static thread_local char msg[160];
-#define RF_BAD(text) do { snprintf(msg, sizeof msg, "%s: %s", who, text); return dwn_set_error(-2, msg); } while (0)
-    if (B <= 0 || Cin <= 0 || T <= 0 || H <= 0 || W <= 0) RF_BAD("B, Cin, T, H, W must be positive");
-    if (c < 0 || c >= Cin) RF_BAD("channel outside [0, Cin)");
-    if ((long long)H * W > (1ll << 30) || (long long)B * Cin * T >= (1ll << 31)) RF_BAD("more than 2^30 pixels per plane or 2^31 planes");
-    if (y0 < 0 || x0 < 0 || wh <= 0 || ww <= 0 || wh > H - y0 || ww > W - x0) RF_BAD("window not inside the plane");
-    if (cell < 1 || wh % cell || ww % cell) RF_BAD("cell must be positive and divide both window sides");
-#undef RF_BAD
-    return 0;
+    return plane_check(who, PL_PLANE | PL_WINDOW | PL_CELL, {B, Cin, T, H, W, c, 1, "channel outside [0, Cin)", y0, x0, wh, ww, cell});
 }
 int dwn_noise_forward(const dwn_noise_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "noise_forward: null arguments");
+    ARGS(a, "noise_forward");
     TRY(rf_plane("noise", a->B, a->Cin, a->T, a->H, a->W, a->video_channel, a->y0, a->x0, a->wh, a->ww, a->cell));
     if (a->kind != DWN_NOISE_BINARY && a->kind != DWN_NOISE_SPARSE) return dwn_set_error(-2, "noise: kind must be DWN_NOISE_BINARY or DWN_NOISE_SPARSE");
     if (a->hold < 1) return dwn_set_error(-2, "noise: hold must be positive");
@@ -1602,16 +1581,13 @@ static int sta_accumulate_geometry(const dwn_sta_args* a) {
     return 0;
 }
 size_t dwn_sta_state_bytes(const dwn_sta_args* a) {
-    if (!a || sta_grid(a) != 0) { g_err[0] = 0; return 0; }
-    return k_sta_state_bytes(*a);
+    WS_BYTES_OR_0(a, sta_grid, k_sta_state_bytes(*a));
 }
 size_t dwn_sta_ws_bytes(const dwn_sta_args* a) {
-    if (!a || sta_grid(a) != 0) { g_err[0] = 0; return 0; }
-    return k_sta_ws_bytes(*a);
+    WS_BYTES_OR_0(a, sta_grid, k_sta_ws_bytes(*a));
 }
 int dwn_sta_accumulate(const dwn_sta_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "sta_accumulate: null arguments");
+    ARGS(a, "sta_accumulate");
     TRY(sta_accumulate_geometry(a));
     if (!a->x || !a->r || !a->state) return dwn_set_error(-1, "sta_accumulate: null pointer (x, r, state)");
     if ((size_t)a->state & 7) return dwn_set_error(-2, "sta_accumulate: state must be 8-byte aligned");
@@ -1619,14 +1595,13 @@ int dwn_sta_accumulate(const dwn_sta_args* a, int device, void* stream) {
     return k_sta_accumulate(*a, (hipStream_t)stream);
 }
 int dwn_sta_finalize(const dwn_sta_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "sta_finalize: null arguments");
+    ARGS(a, "sta_finalize");
     TRY(sta_grid(a));
     if (a->samples < 1 || a->samples >= (1ll << 52)) return dwn_set_error(-2, "sta_finalize: samples outside [1, 2^52)");
     if (!(a->rel_threshold >= 0.0 && a->rel_threshold <= 1.0)) return dwn_set_error(-2, "sta_finalize: rel_threshold outside [0, 1]");
     if (!a->state || !a->cov || !a->summary || !a->ws) return dwn_set_error(-1, "sta_finalize: null pointer (state, cov, summary, ws)");
     if (((size_t)a->state & 7) || ((size_t)a->summary & 7)) return dwn_set_error(-2, "sta_finalize: state and summary must be 8-byte aligned");
-    if (a->ws_bytes < k_sta_ws_bytes(*a) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "sta_finalize: workspace smaller than dwn_sta_ws_bytes or not 8-byte aligned");
+    WS_CHECK(a, -3, "sta_finalize", k_sta_ws_bytes(*a), "dwn_sta_ws_bytes", 8);
     ENTER(device);
     return k_sta_finalize(*a, (hipStream_t)stream);
 }
@@ -1644,12 +1619,10 @@ static int gauss2d_geometry(const dwn_gauss2d_args* a) {
     return 0;
 }
 size_t dwn_gauss2d_ws_bytes(const dwn_gauss2d_args* a) {
-    if (!a || gauss2d_geometry(a) != 0) { g_err[0] = 0; return 0; }
-    return k_gauss2d_ws_bytes(*a);
+    WS_BYTES_OR_0(a, gauss2d_geometry, k_gauss2d_ws_bytes(*a));
 }
 int dwn_gauss2d_fit(const dwn_gauss2d_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "gauss2d_fit: null arguments");
+    ARGS(a, "gauss2d_fit");
     TRY(gauss2d_geometry(a));
     if (!a->sel && a->M > a->R) return dwn_set_error(-2, "gauss2d_fit: M > R without a row table");
     if (a->max_iter < 0) return dwn_set_error(-2, "gauss2d_fit: max_iter must not be negative");
@@ -1657,13 +1630,12 @@ int dwn_gauss2d_fit(const dwn_gauss2d_args* a, int device, void* stream) {
     if (!(a->xtol >= 0.0) || !(a->ftol >= 0.0)) return dwn_set_error(-2, "gauss2d_fit: xtol and ftol must not be negative");
     if (!a->maps || !a->params || !a->table || !a->ws) return dwn_set_error(-1, "gauss2d_fit: null pointer (maps, params, table, ws)");
     if (((size_t)a->params & 7) || ((size_t)a->table & 7)) return dwn_set_error(-2, "gauss2d_fit: params and table must be 8-byte aligned");
-    if (a->ws_bytes < k_gauss2d_ws_bytes(*a) || ((size_t)a->ws & 7)) return dwn_set_error(-3, "gauss2d_fit: workspace smaller than dwn_gauss2d_ws_bytes or not 8-byte aligned");
+    WS_CHECK(a, -3, "gauss2d_fit", k_gauss2d_ws_bytes(*a), "dwn_gauss2d_ws_bytes", 8);
     ENTER(device);
     return k_gauss2d_fit(*a, (hipStream_t)stream);
 }
 int dwn_gauss2d_profile(const dwn_gauss2d_profile_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a) return dwn_set_error(-1, "gauss2d_profile: null arguments");
+    ARGS(a, "gauss2d_profile");
     TRY(gauss2d_grid(a->gh, a->gw));
     if (a->N < 1 || a->L < 1 || a->L > 65535) return dwn_set_error(-2, "gauss2d_profile: N must be positive and L in [1, 65535]");
     if ((long long)a->N * a->L > (1ll << 40) / 4096) return dwn_set_error(-2, "gauss2d_profile: more than 2^28 maps");

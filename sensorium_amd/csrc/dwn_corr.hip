@@ -13,6 +13,7 @@
 // Nothing here depends on the occupancy the runtime reports: every grid is a function of the shapes alone.
 #include "dwn_internal.h"
 #include "dwn_kernels.h"
+#include "dwn_reduce.h"
 
 namespace {
 
@@ -144,17 +145,6 @@ __global__ __launch_bounds__(CR_NT) void corr_moments_kernel(const float* __rest
     if (blockIdx.x == 0 && tid == 0) *count = n;
 }
 
-// fixed-order sum over the workgroup; the result is valid in thread 0
-__device__ __forceinline__ double wg_sum(double a, double* red) {
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int s = CR_NT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 __global__ __launch_bounds__(CR_NT) void corr_finalize_kernel(double* __restrict__ stat, const double* __restrict__ count, int N,
                                                               double eps, double* __restrict__ partial) {
     __shared__ double red[CR_NT];
@@ -175,7 +165,7 @@ __global__ __launch_bounds__(CR_NT) void corr_finalize_kernel(double* __restrict
         stat[6 * (i64)N + j] = c1;
         stat[7 * (i64)N + j] = c2;
     }
-    const double tot = wg_sum(term, red);
+    const double tot = wg_tree_sum(term, red);         // dwn_reduce.h: the fixed tree
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
@@ -185,7 +175,7 @@ __global__ __launch_bounds__(CR_NT) void corr_fold_kernel(const double* __restri
     __shared__ double red[CR_NT];
     double a = 0.0;
     for (int i = threadIdx.x; i < nparts; i += CR_NT) a += partial[i];
-    const double tot = wg_sum(a, red);
+    const double tot = wg_tree_sum(a, red);
     if (threadIdx.x == 0) *loss_acc += (double)*share * (rho * tot);
 }
 
@@ -219,8 +209,6 @@ __global__ __launch_bounds__(CR_NT) void corr_bwd_kernel(const float* __restrict
         else dpred[at] = o[0];
     }
 }
-
-inline bool aligned16(const void* p) { return ((size_t)p & 15) == 0; }
 
 }  // namespace
 

@@ -2,9 +2,6 @@
 // retinotopic readout gain (dwn_spatial.hip).  Device code only.
 #pragma once
 #include "dwn_common.h"
-#include <float.h>
-
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= FLT_MAX; }
 
 // tanh(a) = sign(a) (1 - e) / (1 + e), e = exp(-2 |a|).  Only its ABSOLUTE error counts (it enters log(gain) scaled by m), so the
 // hardware exponential is enough here: the relative error of exp(x) through v_exp_f32 is about 2 eps (1 + |x|), eps = 2^-24, and

@@ -11,6 +11,7 @@
 // here uses an atomic: results are bit-reproducible in the product and the -DDWN_DETERMINISTIC builds alike.
 #include "dwn_internal.h"
 #include "dwn_kernels.h"
+#include "dwn_reduce.h"
 #include "dwn_launch.h"
 #include <float.h>
 
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(GZ_NT) void gaze_stream_kernel(const float* __restr
             continue;
         }
         const GazeFrame g = gaze_frame(shift + ((i64)b * T + t) * 2, H, W);
-        const float bad = ADJ ? 0.f : __builtin_nanf("");
+        const float bad = ADJ ? 0.f : qnan_f();
         for (int i = threadIdx.x; i < HW; i += GZ_NT) {
             const int y = (int)divW.div((unsigned)i), x = i - y * W;
             float v00, v01, v10, v11;
@@ -117,21 +118,6 @@ __global__ __launch_bounds__(GZ_NT) void gaze_stream_kernel(const float* __restr
     }
 }
 
-// fixed-order sum over the workgroup of two doubles per thread; the result is valid in thread 0
-__device__ __forceinline__ void wg_sum2(double& a, double& b, double (*red)[GZ_NT]) {
-    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int s = GZ_NT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + s];
-            red[1][threadIdx.x] += red[1][threadIdx.x + s];
-        }
-        __syncthreads();
-    }
-    a = red[0][0]; b = red[1][0];
-    __syncthreads();
-}
-
 // dshift[b][t] = sum_{y,x} dout * d out / d (dy, dx), iy / ix held constant; one workgroup per frame
 __global__ __launch_bounds__(GZ_NT) void gaze_dshift_kernel(const float* __restrict__ x, const float* __restrict__ shift,
                                                             const float* __restrict__ dout, float* __restrict__ dshift,
@@ -147,7 +133,7 @@ __global__ __launch_bounds__(GZ_NT) void gaze_dshift_kernel(const float* __restr
         const float* d = dout + off;
         const GazeFrame g = gaze_frame(shift + f * 2, H, W);
         const float ay = 1.f - g.fy, ax = 1.f - g.fx;
-        double sy = 0.0, sx = 0.0;
+        double sum[2] = {0.0, 0.0};                   // sy, sx
         for (int i = threadIdx.x; i < HW; i += GZ_NT) {
             const int y = (int)divW.div((unsigned)i), xx = i - y * W;
             const int r = y + g.iy, q = xx + g.ix;
@@ -158,14 +144,14 @@ __global__ __launch_bounds__(GZ_NT) void gaze_dshift_kernel(const float* __restr
             const float gy = (ax != 0.f ? ax * (v10 - v00) : 0.f) + (g.fx != 0.f ? g.fx * (v11 - v01) : 0.f);
             const float gx = (ay != 0.f ? ay * (v01 - v00) : 0.f) + (g.fy != 0.f ? g.fy * (v11 - v10) : 0.f);
             const double dd = (double)d[i];
-            sy += dd * (double)gy;
-            sx += dd * (double)gx;
+            sum[0] += dd * (double)gy;
+            sum[1] += dd * (double)gx;
         }
-        wg_sum2(sy, sx, red);
+        wg_tree_sum(sum, red);                         // dwn_reduce.h: the fixed tree, two values per thread
         if (threadIdx.x == 0) {
-            const float bad = __builtin_nanf("");
-            dshift[f * 2] = g.finite ? (float)sy : bad;
-            dshift[f * 2 + 1] = g.finite ? (float)sx : bad;
+            const float bad = qnan_f();
+            dshift[f * 2] = g.finite ? (float)sum[0] : bad;
+            dshift[f * 2 + 1] = g.finite ? (float)sum[1] : bad;
         }
     }
 }
@@ -174,7 +160,7 @@ __global__ __launch_bounds__(GZ_NT) void gaze_dshift_kernel(const float* __restr
 // of the addition, so that a plane of -0.0 sums to -0.0.
 __global__ __launch_bounds__(GZ_NT) void plane_mean_kernel(const float* __restrict__ x, float* __restrict__ mean, i64 nplanes,
                                                            int Cin, int T, int HW, int c0, int nc, int vec) {
-    __shared__ double red[2][GZ_NT];
+    __shared__ double red[GZ_NT];
     for (i64 f = blockIdx.x; f < nplanes; f += gridDim.x) {
         const i64 bt = f / nc;
         const int k = (int)(f - bt * nc);
@@ -191,14 +177,10 @@ __global__ __launch_bounds__(GZ_NT) void plane_mean_kernel(const float* __restri
         } else {
             for (int i = threadIdx.x; i < HW; i += GZ_NT) s0 += (double)p[i];
         }
-        s0 += s1;
-        s1 = -0.0;
-        wg_sum2(s0, s1, red);
-        if (threadIdx.x == 0) mean[f] = (float)(s0 / (double)HW);
+        const double tot = wg_tree_sum(s0 + s1, red);
+        if (threadIdx.x == 0) mean[f] = (float)(tot / (double)HW);
     }
 }
-
-inline bool aligned16(const void* p) { return ((size_t)p & 15) == 0; }
 
 }  // namespace
 

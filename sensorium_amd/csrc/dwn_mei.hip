@@ -19,7 +19,7 @@
 // depends on a tensor value; no atomics; every grid is a function of the geometry alone.
 #include "dwn_internal.h"
 #include "dwn_kernels.h"
-#include <float.h>
+#include "dwn_reduce.h"
 
 namespace {
 
@@ -41,7 +41,6 @@ inline Window window_of(const A& a) {
     const bool whole = a.wh == 0 && a.ww == 0;
     return Window{whole ? 0 : a.y0, whole ? 0 : a.x0, whole ? a.H : a.wh, whole ? a.W : a.ww};
 }
-inline bool aligned16(const void* p) { return ((size_t)p & 15) == 0; }
 
 // ---- blur: x then y, inside one frame
 __global__ __launch_bounds__(BL_NT) void blur_plane_kernel(const float* __restrict__ src, float* __restrict__ ws,
@@ -134,20 +133,7 @@ __global__ __launch_bounds__(BL_NT) void blur_time_kernel(const float* __restric
     else out[0] = acc[0];
 }
 
-// ---- moments
-// the sum over the workgroup, in every thread: a fixed butterfly inside each wave, then the waves in order
-__device__ __forceinline__ double wg_sum_all(double a, double* red) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) a += __shfl_xor(a, m, 64);
-    __syncthreads();                                           // red[] of the previous call has been read
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-    __syncthreads();
-    double s = red[0];
-#pragma unroll
-    for (int w = 1; w < MO_WAVES; ++w) s += red[w];
-    return s;
-}
-
+// ---- moments (the sums: dwn_reduce.h, a fixed butterfly inside each wave, then the waves in order)
 // address of window element i of a clip's channel (i = (t * wh + wy) * ww + wx)
 __device__ __forceinline__ i64 window_offset(int i, const Window& wd, int W, i64 HW) {
     const int per = wd.wh * wd.ww;
@@ -199,24 +185,18 @@ __global__ __launch_bounds__(MO_NT) void moments_partial_kernel(const float* __r
 #pragma unroll
     for (int k = 0; k < MO_PER; ++k)
         if (on[k]) { const double d = (double)v[k]; s += d; s2 += d * d; }
-    s = wg_sum_all(s, red);
-    s2 = wg_sum_all(s2, red);
+    s = wg_wave_sum<MO_NT>(s, red);
+    s2 = wg_wave_sum<MO_NT>(s2, red);
     const double mean = s / (double)nc;
     double m2 = 0.0;
 #pragma unroll
     for (int k = 0; k < MO_PER; ++k)
         if (on[k]) { const double d = (double)v[k] - mean; m2 += d * d; }
-    m2 = wg_sum_all(m2, red);
+    m2 = wg_wave_sum<MO_NT>(m2, red);
     if (threadIdx.x == 0) {
         double* p = part + (i64)blockIdx.x * 3;
         p[0] = s; p[1] = m2; p[2] = s2;
     }
-}
-
-__device__ __forceinline__ double wave_sum_all(double a) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) a += __shfl_xor(a, m, 64);
-    return a;
 }
 
 // one wave per clip
@@ -226,8 +206,8 @@ __global__ __launch_bounds__(64) void moments_fold_kernel(const double* __restri
     const double* p = part + b * nchunk * 3;
     double s = 0.0, s2 = 0.0;
     for (int ch = threadIdx.x; ch < nchunk; ch += 64) { s += p[ch * 3]; s2 += p[ch * 3 + 2]; }
-    s = wave_sum_all(s);
-    s2 = wave_sum_all(s2);
+    s = wave_sum(s);
+    s2 = wave_sum(s2);
     const double mean = s / (double)n;
     double m2 = 0.0;
     for (int ch = threadIdx.x; ch < nchunk; ch += 64) {
@@ -235,7 +215,7 @@ __global__ __launch_bounds__(64) void moments_fold_kernel(const double* __restri
         const double d = p[ch * 3] / nc - mean;
         m2 += p[ch * 3 + 1] + nc * (d * d);
     }
-    m2 = wave_sum_all(m2);
+    m2 = wave_sum(m2);
     if (threadIdx.x == 0) {
         double* o = stat + b * 4;
         o[0] = (double)n; o[1] = mean; o[2] = m2; o[3] = s2;
@@ -248,8 +228,6 @@ struct MeiCoef {
     float lo, hi;
     double mean_target, contrast;
 };
-
-__device__ __forceinline__ bool finite64(double v) { return fabs(v) <= DBL_MAX; }     // false for NaN and Inf
 
 template <bool VEC>
 __global__ __launch_bounds__(MO_NT) void mei_update_kernel(float* __restrict__ x, const float* __restrict__ g,
@@ -270,9 +248,9 @@ __global__ __launch_bounds__(MO_NT) void mei_update_kernel(float* __restrict__ x
     if constexpr (VEC) { const float4 q = *reinterpret_cast<const float4*>(px); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
     else v[0] = px[0];
     if (k.mode == DWN_MEI_STEP) {
-        if (!finite64(S2)) {
+        if (!is_finite(S2)) {
 #pragma unroll
-            for (int e = 0; e < PER; ++e) v[e] = __builtin_nanf("");
+            for (int e = 0; e < PER; ++e) v[e] = qnan_f();
         } else {
             if (S2 == 0.0) return;                             // the whole clip: no step
             const float* pg = g + (b * Cin_g + c_g) * T * HW + off;
@@ -284,9 +262,9 @@ __global__ __launch_bounds__(MO_NT) void mei_update_kernel(float* __restrict__ x
             for (int e = 0; e < PER; ++e) v[e] = (float)((double)v[e] + a * (double)gv[e]);
         }
     } else {
-        if (!(finite64(mu) && finite64(M2))) {
+        if (!(is_finite(mu) && is_finite(M2))) {
 #pragma unroll
-            for (int e = 0; e < PER; ++e) v[e] = __builtin_nanf("");
+            for (int e = 0; e < PER; ++e) v[e] = qnan_f();
         } else {
             const double sd = sqrt(M2 / cnt);
             const double m = k.has_mean ? k.mean_target : mu;

@@ -21,7 +21,7 @@
 #include "dwn_kernels.h"
 #include "dwn_launch.h"
 #include "dwn_gain.h"
-#include <float.h>
+#include "dwn_reduce.h"
 
 namespace {
 
@@ -49,7 +49,7 @@ inline ModGeom mod_geom(const dwn_modulator_args& a) {
     return g;
 }
 
-// mod_gain, mod_sech2, finite_f: dwn_gain.h (shared with the retinotopic readout gain)
+// mod_gain, mod_sech2: dwn_gain.h (shared with the retinotopic readout gain); is_finite, qnan_f: dwn_reduce.h
 
 // u and c of the neuron tile into LDS: us [MD_TN][KP] (zero beyond K and beyond N), cs [MD_TN]
 template <int KP>
@@ -69,7 +69,7 @@ __device__ __forceinline__ bool load_h(const float* __restrict__ hrow, int K, fl
 #pragma unroll
     for (int k = 0; k < KP; ++k) {
         hr[k] = k < K ? hrow[k] : 0.f;
-        ok = ok && finite_f(hr[k]);
+        ok = ok && is_finite(hr[k]);
     }
     return ok;
 }
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(MD_NT) void modulator_fwd_kernel(const float* __res
     if (ng >= NG || tl >= tcnt) return;
     float hr[KP];
     const bool ok = load_h<KP>(h + ((i64)b * g.T + t0 + tl) * g.K, g.K, hr);
-    const float bad = __builtin_nanf("");
+    const float bad = qnan_f();
     const i64 base = ((i64)b * g.N + n0) * g.T + t0 + tl;
     // MD_U loads in flight per thread (one per iteration left the pass bound by the latency of its loads); a neuron past the
     // tile's end is loaded from the last one (an address inside the tensor) and not stored
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(MD_NT) void modulator_bwd_kernel(const float* __res
     double acc[NACC];
 #pragma unroll
     for (int j = 0; j < NACC; ++j) acc[j] = 0.0;
-    const float bad = __builtin_nanf("");
+    const float bad = qnan_f();
 
     const int b_end = min(g.B, (grp + 1) * MD_RB);
     for (int b = grp * MD_RB; b < b_end; ++b) {

@@ -20,6 +20,7 @@
 // both builds (the file does not read DWN_DETERMINISTIC).
 #include "dwn_internal.h"
 #include "dwn_kernels.h"
+#include "dwn_reduce.h"
 
 namespace {
 
@@ -36,15 +37,6 @@ constexpr int CMP_ROWS = PW_NT / PW_WAVE;  // compare: rows per workgroup
 static_assert(SY_T % ST_TN == 0 && SY_KB % PW_KSTEP == 0 && PW_KSTEP == 4, "tile geometry");
 
 typedef double d4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double pw_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// sum over the 64 lanes; lane i and lane i ^ m add the same two values, so every lane ends with the same bits
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = PW_WAVE / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, PW_WAVE);
-    return v;
-}
 
 // the average over the R repeats of frame f of one neuron's rows (repeats in table order, float64, one division)
 __device__ __forceinline__ double repeat_mean(const dwn_pair_seg* sg, int R, i64 i, int f) {
@@ -235,7 +227,7 @@ __global__ __launch_bounds__(PW_NT) void pair_corr_kernel(const double* __restri
                                                           void* __restrict__ out) {
     const i64 j = (i64)blockIdx.x * PW_NT + threadIdx.x, i = blockIdx.y;
     if (j >= N) return;
-    double v = pw_nan();
+    double v = qnan_d();
     if (n > 0.0) v = (C[i * N + j] / n) / ((sqrt(C[i * N + i] / n) + eps) * (sqrt(C[j * N + j] / n) + eps));
     if (out_f32) ((float*)out)[i * N + j] = (float)v;
     else ((double*)out)[i * N + j] = v;
@@ -272,7 +264,7 @@ __global__ __launch_bounds__(PW_NT) void pair_compare_rows_kernel(const double* 
     const double anybad = wave_sum(bad ? 1.0 : 0.0);
     if (lane == 0) {
         double* st = stats + (i64)m * DWN_PAIR_ROW_STATS;
-        const double nan = pw_nan();
+        const double nan = qnan_d();
         if (anybad > 0.0 || !(cnt > 0.0)) {
             per_neuron[m] = nan;
             st[0] = cnt; st[1] = st[2] = st[3] = st[4] = st[5] = st[6] = st[7] = nan;
@@ -321,7 +313,7 @@ __global__ __launch_bounds__(PW_NT) void pair_compare_fold_kernel(const double* 
         poisoned |= empty_row[q];
         if (part[q].n > 0.0) pair_merge(tot, part[q]);
     }
-    const double nan = pw_nan();
+    const double nan = qnan_d();
     summary[0] = tot.n;
     if (poisoned || !(tot.n > 0.0) || tot.Cab != tot.Cab || tot.s1 != tot.s1) {      // a NaN entry on either side: all of it
         for (int q = 1; q < DWN_PAIR_SUMMARY; ++q) summary[q] = nan;

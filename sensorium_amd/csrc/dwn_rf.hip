@@ -21,6 +21,7 @@
 // inputs give the same bits on every launch and in both builds.
 #include "dwn_internal.h"
 #include "dwn_kernels.h"
+#include "dwn_reduce.h"
 
 namespace {
 
@@ -43,12 +44,6 @@ struct StaGeom {
     int B, Cin, T, H, W, N, channel, y0, x0, gh, gw, cell, L, t0, Tv;      // Tv = T - t0 valid frames per clip
     float s0, inv;                                                          // inv = 1 / cell^2, formed once on the host
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = RF_WAVE / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, RF_WAVE);
-    return v;
-}
 
 // v of the cell whose first pixel is (py, px) in `plane` (one frame of the stimulus channel)
 __device__ __forceinline__ float sta_cell(const float* __restrict__ plane, int W, int py, int px, int cell, float inv, float s0) {
@@ -214,7 +209,7 @@ __global__ __launch_bounds__(RF_NT) void sta_finalize_kernel(const double* __res
         if (e > ebest) { ebest = e; lbest = l; }
     }
     double* out = summary + j * DWN_STA_SUMMARY;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double nan = qnan_d();
     if (!(etot > 0.0)) {
         if (lane == 0) { out[0] = 0.0; out[1] = 0.0; out[2] = out[3] = out[4] = out[5] = nan; out[6] = 0.0; out[7] = 0.0; }
         return;

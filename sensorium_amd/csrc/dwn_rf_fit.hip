@@ -17,6 +17,7 @@
 // inputs give the same bits for any M, any row table, every launch and both builds.
 #include "dwn_internal.h"
 #include "dwn_kernels.h"
+#include "dwn_reduce.h"
 
 namespace {
 
@@ -38,14 +39,6 @@ struct GfArgs {
     int R, gh, gw, M, fit_b, max_iter;
     double rel, xtol, ftol;
 };
-
-__device__ __forceinline__ double gf_sum(double v) {
-#pragma unroll
-    for (int m = GF_WAVE / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, GF_WAVE);
-    return v;
-}
-__device__ __forceinline__ double gf_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ __forceinline__ bool gf_finite(double v) { return fabs(v) < __longlong_as_double(0x7ff0000000000000ll); }
 
 // the cells of one map as their owner lane sees them
 template <bool STAGE>
@@ -98,12 +91,12 @@ __device__ __forceinline__ double gf_pass(const GfMap<STAGE>& m, int G, int gw, 
             }
         }
     }
-    S = gf_sum(S);
+    S = wave_sum(S);
     if (NORMAL) {
 #pragma unroll
-        for (int i = 0; i < GF_NA; ++i) A[i] = gf_sum(A[i]);
+        for (int i = 0; i < GF_NA; ++i) A[i] = wave_sum(A[i]);
 #pragma unroll
-        for (int i = 0; i < GF_NP; ++i) g[i] = gf_sum(g[i]);
+        for (int i = 0; i < GF_NP; ++i) g[i] = wave_sum(g[i]);
         if (!fit_b) A[0] = 1.0;            // the baseline is held: row and column 0 are zero but for this pivot
     }
     return S;
@@ -126,7 +119,7 @@ __device__ __forceinline__ bool gf_chol(const double (&A)[GF_NA], double lam, do
         double d = Mx[j][j];
 #pragma unroll
         for (int q = 0; q < j; ++q) d -= Lf[j][q] * Lf[j][q];
-        ok = ok && (d > 0.0) && gf_finite(d);
+        ok = ok && (d > 0.0) && is_finite(d);
         const double piv = sqrt(d);
         Lf[j][j] = piv;
 #pragma unroll
@@ -173,7 +166,7 @@ __global__ __launch_bounds__(GF_NT) void gauss2d_fit_kernel(const float* __restr
     const int G = o.gh * o.gw, gw = o.gw;
     const UDiv32 dgw((unsigned)gw);
     const bool fit_b = o.fit_b != 0;
-    const double nan = gf_nan();
+    const double nan = qnan_d();
     double* prow = params + (i64)i * GF_NP;
     double* trow = table + (i64)i * DWN_GAUSS_TABLE;
     double* srow = start + (i64)i * 8;
@@ -210,7 +203,7 @@ __global__ __launch_bounds__(GF_NT) void gauss2d_fit_kernel(const float* __restr
     for (int c = lane; c < G; c += GF_WAVE) {
         const double v = m.at(c);
         const int y = (int)dgw.div((unsigned)c), x = c - y * gw;
-        if (!gf_finite(v)) nbad += 1.0;
+        if (!is_finite(v)) nbad += 1.0;
         if (y == 0 || y == o.gh - 1 || x == 0 || x == gw - 1) psum += v;
         tsum += v;
         if (first) { mn = v; mx = v; first = false; }
@@ -221,7 +214,7 @@ __global__ __launch_bounds__(GF_NT) void gauss2d_fit_kernel(const float* __restr
         const double mn0 = __shfl(mn, 0, GF_WAVE), mx0 = __shfl(mx, 0, GF_WAVE);
         if (first) { mn = mn0; mx = mx0; }
     }
-    nbad = gf_sum(nbad); psum = gf_sum(psum); tsum = gf_sum(tsum);
+    nbad = wave_sum(nbad); psum = wave_sum(psum); tsum = wave_sum(tsum);
 #pragma unroll
     for (int s = GF_WAVE / 2; s > 0; s >>= 1) {
         const double on = __shfl_xor(mn, s, GF_WAVE), ox = __shfl_xor(mx, s, GF_WAVE);
@@ -237,7 +230,7 @@ __global__ __launch_bounds__(GF_NT) void gauss2d_fit_kernel(const float* __restr
         sstot += t * t; sd2 += d * d;
         if (a > amax) { amax = a; imax = c; dpk = d; }
     }
-    sstot = gf_sum(sstot); sd2 = gf_sum(sd2);
+    sstot = wave_sum(sstot); sd2 = wave_sum(sd2);
 #pragma unroll
     for (int s = GF_WAVE / 2; s > 0; s >>= 1) {
         const double oa = __shfl_xor(amax, s, GF_WAVE), od = __shfl_xor(dpk, s, GF_WAVE);
@@ -246,7 +239,7 @@ __global__ __launch_bounds__(GF_NT) void gauss2d_fit_kernel(const float* __restr
     }
     const double a0 = dpk;
     if (nbad > 0.0 || mn == mx || a0 == 0.0) {
-        no_fit(gf_finite(b0) ? b0 : nan, gf_finite(sd2) ? sd2 : nan);
+        no_fit(is_finite(b0) ? b0 : nan, is_finite(sd2) ? sd2 : nan);
         return;
     }
     const double thr = o.rel * fabs(a0);
@@ -259,7 +252,7 @@ __global__ __launch_bounds__(GF_NT) void gauss2d_fit_kernel(const float* __restr
             sw += w; swy += w * (double)y; swx += w * (double)x;
         }
     }
-    sw = gf_sum(sw); swy = gf_sum(swy); swx = gf_sum(swx);
+    sw = wave_sum(sw); swy = wave_sum(swy); swx = wave_sum(swx);
     const double cy0 = swy / sw, cx0 = swx / sw;
     double qy = 0.0, qx = 0.0;
     for (int c = lane; c < G; c += GF_WAVE) {
@@ -270,7 +263,7 @@ __global__ __launch_bounds__(GF_NT) void gauss2d_fit_kernel(const float* __restr
             qy += w * (ey * ey); qx += w * (ex * ex);
         }
     }
-    qy = gf_sum(qy); qx = gf_sum(qx);
+    qy = wave_sum(qy); qx = wave_sum(qx);
     double sy = sqrt(qy / sw), sx = sqrt(qx / sw);
     sy = sy > 0.5 ? sy : 0.5; sx = sx > 0.5 ? sx : 0.5;
     p[0] = b0; p[1] = a0; p[2] = cy0; p[3] = cx0; p[4] = -log(sx); p[5] = 0.0; p[6] = -log(sy);
@@ -310,7 +303,7 @@ __global__ __launch_bounds__(GF_NT) void gauss2d_fit_kernel(const float* __restr
             double An[GF_NA], gn[GF_NP];
             (void)An; (void)gn;
             const double Sn = gf_pass<false, STAGE>(m, G, gw, dgw, lane, pn, fit_b, An, gn);
-            if (gf_finite(Sn) && Sn < S) {
+            if (is_finite(Sn) && Sn < S) {
                 dec = S - Sn;
 #pragma unroll
                 for (int k = 0; k < GF_NP; ++k) p[k] = pn[k];
@@ -376,10 +369,10 @@ __global__ __launch_bounds__(GF_NT) void gauss2d_profile_kernel(const double* __
     const int G = gh * gw;
     const UDiv32 dgw((unsigned)gw);
     const double* p = params + (i64)j * GF_NP;
-    const double nan = gf_nan();
+    const double nan = qnan_d();
     bool bad = false;
 #pragma unroll
-    for (int k = 0; k < GF_NP; ++k) bad = bad || !gf_finite(p[k]);
+    for (int k = 0; k < GF_NP; ++k) bad = bad || !is_finite(p[k]);
     if (bad) {
         for (int l = lane; l < L; l += GF_WAVE) profile[(i64)j * L + l] = nan;
         if (lane == 0) sep[j] = nan;
@@ -395,7 +388,7 @@ __global__ __launch_bounds__(GF_NT) void gauss2d_profile_kernel(const double* __
     };
     double se1 = 0.0, se2 = 0.0;
     for (int c = lane; c < G; c += GF_WAVE) { const double e = shape(c); se1 += e; se2 += e * e; }
-    se1 = gf_sum(se1); se2 = gf_sum(se2);
+    se1 = wave_sum(se1); se2 = wave_sum(se2);
     const double Gd = (double)G;
     const double det = Gd * se2 - se1 * se1;
     double sse_all = 0.0, sst_all = 0.0;
@@ -403,7 +396,7 @@ __global__ __launch_bounds__(GF_NT) void gauss2d_profile_kernel(const double* __
         const float* mp = maps + ((i64)j * L + l) * G;
         double sm = 0.0, sme = 0.0;
         for (int c = lane; c < G; c += GF_WAVE) { const double v = (double)mp[c]; sm += v; sme += v * shape(c); }
-        sm = gf_sum(sm); sme = gf_sum(sme);
+        sm = wave_sum(sm); sme = wave_sum(sme);
         double al, bl, mu;
         if (fit_b) {
             al = det > 0.0 ? (Gd * sme - se1 * sm) / det : 0.0;
@@ -419,7 +412,7 @@ __global__ __launch_bounds__(GF_NT) void gauss2d_profile_kernel(const double* __
             const double r = v - (bl + al * shape(c)), t = v - mu;
             sse += r * r; sst += t * t;
         }
-        sse = gf_sum(sse); sst = gf_sum(sst);
+        sse = wave_sum(sse); sst = wave_sum(sst);
         sse_all += sse; sst_all += sst;
         if (lane == 0) profile[(i64)j * L + l] = al;
     }

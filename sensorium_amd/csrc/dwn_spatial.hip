@@ -32,6 +32,7 @@
 #include "dwn_kernels.h"
 #include "dwn_launch.h"
 #include "dwn_gain.h"
+#include "dwn_reduce.h"
 
 namespace {
 
@@ -64,7 +65,7 @@ inline SpGeom sp_geom(const dwn_spatial_gain_args& a) {
     g.nTc = (a.T + g.TT - 1) / g.TT;
     g.nNt = (a.N + SP_NT - 1) / SP_NT;
     g.G = (a.B + SP_RB - 1) / SP_RB;
-    g.vec = (a.K % 8 == 0) && (((size_t)a.g & 15) == 0);
+    g.vec = (a.K % 8 == 0) && aligned16(a.g);
     return g;
 }
 
@@ -79,7 +80,7 @@ __device__ __forceinline__ void sp_axis(float v, int n, int& i0, int& i1, float&
 
 __device__ __forceinline__ SpEnt sp_decide(float x, float y, int Hf, int Wf) {
     SpEnt e;
-    const bool bad = !finite_f(x) || !finite_f(y);
+    const bool bad = !is_finite(x) || !is_finite(y);
     e.flags = (bad ? SP_BAD : 0) | ((!bad && x >= -1.f && x <= 1.f && Wf > 1) ? SP_LIVE_X : 0) |
               ((!bad && y >= -1.f && y <= 1.f && Hf > 1) ? SP_LIVE_Y : 0);
     if (bad) { x = 0.f; y = 0.f; }                       // indices stay inside the map; the flag decides what is written
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(SP_NT) void spatial_elem_kernel(const float* __rest
     }
     const bool isbad = (e.flags & SP_BAD) != 0;
     const i64 e00 = (i64)e.c00 * K, e01 = (i64)e.c01 * K, e10 = (i64)e.c10 * K, e11 = (i64)e.c11 * K;
-    const float bad = __builtin_nanf("");
+    const float bad = qnan_f();
     double dW[BWD ? KP : 1], dB = 0.0, dX = 0.0, dY = 0.0;
 #pragma unroll
     for (int k = 0; k < (BWD ? KP : 1); ++k) dW[k] = 0.0;
@@ -426,7 +427,7 @@ __global__ __launch_bounds__(256) void spatial_finalize_kernel(const double* __r
         const int flags = table[n].flags;
         const double scale = 0.5 * (double)((c ? Hf : Wf) - 1);
         float v = 0.f;                                   // clamped, or a one-cell axis: exactly 0
-        if (flags & SP_BAD) v = __builtin_nanf("");
+        if (flags & SP_BAD) v = qnan_f();
         else if (flags & (c ? SP_LIVE_Y : SP_LIVE_X)) v = (float)(s * scale);
         dpos[j] = v;
     }

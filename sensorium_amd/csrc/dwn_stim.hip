@@ -15,7 +15,7 @@
 #include "dwn_internal.h"
 #include "dwn_kernels.h"
 #include "dwn_launch.h"
-#include <float.h>
+#include "dwn_reduce.h"
 
 namespace {
 
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(GB_NT) void gabor_stream_kernel(const float* __rest
             continue;
         }
         const GaborClip g = gabor_clip(params + b * 8, GAUSS);
-        const float ft = (float)t, bad = __builtin_nanf("");
+        const float ft = (float)t, bad = qnan_f();
         for (int i = threadIdx.x; i < HW; i += GB_NT) {
             const int y = (int)divW.div((unsigned)i), x = i - y * W;
             const bool inside = (unsigned)(y - gm.y0) < (unsigned)gm.wh && (unsigned)(x - gm.x0) < (unsigned)gm.ww;
@@ -162,10 +162,7 @@ __global__ __launch_bounds__(GB_NT) void gabor_partial_kernel(const float* __res
     }
     // fixed butterfly inside the wave, then the waves in order
 #pragma unroll
-    for (int k = 0; k < GB_NSUM - 1; ++k) {
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) acc[k] += __shfl_xor(acc[k], m, 64);
-    }
+    for (int k = 0; k < GB_NSUM - 1; ++k) acc[k] = wave_sum(acc[k]);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (lane == 0) {
 #pragma unroll
@@ -227,7 +224,7 @@ __global__ __launch_bounds__(GB_NT) void gabor_finalize_kernel(const float* __re
         o[5] = tau * A * S7;
         o[6] = -A * S1;
         o[7] = S0;
-        const float bad = __builtin_nanf("");
+        const float bad = qnan_f();
 #pragma unroll
         for (int j = 0; j < 8; ++j) dparams[b * 8 + j] = g.ok ? (float)o[j] : bad;
     }
@@ -282,8 +279,6 @@ __global__ __launch_bounds__(GB_NT) void noise_stream_kernel(const float* __rest
         }
     }
 }
-
-inline bool aligned16(const void* p) { return ((size_t)p & 15) == 0; }
 
 inline GaborGeom gabor_geom(const dwn_gabor_args& a) {
     GaborGeom gm;

@@ -22,6 +22,7 @@
 // (the file does not read DWN_DETERMINISTIC).
 #include "dwn_internal.h"
 #include "dwn_kernels.h"
+#include "dwn_reduce.h"
 
 namespace {
 
@@ -32,13 +33,6 @@ constexpr int TS_U = 4;                // frames per lane in flight
 constexpr int TS_CHUNK = TS_U * TS_WAVE;
 constexpr int TS_PARTS = 5;           // summary partials per workgroup: sum r1, sum r2, sum r4, sum of the masked feve, mask count
 static_assert(TS_TILE * TS_WAVE == TS_NT, "one wave per neuron of the tile");
-
-// sum over the 64 lanes; lane i and lane i ^ m add the same two values, so every lane ends with the same bits
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = TS_WAVE / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, TS_WAVE);
-    return v;
-}
 
 // pairwise merge of (mean_a, mean_b, M2a, M2b, Cab) with counts na (state s..) and nb > 0 (new); an empty state is replaced
 __device__ __forceinline__ void chan5(double na, double nb, double& s_ma, double& s_mb, double& s_M2a, double& s_M2b, double& s_C,
@@ -173,20 +167,8 @@ __global__ __launch_bounds__(TS_NT) void trial_moments_kernel(const dwn_trial_de
     }
 }
 
-// fixed-order sum over the workgroup; the result is valid in thread 0
-__device__ __forceinline__ double ts_wg_sum(double a, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int s = TS_NT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 __device__ __forceinline__ double pearson(double Ma, double Mb, double Cab, double n, double eps) {
-    if (!(n > 0.0)) return __longlong_as_double(0x7ff8000000000000ll);
+    if (!(n > 0.0)) return qnan_d();
     return (Cab / n) / ((sqrt(Ma / n) + eps) * (sqrt(Mb / n) + eps));
 }
 
@@ -195,7 +177,7 @@ __global__ __launch_bounds__(TS_NT) void trial_finalize_kernel(const double* __r
                                                                double* __restrict__ partial) {
     __shared__ double red[TS_NT];
     const i64 j = (i64)blockIdx.x * TS_NT + threadIdx.x;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double nan = qnan_d();
     double v[TS_PARTS] = {0.0, 0.0, 0.0, 0.0, 0.0};
     if (j < N) {
         auto S = [&](int q) { return state[(i64)q * N + j]; };
@@ -214,7 +196,7 @@ __global__ __launch_bounds__(TS_NT) void trial_finalize_kernel(const double* __r
     }
 #pragma unroll
     for (int q = 0; q < TS_PARTS; ++q) {
-        const double tot = ts_wg_sum(v[q], red);
+        const double tot = wg_tree_sum(v[q], red);     // dwn_reduce.h: the fixed tree
         if (threadIdx.x == 0) partial[(i64)blockIdx.x * TS_PARTS + q] = tot;
     }
 }
@@ -228,11 +210,11 @@ __global__ __launch_bounds__(TS_NT) void trial_fold_kernel(const double* __restr
     for (int q = 0; q < TS_PARTS; ++q) {
         double a = 0.0;
         for (int i = threadIdx.x; i < nparts; i += TS_NT) a += partial[(i64)i * TS_PARTS + q];
-        tot[q] = ts_wg_sum(a, red);
+        tot[q] = wg_tree_sum(a, red);
     }
     if (threadIdx.x == 0) {
         summary[0] = tot[0] / (double)N; summary[1] = tot[1] / (double)N; summary[2] = tot[2] / (double)N;
-        summary[3] = tot[4] > 0.0 ? tot[3] / tot[4] : __longlong_as_double(0x7ff8000000000000ll);
+        summary[3] = tot[4] > 0.0 ? tot[3] / tot[4] : qnan_d();
         summary[4] = tot[4];
         summary[5] = n_all; summary[6] = n_rep; summary[7] = n_gf;
     }

@@ -3,15 +3,12 @@ no grid that depends on the build, so a fresh child process on the deterministic
 library in this process — moments, coefficients, loss accumulator, fp32 loss and dpred of the fixed cases of tests/test_gpu_corr.py,
 compared through one digest."""
 import os
-import re
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+from tests.det_child import deterministic_child
+
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parents[1]
 
 
 def test_deterministic_build_gives_the_bits_of_the_product_build():
@@ -21,14 +18,8 @@ def test_deterministic_build_gives_the_bits_of_the_product_build():
         pytest.skip("libdwiseneuro_hip_det.so is not built")
     assert L.LIB_PATH.name == "libdwiseneuro_hip.so" or os.environ.get("DWN_LIB_PATH") or L.DETERMINISTIC
     tensors, digest = corr_digest()
-    env = dict(os.environ, DWN_DETERMINISTIC="1")
-    env.pop("DWN_LIB_PATH", None)
-    res = subprocess.run([sys.executable, str(ROOT / "tests" / "det_corr_worker.py")], cwd=str(ROOT), env=env, capture_output=True,
-                         text=True, timeout=300)
-    m = re.search(r"DET_CORR deterministic=(\d) lib=(\S+) tensors=(\d+) digest=([0-9a-f]{64})", res.stdout)
-    assert res.returncode == 0 and m, res.stdout[-2000:] + res.stderr[-3000:]
-    print(m.group(0))
+    deterministic, lib, (child_tensors, child_digest) = deterministic_child("tests.test_gpu_corr:corr_digest")
     print(f"this process ({L.LIB_PATH.name}): tensors={tensors} digest={digest}")
-    assert m.group(1) == "1" and m.group(2) == "libdwiseneuro_hip_det.so"
-    assert int(m.group(3)) == tensors == 5 * len(DIGEST_CASES)
-    assert m.group(4) == digest, "the deterministic build and the product build disagree in at least one bit"
+    assert deterministic == "1" and lib == "libdwiseneuro_hip_det.so"
+    assert child_tensors == tensors == 5 * len(DIGEST_CASES)
+    assert child_digest == digest, "the deterministic build and the product build disagree in at least one bit"

@@ -13,19 +13,14 @@ The sums of magnitudes come from the checker.  Every output buffer sits between 
 """
 import ctypes as C
 import math
-import os
-import re
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parents[1]
 
 from tests import gaze_reference as gr  # noqa: E402
+from tests.det_child import deterministic_child  # noqa: E402
 from tests.gpu_helpers import dev  # noqa: E402
 
 U = 2.0 ** -24
@@ -279,15 +274,9 @@ def test_deterministic_build_two_calls_give_equal_bits():
     import sensorium_amd._lib as L
     if not (L._HERE / "csrc" / "libdwiseneuro_hip_det.so").exists():
         pytest.skip("libdwiseneuro_hip_det.so is not built")
-    env = dict(os.environ, DWN_DETERMINISTIC="1")
-    env.pop("DWN_LIB_PATH", None)
-    res = subprocess.run([sys.executable, str(ROOT / "tests" / "det_gaze_worker.py")], cwd=str(ROOT), env=env, capture_output=True,
-                         text=True, timeout=300)
-    m = re.search(r"DET_GAZE deterministic=(\d) lib=(\S+) tensors=(\d+) differing=(\d+)", res.stdout)
-    assert res.returncode == 0 and m, res.stdout[-2000:] + res.stderr[-3000:]
-    print(m.group(0))
-    assert m.group(1) == "1" and m.group(2) == "libdwiseneuro_hip_det.so"
-    assert int(m.group(3)) == 4 * len(CASES) and int(m.group(4)) == 0
+    deterministic, lib, (tensors, differing) = deterministic_child("tests.test_gpu_gaze_shift:repeat_report")
+    assert deterministic == "1" and lib == "libdwiseneuro_hip_det.so"
+    assert tensors == 4 * len(CASES) and differing == 0
 
 
 # --------------------------------------------------------------------------------------------------------------- 5. plane mean

@@ -4,17 +4,12 @@ gradient, the mean / contrast constraints hold after every step, per-clip object
 set, and the captured graph gives the bits of the eager loop.  Every test prints what it measured before it asserts.
 
 Bit-for-bit statements about two runs THROUGH THE MODEL are made in the ordered-reduction build (DWN_DETERMINISTIC=1, a child
-process: tests/det_mei_model_worker.py).  The product build leaves the order of some of the model's sums to the arrival of waves and
+process: tests/det_child.py runs bitwise_report()).  The product build leaves the order of some of the model's sums to the arrival of waves and
 workgroups (csrc/dwn_common.h), so there the same ascent run twice differs in the last bits — measured here with the verbatim copy
 of the plain loop against the plain loop itself — and equal bits would say nothing about the code under test.  In the product build
 the graph is held to the eager loop at the standing fp32 bound instead."""
 import functools
 import math
-import os
-import re
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 import torch
@@ -22,6 +17,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import mei_reference as mr  # noqa: E402
+from tests.det_child import deterministic_child  # noqa: E402
 from tests.gpu_helpers import dev, rel  # noqa: E402
 from tests.test_gpu_frozen_bn import _model_input, tiny_model  # noqa: E402
 
@@ -29,7 +25,6 @@ INDEX, NEURONS = 1, [0, 3, 4, 9]
 T, H, W = 6, 9, 11
 WINDOW = (1, 1, 7, 9)
 WIDE = (-1e4, 1e4)           # a video range that never clamps
-ROOT = Path(__file__).resolve().parents[1]
 
 
 def start(batch, seed=4):
@@ -243,7 +238,7 @@ def test_five_calls_of_one_step_are_one_call_of_five_steps():
 
 
 def bitwise_report():
-    """What must hold bit for bit when the model itself is reproducible: name -> bool.  Run by tests/det_mei_model_worker.py."""
+    """What must hold bit for bit when the model itself is reproducible: name -> bool.  Run in a child process (tests/det_child.py)."""
     out = {}
     for nb in (None, 300.0):
         (gx, gt), (wx, wt) = plain_path_pair(nb)
@@ -264,11 +259,6 @@ def deterministic_report():
     import sensorium_amd._lib as L
     if not (L._HERE / "csrc" / "libdwiseneuro_hip_det.so").exists():
         pytest.skip("libdwiseneuro_hip_det.so is not built")
-    env = dict(os.environ, DWN_DETERMINISTIC="1")
-    env.pop("DWN_LIB_PATH", None)
-    res = subprocess.run([sys.executable, str(ROOT / "tests" / "det_mei_model_worker.py")], cwd=str(ROOT), env=env, capture_output=True,
-                         text=True, timeout=300)
-    m = re.search(r"DET_MEI_MODEL deterministic=1 lib=libdwiseneuro_hip_det\.so (.*)", res.stdout)
-    assert res.returncode == 0 and m, res.stdout[-2000:] + res.stderr[-3000:]
-    print(m.group(0))
-    return dict(kv.split("=") for kv in m.group(1).split())
+    deterministic, lib, report = deterministic_child("tests.test_gpu_model_mei:bitwise_report")
+    assert deterministic == "1" and lib == "libdwiseneuro_hip_det.so"
+    return {k: str(int(v)) for k, v in report.items()}

@@ -305,7 +305,7 @@ def test_python_layer_builds_the_same_tables():
 
 
 def trial_score_digest():
-    """sha256 over state, scores and summary of the fixed cases (tests/test_gpu_trial_score_det.py, tests/det_trial_score_worker.py)."""
+    """sha256 over state, scores and summary of the fixed cases (tests/test_gpu_trial_score_det.py, here and in a child process)."""
     h, n = hashlib.sha256(), 0
     for trials in (tc.mixed_case(), tc.hard_case(), tc.fev_case()[0]):
         for t in gpu_run(trials)[:3]:
