@@ -461,7 +461,7 @@ int dwn_pack_weight(const float* src, void* dst, int groups, int R, int C, int t
  * weights the matrix cores multiply with).  Writes bn->coef [4][E] = scale, shift, mean, invstd and updates the running statistics
  * and num_batches_tracked like nn.BatchNorm3d.  sc_stats (optional, double[DWN_NREP][2][Cin], zeroed by the caller): receives the
  * shortcut BatchNorm's sums of an identity-map block (sum a0, sum a0^2 per channel) in replica 0.  ws: caller-owned scratch. */
-size_t dwn_conv_pw_bn_stats_workspace_bytes(int Cin);    /* (Cin + 8) * Cin doubles + alignment */
+size_t dwn_conv_pw_bn_stats_workspace_bytes(int Cin);    /* replicas x (Cin + 8) * Cin doubles + alignment (8 replicas at Cin = 64) */
 int dwn_conv_pw_bn_stats(const void* a0, long long a0_ld, long long M, const float* w_pw, int E, int Cin, const dwn_bn* bn,
                          float momentum, float eps, double* sc_stats, void* ws, size_t ws_bytes, int dtype, int device,
                          void* stream);

@@ -444,7 +444,7 @@ class DwnError(RuntimeError):
 
 # csrc/Makefile HASH_SRCS, in its order
 HASH_SRCS = ("dwn_api.hip", "dwn_gemm.hip", "dwn_gemm_nn_1.hip", "dwn_gemm_nn_2.hip", "dwn_gemm_nn_3.hip", "dwn_gemm_nn_4.hip", "dwn_gemm_nn_5.hip",
-             "dwn_gemm_nn_6.hip", "dwn_gemm_tn.hip", "dwn_pw_bwd.hip", "dwn_gemm_xl.hip", "dwn_gemm_kd.hip", "dwn_dwconv.hip", "dwn_dwrc.hip",
+             "dwn_gemm_nn_6.hip", "dwn_gemm_tn.hip", "dwn_gram.hip", "dwn_pw_bwd.hip", "dwn_gemm_xl.hip", "dwn_gemm_kd.hip", "dwn_dwconv.hip", "dwn_dwrc.hip",
              "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_spatial.hip", "dwn_mei.hip", "dwn_rf_fit.hip", "dwn_pairwise.hip", "dwn_trial_score.hip", "dwn_rf.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
              "dwn_kernels.h", "dwn_launch.h", "dwn_gemm_nn.h", "dwn_gain.h", "dwn_reduce.h",
              "../../include/dwn.h")

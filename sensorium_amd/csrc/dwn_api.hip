@@ -175,7 +175,7 @@ struct BlockWs {
     float* tacc;                                           // conv_pw weight gradient: raw products T1 / Ga / s (k_pw_wgrad_fold)
     void* wgated;                                          // [B][Cout][Cmid] W2 . diag(gate_b) (forward only)
     void* rcblob;                                          // forward: slice images of the y1-recomputing stencil
-    double* gram;                                          // y1-free training forward: [(Cin + 8)][Cin] raw products a0^T a0, 1^T a0 (fp64 atomics)
+    double* gram;                                          // y1-free training forward: gram_nrep() x [(Cin + 8)][Cin] raw products a0^T a0, 1^T a0 (fp64 atomics)
     float* pb;                                             // [B][Cout][Cmid] per-sample dy4^T z3 (backward, see pwl_bwd_per_sample)
     char* zero_beg; char* zero_end;
     size_t bytes;
@@ -252,7 +252,7 @@ BlockWs carve_block(const dwn_block_args& a, int backward, void* base, size_t ca
     w.st4 = c.take<double>(nstat(a.Cout));
     w.stsc = c.take<double>(nstat(backward ? a.Cout : a.Cin));
     w.pooled = c.take<long long>((size_t)a.B * a.Cmid);
-    if (!backward && block_y1_free(a)) w.gram = c.take<double>((size_t)(a.Cin + 8) * a.Cin);
+    if (!backward && block_y1_free(a)) w.gram = c.take<double>((size_t)gram_nrep(a.dtype, a.Cin) * (a.Cin + 8) * a.Cin);
     size_t z1 = c.off;
     if (backward) {
         w.abc1 = c.take<float>(3 * (size_t)a.Cmid);
@@ -399,7 +399,11 @@ int dwn_bn_bwd_finalize(const double* stats, double count, const dwn_bn* bn, flo
     return k_bn_bwd_finalize(bwd_job(stats, count, *bn, abc, C, false), BnBwdJob{}, (hipStream_t)stream);
 }
 // BatchNorm-1 of conv_pw WITHOUT conv_pw's output (dwn.h): raw products [a0 | 1]^T a0 by one gemm_tn pass, then k_bn1_gram_finalize
-size_t dwn_conv_pw_bn_stats_workspace_bytes(int Cin) { return (size_t)(Cin + 8) * Cin * sizeof(double) + 256; }
+// (sized for the replicas of the streaming kernel of dwn_gram.hip where either dtype has them)
+size_t dwn_conv_pw_bn_stats_workspace_bytes(int Cin) {
+    const int nrep = gram_nrep(DWN_BF16, Cin) > gram_nrep(DWN_F32, Cin) ? gram_nrep(DWN_BF16, Cin) : gram_nrep(DWN_F32, Cin);
+    return (size_t)nrep * (Cin + 8) * Cin * sizeof(double) + 256;
+}
 int dwn_conv_pw_bn_stats(const void* a0, long long a0_ld, long long M, const float* w_pw, int E, int Cin, const dwn_bn* bn,
                          float momentum, float eps, double* sc_stats, void* ws, size_t ws_bytes, int dtype, int device, void* stream) {
     ENTER(device);
@@ -408,13 +412,18 @@ int dwn_conv_pw_bn_stats(const void* a0, long long a0_ld, long long M, const flo
     if (Cin % 8 || E <= 0 || M <= 0 || M >= (1ll << 31)) return dwn_set_error(-2, "conv_pw_bn_stats: Cin % 8 == 0, 0 < M < 2^31");
     if (ws_bytes < dwn_conv_pw_bn_stats_workspace_bytes(Cin)) return dwn_set_error(-6, "conv_pw_bn_stats: workspace too small");
     double* gram = reinterpret_cast<double*>(((size_t)ws + 255) & ~(size_t)255);
-    TRY(k_zero(gram, (size_t)(Cin + 8) * Cin * sizeof(double), s));
-    LoadDesc cat = ld_plain(a0, a0_ld);
-    cat.cat_c1 = Cin; cat.cat_c2 = 0;
-    GemmTN g = tn_base(cat, LD_CAT1, ld_plain(a0, a0_ld), LD_PLAIN, (int)M, Cin + 8, Cin, reinterpret_cast<float*>(gram), Cin, 1);
-    g.dw_f64 = 1;
-    TRY(launch_gemm_tn(g, dtype, s));
-    return k_bn1_gram_finalize(gram, w_pw, E, Cin, (double)M, bn->gamma, bn->beta, bn->running_mean, bn->running_var,
+    const int nrep = gram_nrep(dtype, Cin);
+    TRY(k_zero(gram, (size_t)nrep * (Cin + 8) * Cin * sizeof(double), s));
+    bool streamed = false;
+    TRY(k_gram(a0, a0_ld, M, Cin, gram, dtype, &streamed, s));
+    if (!streamed) {
+        LoadDesc cat = ld_plain(a0, a0_ld);
+        cat.cat_c1 = Cin; cat.cat_c2 = 0;
+        GemmTN g = tn_base(cat, LD_CAT1, ld_plain(a0, a0_ld), LD_PLAIN, (int)M, Cin + 8, Cin, reinterpret_cast<float*>(gram), Cin, 1);
+        g.dw_f64 = 1;
+        TRY(launch_gemm_tn(g, dtype, s));
+    }
+    return k_bn1_gram_finalize(gram, streamed ? nrep : 1, w_pw, E, Cin, (double)M, bn->gamma, bn->beta, bn->running_mean, bn->running_var,
                                bn->num_batches_tracked, momentum, eps, bn->coef, sc_stats, dtype, s);
 }
 int dwn_pack_weight(const float* src, void* dst, int groups, int R, int C, int transpose, int Rd, int Cd, int dtype,
@@ -589,10 +598,15 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
         LoadDesc cat = ld_plain(a0, a.Cin);
         cat.cat_c1 = a.Cin; cat.cat_c2 = 0;
         if (bs) {                                     // (frozen: BatchNorm-1 is known, no Gram pass)
+        // the streaming kernel of dwn_gram.hip where it is built (bf16, 64 channels: one read of a0, gram_nrep replicas), else gemm_tn
+        bool streamed = false;
+        PROF(DWN_FAM_PW_FWD, k_gram(a0, a.Cin, Min, a.Cin, w.gram, dt, &streamed, s));
+        if (!streamed) {
         GemmTN g = tn_base(cat, LD_CAT1, ld_plain(a0, a.Cin), LD_PLAIN, (int)Min, a.Cin + 8, a.Cin, reinterpret_cast<float*>(w.gram), a.Cin, 1);
         g.dw_f64 = 1;                                 // fp64 atomics: the variance is a difference of these sums
         PROF(DWN_FAM_PW_FWD, launch_gemm_tn(g, dt, s));
-        PROF(DWN_FAM_PW_FWD, k_bn1_gram_finalize(w.gram, a.w_pw, a.Cmid, a.Cin, (double)Min, a.bn1.gamma, a.bn1.beta, a.bn1.running_mean,
+        }
+        PROF(DWN_FAM_PW_FWD, k_bn1_gram_finalize(w.gram, streamed ? gram_nrep(dt, a.Cin) : 1, a.w_pw, a.Cmid, a.Cin, (double)Min, a.bn1.gamma, a.bn1.beta, a.bn1.running_mean,
                                                  a.bn1.running_var, a.bn1.num_batches_tracked, a.momentum, a.eps, a.bn1.coef,
                                                  identity_sc ? w.stsc : nullptr, dt, s));
         }
@@ -686,7 +700,7 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
 // plane sizes; the x terms then stay in the kernel's epilogue (only sampled rows have them).
 static int pw_backward(int dt, const void* dh1, const void* a0, const float* w_pw, const float* abc, int E, int Cin, i64 M,
                        void* bp, float* gacc, float* r3, float* tacc, void* da0, float* dw, const void* res,
-                       const float* res_abc, int res_C, const ResGeom* rg, hipStream_t s) {
+                       const float* res_abc, int res_C, const ResGeom* rg, hipStream_t s, bool fold = true) {
     const int res_n = res ? res_C / Cin : 0;
     const bool gathered = res && rg && rg->hinv;
     if (res && (!res_abc || res_C % Cin || res_n < 1 || res_n > 2))
@@ -712,6 +726,7 @@ static int pw_backward(int dt, const void* dh1, const void* a0, const float* w_p
             PROF(DWN_FAM_PW_WGRAD, launch_gemm_tn(g, dt, s));
         }
     }
+    if (!fold) return 0;            // dwn_block_backward folds tacc in its parameter-gradient tail (k_block_param_tail)
     return k_pw_wgrad_fold(tacc, abc, w_pw, E, Cin, dw, dt, s);
 }
 
@@ -771,7 +786,7 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
         }
         PROF(DWN_FAM_PWL_WGRAD, k_pwl_bwd_reduce(w.pb, a.se_gate, a.w_pwl, a.B, a.Cout, a.Cmid, a.dw_pwl, dg, s));
         TRY(k_se_mlp_bwd(dg, a.se_gate, a.se_hidpre, a.se_pmean, a.se_wr, a.se_we, a.B, a.Cmid, a.se_r,
-                         1.0f / (float)S_out, w.dgp, w.dhp, w.dps, a.dse_wr, a.dse_br, a.dse_we, a.dse_be, s));
+                         1.0f / (float)S_out, w.dgp, w.dhp, w.dps, a.dse_wr, a.dse_br, a.dse_we, a.dse_be, s, false));
         // dh3 = (du*gate + dpS) * silu'(bn3(y3)) with du = dy4 . W2 recomputed in the GEMM, plus the bn3 backward sums
         GemmNN g = nn_base(ld_plain(a.dy4, a.Cout), LD_PLAIN, w.wpwl, a.Cout, du, a.Cmid, (int)Mout, a.Cmid, a.Cout, 1);
         g.epi = EPI_DH3; g.y3 = a.y3; g.ldy3 = a.Cmid; g.gate3 = a.se_gate; g.dps3 = w.dps; g.dg_ld = a.Cmid;
@@ -793,7 +808,7 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
     }
     // SE backward
     TRY(k_se_mlp_bwd(dg, a.se_gate, a.se_hidpre, a.se_pmean, a.se_wr, a.se_we, a.B, a.Cmid, a.se_r,
-                     1.0f / (float)S_out, w.dgp, w.dhp, w.dps, a.dse_wr, a.dse_br, a.dse_we, a.dse_be, s));
+                     1.0f / (float)S_out, w.dgp, w.dhp, w.dps, a.dse_wr, a.dse_br, a.dse_we, a.dse_be, s, false));
     // bn3 backward sums over dh3 = (du*gate + dpS) * silu'(h3)
     LoadDesc d3; memset(&d3, 0, sizeof(d3));
     d3.p = du; d3.q = a.y3; d3.ld = a.Cmid; d3.v1 = w.ident3; d3.v2 = w.ident3 + a.Cmid; d3.v3 = w.ident3 + 2 * a.Cmid;
@@ -837,10 +852,12 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
     const bool dx_folded = a.Cout % a.Cin == 0 && a.Cout / a.Cin <= 2 && dwn_pw_bwd_fused_supported(dt, Min, a.Cmid, a.Cin) &&
                            (identity_sc || (gm.hinv && gm.winv && a.Hin + a.Win <= 512));
     TRY(pw_backward(dt, dh1, xin.p, a.w_pw, w.abc1, a.Cmid, a.Cin, Min, w.bp, w.gacc, w.r3, w.tacc, dx_folded ? a.dx : a.da0, a.dw_pw,
-                    dx_folded ? a.dout : nullptr, w.abcsc, a.Cout, (dx_folded && !identity_sc) ? &gm : nullptr, s));
-    if (dx_folded) return 0;
-    PROF(DWN_FAM_RESID_BWD, k_residual_bwd_dx(xin, a.da0, a.dout, w.abcsc, gm, a.dx, dt, s));
-    return 0;
+                    dx_folded ? a.dout : nullptr, w.abcsc, a.Cout, (dx_folded && !identity_sc) ? &gm : nullptr, s, false));
+    if (!dx_folded) PROF(DWN_FAM_RESID_BWD, k_residual_bwd_dx(xin, a.da0, a.dout, w.abcsc, gm, a.dx, dt, s));
+    // the parameter-gradient tail, last launch of the block: the SE MLP's parameter gradients (from dgp / dhp, k_se_mlp_bwd above)
+    // and dW1 folded from tacc.  Nothing in the block reads them, so they leave the chain between the SE kernel and the dh3 GEMM
+    return k_block_param_tail(w.dgp, w.dhp, a.se_pmean, a.se_hidpre, a.B, a.Cmid, a.se_r, a.dse_wr, a.dse_br, a.dse_we, a.dse_be,
+                              w.tacc, w.abc1, a.w_pw, a.Cmid, a.Cin, a.dw_pw, dt, s);
 }
 
 // Which of the intermediates dwn_block_forward will write for these arguments: bit 0 = y1, bit 1 = y3.  Training writes

@@ -199,6 +199,25 @@ int k_bn_finalize_eval(const float* gamma, const float* beta, const float* rm, c
 // sc_stats != NULL: the same raw products also are the shortcut BatchNorm's sums on an identity-map block (its input is a0):
 // block 0 writes sum x = 1^T a0 and sum x^2 = diag(G) into replica 0 of that statistics buffer (zeroed by the caller).
 // ------------------------------------------------------------------------------------------------
+// one channel's coefficients and running statistics from lin = w . (1^T a0) and quad = w^T G w
+__device__ __forceinline__ void bn1_gram_write(int e, int E, double lin, double quad, double count, const float* gamma, const float* beta,
+                                               float* running_mean, float* running_var, float momentum, float eps, float* coef) {
+    const double inv_n = 1.0 / count;
+    const double mean = lin * inv_n;
+    double var = quad * inv_n - mean * mean;
+    if (var < 0) var = 0;
+    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+    const float scale = gamma[e] * invstd;
+    coef[e] = scale;
+    coef[E + e] = beta[e] - (float)mean * scale;
+    coef[2 * E + e] = (float)mean;
+    coef[3 * E + e] = invstd;
+    if (running_mean) {
+        const double unbiased = count > 1 ? var * count / (count - 1) : var;
+        running_mean[e] = (1.f - momentum) * running_mean[e] + momentum * (float)mean;
+        running_var[e] = (1.f - momentum) * running_var[e] + momentum * (float)unbiased;
+    }
+}
 template <typename T>
 __global__ __launch_bounds__(256) void bn1_gram_finalize_kernel(const double* __restrict__ gram, const float* __restrict__ w1,
                                                                 int E, int Cin, double count, const float* gamma, const float* beta,
@@ -217,7 +236,6 @@ __global__ __launch_bounds__(256) void bn1_gram_finalize_kernel(const double* __
     if (e >= E) return;
     for (int j = lane; j < Cin; j += 64) lw[wv][j] = round_t<T>(w1[(i64)e * Cin + j]);
     __builtin_amdgcn_wave_barrier();
-    const double inv_n = 1.0 / count;
     double quad = 0.0, lin = 0.0;
     for (int i = lane; i < Cin; i += 64) {
         const double* grow = gram + (i64)i * Cin;
@@ -232,24 +250,84 @@ __global__ __launch_bounds__(256) void bn1_gram_finalize_kernel(const double* __
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { quad += __shfl_xor(quad, o); lin += __shfl_xor(lin, o); }
     if (lane != 0) return;
-    const double mean = lin * inv_n;
-    double var = quad * inv_n - mean * mean;
-    if (var < 0) var = 0;
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float scale = gamma[e] * invstd;
-    coef[e] = scale;
-    coef[E + e] = beta[e] - (float)mean * scale;
-    coef[2 * E + e] = (float)mean;
-    coef[3 * E + e] = invstd;
-    if (running_mean) {
-        const double unbiased = count > 1 ? var * count / (count - 1) : var;
-        running_mean[e] = (1.f - momentum) * running_mean[e] + momentum * (float)mean;
-        running_var[e] = (1.f - momentum) * running_var[e] + momentum * (float)unbiased;
-    }
+    bn1_gram_write(e, E, lin, quad, count, gamma, beta, running_mean, running_var, momentum, eps, coef);
 }
-int k_bn1_gram_finalize(const double* gram, const float* w1, int E, int Cin, double count, const float* gamma, const float* beta,
+// The same from the replicas of the streaming Gram kernel (dwn_gram.hip; Cin = 64): each replica holds the 16 x 16 tiles of G with
+// tile row <= tile column and the row 1^T a0.  The workgroup first sums the replicas, in replica order, into ONE full symmetric
+// matrix in LDS (every element read once per workgroup — a wave that walked the replicas itself would read NREP x 32 KB), then a
+// wave per channel forms w^T G w as above; lane i reads gs[j][i] = G[i][j]: consecutive doubles.
+// element k of a replica's packed order (ten 16 x 16 tiles, row-major inside a tile, then the ones row) -> its offset in the replica
+__device__ __forceinline__ int gram64_offset(int k) {
+    if (k >= 10 * 256) return 64 * 64 + (k - 10 * 256);
+    const int t = k >> 8;
+    const int bi = t < 4 ? 0 : t < 7 ? 1 : t < 9 ? 2 : 3;
+    const int bj = t - (bi == 0 ? 0 : bi == 1 ? 3 : bi == 2 ? 5 : 6);
+    return (bi * 16 + ((k >> 4) & 15)) * 64 + bj * 16 + (k & 15);
+}
+template <typename T, int NREP>
+__global__ __launch_bounds__(256) void bn1_gram64_finalize_kernel(const double* __restrict__ gram, const float* __restrict__ w1,
+                                                                  int E, double count, const float* gamma, const float* beta,
+                                                                  float* running_mean, float* running_var, long long* nbt,
+                                                                  float momentum, float eps, float* coef, double* sc_stats) {
+    constexpr int C = 64, TILE = 256, NT = 10;                     // NT upper tiles of 16 x 16, in gram64_kernel's order
+    constexpr i64 REP = (i64)(C + 8) * C;
+    __shared__ double gs[C][C];
+    __shared__ double ssum[C];
+    __shared__ float lw[4][C];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int e = blockIdx.x * 4 + wv;
+    if (blockIdx.x == 0 && tid == 0 && nbt) *nbt += 1;
+    // pairs of neighbouring columns (one 16-byte load each), NIT per thread, all NIT x NREP loads issued before the first add: the
+    // replicas were written by atomics at the memory side, so every one of these is a miss as far as this workgroup's XCD goes
+    constexpr int NP = (NT * TILE + C) / 2, NIT = (NP + 255) / 256;
+    double2 v[NIT][NREP];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        int p = tid + 256 * it;
+        if (p > NP - 1) p = NP - 1;                                // (clamped, not predicated: the store below is)
+        const double2* gp = reinterpret_cast<const double2*>(gram + gram64_offset(2 * p));
+#pragma unroll
+        for (int r = 0; r < NREP; ++r) v[it][r] = gp[r * (REP / 2)];
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int p = tid + 256 * it, k = 2 * p;
+        double2 a = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int r = 0; r < NREP; ++r) { a.x += v[it][r].x; a.y += v[it][r].y; }
+        if (p >= NP) continue;
+        if (k >= NT * TILE) { ssum[k - NT * TILE] = a.x; ssum[k - NT * TILE + 1] = a.y; continue; }
+        const int off = gram64_offset(k), i = off / C, j = off % C;
+        gs[i][j] = a.x; gs[i][j + 1] = a.y;
+        if ((i >> 4) != (j >> 4)) { gs[j][i] = a.x; gs[j + 1][i] = a.y; }
+    }
+    if (e < E) lw[wv][lane] = round_t<T>(w1[(i64)e * C + lane]);
+    __syncthreads();
+    if (sc_stats && blockIdx.x == 0 && tid < C) {
+        sc_stats[tid] = ssum[tid];
+        sc_stats[C + tid] = gs[tid][tid];
+    }
+    if (e >= E) return;
+    double r = 0.0;
+#pragma unroll 8
+    for (int j = 0; j < C; ++j) r += gs[j][lane] * (double)lw[wv][j];
+    double quad = (double)lw[wv][lane] * r, lin = (double)lw[wv][lane] * ssum[lane];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { quad += __shfl_xor(quad, o); lin += __shfl_xor(lin, o); }
+    if (lane != 0) return;
+    bn1_gram_write(e, E, lin, quad, count, gamma, beta, running_mean, running_var, momentum, eps, coef);
+}
+int k_bn1_gram_finalize(const double* gram, int nrep, const float* w1, int E, int Cin, double count, const float* gamma, const float* beta,
                         float* rm, float* rv, long long* nbt, float momentum, float eps, float* coef, double* sc_stats, int dtype,
                         hipStream_t s) {
+    if (nrep > 1) {
+        if (Cin != 64 || dtype != DWN_BF16 || nrep != DWN_GRAM_NREP)
+            return dwn_set_error(-2, "bn1_gram_finalize: replicas are the bf16, 64-channel Gram kernel's (DWN_GRAM_NREP of them)");
+        hipLaunchKernelGGL((bn1_gram64_finalize_kernel<bf16_t, DWN_GRAM_NREP>), dim3((E + 3) / 4), dim3(256), 0, s, gram, w1, E, count, gamma, beta,
+                           rm, rv, nbt, momentum, eps, coef, sc_stats);
+        DWN_CHECK_LAUNCH();
+        return 0;
+    }
     if (Cin > 512 || Cin % 4) return dwn_set_error(-2, "bn1_gram_finalize: Cin must be a multiple of 4, at most 512");
     if (dtype == DWN_BF16)
         hipLaunchKernelGGL(bn1_gram_finalize_kernel<bf16_t>, dim3((E + 3) / 4), dim3(256), 0, s, gram, w1, E, Cin, count, gamma, beta,
@@ -1565,11 +1643,12 @@ __global__ __launch_bounds__(256) void se_mlp_bwd_fold_kernel(const float* dg, c
 }
 
 // parameter grads of the SE MLP.  grid.x = ceil(C/256), grid.y = R: thread (c, r) reduces over the batch.
-__global__ __launch_bounds__(256) void se_mlp_wgrad_kernel(const float* dgp, const float* dhp, const float* pmean,
-                                                           const float* hid_pre, int B, int C, int R, float* dwr,
-                                                           float* dbr, float* dwe, float* dbe) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    const int r = blockIdx.y;
+// (bx, r: the workgroup's place in that grid — the stand-alone kernel passes blockIdx, the block backward's parameter-gradient
+// tail, block_param_tail_kernel below the conv_pw fold, its own job index)
+__device__ __forceinline__ void se_mlp_wgrad_body(int bx, int r, const float* dgp, const float* dhp, const float* pmean,
+                                                  const float* hid_pre, int B, int C, int R, float* dwr, float* dbr, float* dwe,
+                                                  float* dbe) {
+    const int c = bx * 256 + threadIdx.x;
     if (c < C) {
         float a = 0.f, a2 = 0.f, sb = 0.f;
 #pragma unroll 8
@@ -1583,11 +1662,16 @@ __global__ __launch_bounds__(256) void se_mlp_wgrad_kernel(const float* dgp, con
         dwr[(i64)r * C + c] = a2;
         if (r == 0) dbe[c] = sb;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (bx == 0 && threadIdx.x == 0) {
         float sb = 0.f;
         for (int b = 0; b < B; ++b) sb += dhp[(i64)b * R + r];
         dbr[r] = sb;
     }
+}
+__global__ __launch_bounds__(256) void se_mlp_wgrad_kernel(const float* dgp, const float* dhp, const float* pmean,
+                                                           const float* hid_pre, int B, int C, int R, float* dwr,
+                                                           float* dbr, float* dwe, float* dbe) {
+    se_mlp_wgrad_body((int)blockIdx.x, (int)blockIdx.y, dgp, dhp, pmean, hid_pre, B, C, R, dwr, dbr, dwe, dbe);
 }
 
 // w2 / wg / N2 (optional): fold the gate into conv_pwl's weight in the same launch (rows kernel only; returns 1 in *folded)
@@ -1618,7 +1702,7 @@ int k_se_mlp_fwd(const long long* pooled_sum, float inv_s, const float* wr, cons
 }
 int k_se_mlp_bwd(const float* dg, const float* gate, const float* hid_pre, const float* pmean, const float* wr,
                  const float* we, int B, int C, int R, float inv_s, float* dgp, float* dhp, float* dps, float* dwr,
-                 float* dbr, float* dwe, float* dbe, hipStream_t s) {
+                 float* dbr, float* dwe, float* dbe, hipStream_t s, bool wgrad) {
     if ((R & 1) == 0 && R <= SE_RT && !((size_t)we & 15)) {
 #define SE_BWD_FOLD(RP_) do { \
         if ((R & 3) == 0) hipLaunchKernelGGL((se_mlp_bwd_fold_kernel<RP_, 4>), dim3(B, 8), dim3(256), 0, s, dg, gate, hid_pre, wr, we, C, R, inv_s, dgp, dhp, dps); \
@@ -1632,6 +1716,7 @@ int k_se_mlp_bwd(const float* dg, const float* gate, const float* hid_pre, const
                            C, R, inv_s, dgp, dhp, dps);
     }
     DWN_CHECK_LAUNCH();
+    if (!wgrad) return 0;           // the caller launches the parameter gradients itself (k_block_param_tail), from dgp / dhp
     hipLaunchKernelGGL(se_mlp_wgrad_kernel, dim3((C + 255) / 256, R), dim3(256), 0, s, dgp, dhp, pmean, hid_pre, B, C, R,
                        dwr, dbr, dwe, dbe);
     DWN_CHECK_LAUNCH();
@@ -2899,11 +2984,11 @@ __global__ __launch_bounds__(256) void pw_wgrad_fold_kernel(const float* __restr
 // them in flight — the thread-per-element kernel above re-reads W1's row and Ga's column per element and ran at the L1 rate
 // (30 us at E = 1792, C = 256); 16 rows per thread left 7 workgroups at C = 64 walking 64 dependent loads (20 us)
 template <typename T, int CC>
-__global__ __launch_bounds__(256) void pw_wgrad_fold_tile_kernel(const float* __restrict__ tacc, const float* __restrict__ abc,
-                                                                 const float* __restrict__ w1, int E, float* __restrict__ dw) {
+__device__ __forceinline__ void pw_wgrad_fold_tile_body(int bx, const float* __restrict__ tacc, const float* __restrict__ abc,
+                                                        const float* __restrict__ w1, int E, float* __restrict__ dw) {
     constexpr int G = 256 / CC, ROWS = 4 * G;
     __shared__ __attribute__((aligned(16))) float sw[CC][ROWS];          // sw[c'][row] = round(W1[e0 + row][c'])
-    const int tid = threadIdx.x, e0 = blockIdx.x * ROWS;
+    const int tid = threadIdx.x, e0 = bx * ROWS;
     for (int i = tid; i < ROWS * CC; i += 256) {
         const int row = i / CC, cp = i % CC;
         sw[cp][row] = e0 + row < E ? round_t<T>(w1[(i64)(e0 + row) * CC + cp]) : 0.f;
@@ -2933,6 +3018,11 @@ __global__ __launch_bounds__(256) void pw_wgrad_fold_tile_kernel(const float* __
         if (e < E) dw[(i64)e * CC + c] = fmaf(abc[e], tacc[(i64)e * CC + c], fmaf(abc[E + e], acc[r], abc[2 * E + e] * sc));
     }
 }
+template <typename T, int CC>
+__global__ __launch_bounds__(256) void pw_wgrad_fold_tile_kernel(const float* __restrict__ tacc, const float* __restrict__ abc,
+                                                                 const float* __restrict__ w1, int E, float* __restrict__ dw) {
+    pw_wgrad_fold_tile_body<T, CC>((int)blockIdx.x, tacc, abc, w1, E, dw);
+}
 int k_pw_wgrad_fold(const float* tacc, const float* abc, const float* w1, int E, int C, float* dw, int dtype, hipStream_t s) {
 #define FOLD_TILE(CC_) do { \
         dim3 grid((unsigned)((E + 4 * (256 / CC_) - 1) / (4 * (256 / CC_)))); \
@@ -2951,4 +3041,46 @@ int k_pw_wgrad_fold(const float* tacc, const float* abc, const float* w1, int E,
         hipLaunchKernelGGL((pw_wgrad_fold_kernel<float>), grid, dim3(256), 0, s, tacc, abc, w1, E, C, dw));
     DWN_CHECK_LAUNCH();
     return 0;
+}
+
+// The block backward's parameter-gradient tail: the SE MLP's parameter gradients and conv_pw's weight-gradient fold in ONE launch,
+// the last of dwn_block_backward.  Nothing in the block reads what either writes (only the optimizer does), so neither needs
+// its place in the stream order: as two launches they cost two launch gaps per block, the first of them between the SE fold
+// kernel and the dh3 GEMM.  Job split on blockIdx.x in the way of prep_kernel: workgroups [0, nse) are se_mlp_wgrad_kernel's grid
+// (x = job % gxse, r = job / gxse), the rest pw_wgrad_fold_tile_kernel<T, CC>'s — the same device functions, so the same results
+// bit for bit.
+template <typename T, int CC>
+__global__ __launch_bounds__(256) void block_param_tail_kernel(const float* dgp, const float* dhp, const float* pmean,
+                                                               const float* hid_pre, int B, int Cse, int R, float* dwr, float* dbr,
+                                                               float* dwe, float* dbe, int gxse, int nse,
+                                                               const float* __restrict__ tacc, const float* __restrict__ abc,
+                                                               const float* __restrict__ w1, int E, float* __restrict__ dw) {
+    const int job = (int)blockIdx.x;
+    if (job < nse) {
+        se_mlp_wgrad_body(job % gxse, job / gxse, dgp, dhp, pmean, hid_pre, B, Cse, R, dwr, dbr, dwe, dbe);
+        return;
+    }
+    pw_wgrad_fold_tile_body<T, CC>(job - nse, tacc, abc, w1, E, dw);
+}
+// (a width the tile kernel is not built for: the two stand-alone launches, in this place)
+int k_block_param_tail(const float* dgp, const float* dhp, const float* pmean, const float* hid_pre, int B, int Cse, int R,
+                       float* dwr, float* dbr, float* dwe, float* dbe, const float* tacc, const float* abc, const float* w1, int E,
+                       int C, float* dw, int dtype, hipStream_t s) {
+    const int gxse = (Cse + 255) / 256, nse = gxse * R;
+#define PARAM_TAIL(CC_) do { \
+        dim3 grid((unsigned)(nse + (E + 4 * (256 / CC_) - 1) / (4 * (256 / CC_)))); \
+        DISPATCH_T(dtype, \
+            hipLaunchKernelGGL((block_param_tail_kernel<bf16_t, CC_>), grid, dim3(256), 0, s, dgp, dhp, pmean, hid_pre, B, Cse, R, \
+                               dwr, dbr, dwe, dbe, gxse, nse, tacc, abc, w1, E, dw), \
+            hipLaunchKernelGGL((block_param_tail_kernel<float, CC_>), grid, dim3(256), 0, s, dgp, dhp, pmean, hid_pre, B, Cse, R, \
+                               dwr, dbr, dwe, dbe, gxse, nse, tacc, abc, w1, E, dw)); \
+        DWN_CHECK_LAUNCH(); \
+        return 0; } while (0)
+    if (C == 64) PARAM_TAIL(64);
+    if (C == 128) PARAM_TAIL(128);
+    if (C == 256) PARAM_TAIL(256);
+#undef PARAM_TAIL
+    hipLaunchKernelGGL(se_mlp_wgrad_kernel, dim3(gxse, R), dim3(256), 0, s, dgp, dhp, pmean, hid_pre, B, Cse, R, dwr, dbr, dwe, dbe);
+    DWN_CHECK_LAUNCH();
+    return k_pw_wgrad_fold(tacc, abc, w1, E, C, dw, dtype, s);
 }

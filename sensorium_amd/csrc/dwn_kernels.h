@@ -22,9 +22,16 @@ int k_bn_bwd_finalize(BnBwdJob j0, BnBwdJob j1, hipStream_t s);
 int k_bn_finalize_eval(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
                        float* coef, int C, hipStream_t s);
 // BatchNorm-1 statistics from the Gram matrix of the block input (y1 never materialised; dwn_elementwise.hip)
-int k_bn1_gram_finalize(const double* gram, const float* w1, int E, int Cin, double count, const float* gamma, const float* beta,
+// nrep = 1: one full matrix (the gemm_tn route); nrep = gram_nrep() > 1: the replicas of the streaming kernel (dwn_gram.hip: Cin = 64,
+// upper tiles), summed in replica order
+int k_bn1_gram_finalize(const double* gram, int nrep, const float* w1, int E, int Cin, double count, const float* gamma, const float* beta,
                         float* rm, float* rv, long long* nbt, float momentum, float eps, float* coef, double* sc_stats, int dtype,
                         hipStream_t s);
+// the streaming Gram kernel (dwn_gram.hip): replicas per (dtype, Cin) — 1 where it is not built —, and its launcher (*done = false:
+// not built for this shape, nothing launched, the caller takes the gemm_tn route)
+#define DWN_GRAM_NREP 8
+int gram_nrep(int dtype, int Cin);
+int k_gram(const void* a0, i64 ld, i64 M, int Cin, double* gram, int dtype, bool* done, hipStream_t s);
 int k_ew_apply(const LoadDesc& d, int kind, void* out, i64 ldo, i64 rows, int C, int dtype, hipStream_t s);
 // stem through the input moments (no y0 round trip; dwn_elementwise.hip)
 int k_stem_xmom(const float* x, int B, int Cin, i64 S, double* mom, hipStream_t s);
@@ -65,7 +72,7 @@ int k_se_mlp_fwd(const long long* pooled_sum, float inv_s, const float* wr, cons
                  int dtype, int* folded, hipStream_t s);
 int k_se_mlp_bwd(const float* dg, const float* gate, const float* hid_pre, const float* pmean, const float* wr,
                  const float* we, int B, int C, int R, float inv_s, float* dgp, float* dhp, float* dps, float* dwr,
-                 float* dbr, float* dwe, float* dbe, hipStream_t s);
+                 float* dbr, float* dwe, float* dbe, hipStream_t s, bool wgrad = true);
 int k_bn3_bwd_reduce(const LoadDesc& d, const float* coef3, i64 rows, int C, double* stats, void* dh_out, int dtype, hipStream_t s);
 int k_pool_fwd(const void* x, void* out, i64 BT, int HW, int C, int dtype, hipStream_t s);
 int k_pool_bwd(const void* dpool, void* dx, i64 BT, int HW, int C, int dtype, hipStream_t s);
@@ -170,6 +177,10 @@ int k_pw_bwd_prep(const float* w1, const float* abc, int E, int C, void* bp, flo
 // Ga = a0^T a0, s = 1^T a0;  dw[e][c] = A1[e] T1[e][c] + A2[e] sum_c' W1[e][c'] Ga[c'][c] + A3[e] s[c]   (W1 as rounded to dtype)
 size_t pw_wgrad_tacc_floats(int E, int C);
 int k_pw_wgrad_fold(const float* tacc, const float* abc, const float* w1, int E, int C, float* dw, int dtype, hipStream_t s);
+// the block backward's parameter-gradient tail: k_se_mlp_bwd's wgrad kernel (wgrad = false there) and k_pw_wgrad_fold in one launch
+int k_block_param_tail(const float* dgp, const float* dhp, const float* pmean, const float* hid_pre, int B, int Cse, int R,
+                       float* dwr, float* dbr, float* dwe, float* dbe, const float* tacc, const float* abc, const float* w1, int E,
+                       int C, float* dw, int dtype, hipStream_t s);
 
 // ---- fused per-call preparation (k_prep): zero ranges, constant fills and weight packs in one launch
 enum { PREP_ZERO = 0, PREP_FILL = 1, PREP_PACKW = 2, PREP_PACKDW = 3, PREP_BNEVAL = 4 };
