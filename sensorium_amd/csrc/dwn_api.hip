@@ -11,13 +11,6 @@ static thread_local char g_err[512] = "";
 #define DWN_EVAL_CHAIN 1      // eval forward: the chained stencil's rebuilt-input form where it is built (0: dwn_dwrc.hip everywhere; A/B builds)
 #endif
 
-// y1-recomputing spatial forward (dwn_dwrc.hip): used by the eval-mode block forward, where neither the BatchNorm-1
-// statistics nor a saved y1 are needed, so conv_pw never runs as a pass of its own
-extern "C" size_t dwn_dw_spatial_rc_blob_bytes(int E, int Cin);
-extern "C" int dwn_dw_spatial_rc_supported(int dtype, int Cin, int E, int ks, int stride, int Hin, int Win);
-extern "C" int dwn_dw_spatial_rc_prep(const float* w_pw, const float* w_dws, const float* bn1_coef, int E, int Cin, void* blob,
-                                      int device, void* stream);
-extern "C" int dwn_dw_spatial_fwd_rc(const dwn_dw_spatial_rc_fwd_args* a, int device, void* stream);
 bool dw_spatial_bwd_rc_supported(const DwSpatialBwd& a, int dtype);          // dwn_dwbwd.hip
 bool dw_spatial_fwd_rc_walk_supported(const DwSpatialFwd& a, int dtype);     // dwn_dwfwd.hip
 
@@ -176,24 +169,38 @@ struct BlockWs {
     void* wgated;                                          // [B][Cout][Cmid] W2 . diag(gate_b) (forward only)
     void* rcblob;                                          // forward: slice images of the y1-recomputing stencil
     double* gram;                                          // y1-free training forward: gram_nrep() x [(Cin + 8)][Cin] raw products a0^T a0, 1^T a0 (fp64 atomics)
-    float* pb;                                             // [B][Cout][Cmid] per-sample dy4^T z3 (backward, see pwl_bwd_per_sample)
+    float* pb;                                             // [B][Cout][Cmid] per-sample dy4^T z3 (backward, BlockPlan::pwl_per_sample)
     char* zero_beg; char* zero_end;
     size_t bytes;
 };
-// conv_pwl forward with the SE gate folded into per-sample weights (plain A loader): needs whole tiles per sample and
-// the k-loop GEMM variant
-// ... and enough rows per sample to pay for writing B weight copies: with 18432 rows (blocks 0-3) the copies are 1.8 MB and the
-// plain-loader GEMM on its LDS-DMA ring wins; at 4608 / 1280 rows (blocks 4-8) the copies are 7-29 MB per block — written, then
-// re-read at 1.35-1.53x the activations' bytes — and the gate in the A loader is faster for the step although the GEMM itself is
-// slower (round 5, same box: pwl_fwd 1.085 -> 1.289 ms, step 24.27 -> 24.12 ms)
+// ---------------------------------------------------------------- block plan
+// Everything the block entries decide from the arguments alone, decided once: carve_block, dwn_block_forward, dwn_block_backward
+// and dwn_block_forward_writes read a BlockPlan and ask no route predicate themselves.
+enum PwRoute {                   // how conv_pw and the spatial stencil run (precedence: plan_block)
+    PW_MATERIALISED,             // gemm_nn writes y1, then the stencil on y1
+    PW_Y1_FREE,                  // training / frozen: the chained row-walk stencil rebuilds y1 from a0; a Gram pass only with batch statistics
+    PW_EVAL_CHAIN,               // eval: the same stencil, BatchNorm-1 known
+    PW_EVAL_RC,                  // eval: the tile-resident y1-recomputing stencil (dwn_dwrc.hip)
+};
+struct BlockPlan {
+    i64 Min, Mout; int S_out;    // rows of the block's input / output; output rows per sample
+    // tr: the training kernels and their saved intermediates (DWN_BN_TRAIN and DWN_BN_FROZEN); bs: batch statistics (DWN_BN_TRAIN).
+    // Frozen: every BatchNorm's coefficients are known before the first launch (prep, as eval), so the Gram pass, the shortcut's
+    // statistics pass and all finalisers go; the statistics epilogues of the GEMMs / stencils stay (same kernels, same arguments
+    // as training: their sums land in the zeroed arena and nobody reads them).  Backward: BatchNorm triples (scale, 0, 0)
+    bool tr, bs, frozen;
+    bool identity_sc;            // the shortcut's nearest map is the identity
+    PwRoute pw;
+    bool rc_blob;                // the forward workspace holds dwn_dwrc.hip's slice images (eval, wherever that stencil is built)
+    bool pwl_gated;              // conv_pwl forward on per-sample gated weights
+    bool pwl_per_sample;         // conv_pwl backward through per-sample products (pwl_bwd_per_sample)
+    bool dx_folded, sc_gathered; // backward: the shortcut's gradient folded into conv_pw's data gradient; ... through its nearest map
+    bool eval_z3;                // eval: z3 and the SE pooling sums come straight from the temporal pass, y3 is never stored
+    int writes;                  // dwn_block_forward_writes: bit 0 = y1, bit 1 = y3
+};
 #ifndef PWL_GATED_MIN_ROWS
 #define PWL_GATED_MIN_ROWS 8192
 #endif
-static bool pwl_gated_weights(const dwn_block_args& a) {
-    const int bk = a.dtype == DWN_BF16 ? 64 : 32;
-    // (bf16 only: fp32 keeps the per-sample weights everywhere — its eval-mode split products were validated in that form)
-    return ((a.T * a.Hout * a.Wout) % 128) == 0 && a.Cmid > bk && (a.dtype != DWN_BF16 || a.T * a.Hout * a.Wout >= PWL_GATED_MIN_ROWS);
-}
 // conv_pwl backward through per-sample products (k_pwl_bwd_reduce) + the recompute-du GEMM epilogue (EPI_DH3): saves
 // three passes over a [Mout][Cmid] tensor at the price of zeroing / accumulating / reading B [Cout][Cmid] fp32 matrices,
 // so it is used when those are small next to one such pass.  dwn_block_args.pwl_bwd = 1 | 2 forces a path (the parity
@@ -208,33 +215,64 @@ static bool pwl_bwd_per_sample(const dwn_block_args& a) {
     const double pass = (double)a.B * a.T * a.Hout * a.Wout * a.Cmid * tsize(a.dtype);
     return pb <= pass;
 }
-// Training WITHOUT a materialised y1 (round 5; dwn_block_args.y1_mode).  y1 = a0 . W1^T is the widest tensor of a block and a
-// Cin-deep product of one seven times narrower: the forward stencil rebuilds its rows on the matrix cores (dwn_dwfwd.hip, CIN > 0) with
-// BatchNorm-1's batch statistics taken from the Gram matrix of a0 (k_bn1_gram_finalize), the backward stencil rebuilds the rows it
-// needs the same way (dwn_dwbwd.hip, CIN > 0), and conv_pw's backward has not read y1 since round 4 — so y1 is neither written nor
-// read: three E-wide passes over M_in rows less per block.  Both directions decide with this one predicate.
-static bool block_y1_free(const dwn_block_args& a) {
-    if (!a.training || a.dtype != DWN_BF16 || a.y1_mode == 1) return false;
-    DwSpatialFwd f; memset(&f, 0, sizeof(f));
-    f.planes = a.B * a.T; f.Hin = a.Hin; f.Win = a.Win; f.Hout = a.Hout; f.Wout = a.Wout; f.C = a.Cmid; f.stride = a.stride; f.ks = a.ks;
-    f.in.ld = a.Cmid; f.a0_ld = a.Cin; f.Cin = a.Cin;
-    if (!dw_spatial_fwd_rc_walk_supported(f, a.dtype)) return false;
-    DwSpatialBwd d; memset(&d, 0, sizeof(d));
+// The geometry of the block's spatial stencil (D: DwSpatialFwd / DwSpatialBwd) and, rebuilt: the rebuilt-input form's a0_ld / Cin.
+// The support probes of plan_block and the launches start from the same descriptor; a launch adds its loaders (every row length
+// is Cmid), pointers and statistics.
+template <class D> static D dws_desc(const dwn_block_args& a, bool rebuilt) {
+    D d; memset(&d, 0, sizeof(d));
     d.planes = a.B * a.T; d.Hin = a.Hin; d.Win = a.Win; d.Hout = a.Hout; d.Wout = a.Wout; d.C = a.Cmid; d.stride = a.stride; d.ks = a.ks;
-    d.dy.ld = a.Cmid; d.y1.ld = a.Cmid; d.a0_ld = a.Cin; d.Cin = a.Cin;
-    if (!dw_spatial_bwd_rc_supported(d, a.dtype)) return false;
+    if (rebuilt) { d.a0_ld = a.Cin; d.Cin = a.Cin; }
+    return d;
+}
+// Pure: no device call, no state; the same arguments give the same plan in every entry and on a host without a device.
+static BlockPlan plan_block(const dwn_block_args& a) {
+    BlockPlan p; memset(&p, 0, sizeof(p));
+    p.Min = (i64)a.B * a.T * a.Hin * a.Win; p.Mout = (i64)a.B * a.T * a.Hout * a.Wout; p.S_out = a.T * a.Hout * a.Wout;
+    p.tr = a.training != DWN_BN_EVAL; p.bs = a.training == DWN_BN_TRAIN; p.frozen = a.training == DWN_BN_FROZEN;
+    p.identity_sc = a.stride == 1 && a.Hin == a.Hout && a.Win == a.Wout;
+    // the one probe of each direction: is the row-walk stencil's rebuilt-input form built for this geometry?
+    DwSpatialFwd f = dws_desc<DwSpatialFwd>(a, true); f.in.ld = a.Cmid;
+    DwSpatialBwd b = dws_desc<DwSpatialBwd>(a, true); b.dy.ld = b.y1.ld = a.Cmid;
+    const bool walk = a.dtype == DWN_BF16 && dw_spatial_fwd_rc_walk_supported(f, a.dtype);
+    // Training WITHOUT a materialised y1 (round 5; dwn_block_args.y1_mode).  y1 = a0 . W1^T is the widest tensor of a block and a
+    // Cin-deep product of one seven times narrower: the forward stencil rebuilds its rows on the matrix cores (dwn_dwfwd.hip, CIN > 0) with
+    // BatchNorm-1's batch statistics taken from the Gram matrix of a0 (k_bn1_gram_finalize), the backward stencil rebuilds the rows it
+    // needs the same way (dwn_dwbwd.hip, CIN > 0), and conv_pw's backward has not read y1 since round 4 — so y1 is neither written nor
+    // read: three E-wide passes over M_in rows less per block.
     // y1_mode 0: where it is also the faster path — 64 input channels (blocks 0-3: -0.4 ms per step); with 128 (blocks 4-6: four k-steps
     // per MFMA tile, 256 B of a0 per pixel against 128 B of a y1 slice) the rebuilding stencils lose more than conv_pw costs
     // (stand-alone 508 vs 295 us forward, 614 vs 549 us backward on block 4's shape); y1_mode 2 takes every block that is built
-    return a.y1_mode == 2 || a.Cin == 64;
-}
-// eval-mode forward without conv_pw as its own pass (BatchNorm-1 is known: the tile-resident stencil of dwn_dwrc.hip)
-static bool block_fwd_rc(const dwn_block_args& a) {
-    return !a.training && dwn_dw_spatial_rc_supported(a.dtype, a.Cin, a.Cmid, a.ks, a.stride, a.Hin, a.Win) != 0;
+    const bool y1_free = p.tr && walk && a.y1_mode != 1 && dw_spatial_bwd_rc_supported(b, a.dtype) && (a.y1_mode == 2 || a.Cin == 64);
+    // eval-mode forward without conv_pw as its own pass (BatchNorm-1 is known): the tile-resident stencil of dwn_dwrc.hip
+    p.rc_blob = !p.tr && dwn_dw_spatial_rc_supported(a.dtype, a.Cin, a.Cmid, a.ks, a.stride, a.Hin, a.Win) != 0;
+    // eval, 64 or 128 input channels, row-walk plane widths: the chained stencil's rebuilt-input form is also the faster way to skip
+    // conv_pw (623 vs 768 us on block 0's shape, 276 vs 308 us on blocks 1-3'; faster than the tile-resident kernel at 128 channels
+    // too: profiles/r5_predict_bf16_kernel_stats.csv); the tile-resident kernel keeps the other geometries — and its slice of the
+    // workspace (rc_blob) also where the chain wins and nothing reads it: a known leftover of the layout
+    p.pw = DWN_EVAL_CHAIN && !p.tr && walk ? PW_EVAL_CHAIN : y1_free ? PW_Y1_FREE : p.rc_blob ? PW_EVAL_RC : PW_MATERIALISED;
+    // conv_pwl forward with the SE gate folded into per-sample weights (plain A loader): needs whole tiles per sample and
+    // the k-loop GEMM variant
+    // ... and enough rows per sample to pay for writing B weight copies: with 18432 rows (blocks 0-3) the copies are 1.8 MB and the
+    // plain-loader GEMM on its LDS-DMA ring wins; at 4608 / 1280 rows (blocks 4-8) the copies are 7-29 MB per block — written, then
+    // re-read at 1.35-1.53x the activations' bytes — and the gate in the A loader is faster for the step although the GEMM itself is
+    // slower (round 5, same box: pwl_fwd 1.085 -> 1.289 ms, step 24.27 -> 24.12 ms)
+    // (bf16 only: fp32 keeps the per-sample weights everywhere — its eval-mode split products were validated in that form)
+    p.pwl_gated = (p.S_out % 128) == 0 && a.Cmid > (a.dtype == DWN_BF16 ? 64 : 32) && (a.dtype != DWN_BF16 || p.S_out >= PWL_GATED_MIN_ROWS);
+    p.pwl_per_sample = pwl_bwd_per_sample(a);
+    // backward, conv_pw's data gradient IS dx: output channels = input channels tiled once or twice, the one-pass kernel (asked
+    // first: it leaves no Cin to divide by but the one it is built for), and the shortcut's map the identity or, on a strided block,
+    // gathered through hinv / winv
+    p.dx_folded = pw_bwd_fused_supported(a.dtype, p.Min, a.Cmid, a.Cin) && a.Cout % a.Cin == 0 && a.Cout / a.Cin <= 2 &&
+                  (p.identity_sc || (a.hinv && a.winv && a.Hin + a.Win <= 512));
+    p.sc_gathered = p.dx_folded && !p.identity_sc;
+    p.eval_z3 = !p.tr;
+    // training writes y3 and, unless the stencils rebuild it, y1; eval never writes y3 and writes y1 on the materialised route only
+    p.writes = p.tr ? (p.pw == PW_Y1_FREE ? 2 : 3) : (p.pw == PW_MATERIALISED ? 1 : 0);
+    return p;
 }
 // floats of the conv_pw data-gradient folding scratch: G accumulator [Cin][Cin] and r3 [Cin]
 static size_t pw_fold_floats(int Cin) { return (size_t)Cin * Cin + Cin; }
-BlockWs carve_block(const dwn_block_args& a, int backward, void* base, size_t cap) {
+BlockWs carve_block(const dwn_block_args& a, const BlockPlan& p, int backward, void* base, size_t cap) {
     BlockWs w; memset(&w, 0, sizeof(w));
     Carver c(base, cap);
     const size_t ts = tsize(a.dtype);
@@ -242,8 +280,8 @@ BlockWs carve_block(const dwn_block_args& a, int backward, void* base, size_t ca
     w.wpwl = c.take<char>((size_t)a.Cout * a.Cmid * ts);
     w.wdws = c.take<float>((size_t)a.ks * a.ks * a.Cmid);
     w.wdwt = c.take<float>((size_t)a.kt * a.Cmid);
-    if (!backward && pwl_gated_weights(a)) w.wgated = c.take<char>((size_t)a.B * a.Cout * a.Cmid * ts);
-    if (!backward && block_fwd_rc(a)) w.rcblob = c.take<char>(dwn_dw_spatial_rc_blob_bytes(a.Cmid, a.Cin));      // eval only
+    if (!backward && p.pwl_gated) w.wgated = c.take<char>((size_t)a.B * a.Cout * a.Cmid * ts);
+    if (!backward && p.rc_blob) w.rcblob = c.take<char>(dwn_dw_spatial_rc_blob_bytes(a.Cmid, a.Cin));      // eval only
     c.take<char>(0);
     size_t z0 = (c.off + 255) & ~(size_t)255;
     w.st1 = c.take<double>(nstat(a.Cmid));
@@ -252,7 +290,7 @@ BlockWs carve_block(const dwn_block_args& a, int backward, void* base, size_t ca
     w.st4 = c.take<double>(nstat(a.Cout));
     w.stsc = c.take<double>(nstat(backward ? a.Cout : a.Cin));
     w.pooled = c.take<long long>((size_t)a.B * a.Cmid);
-    if (!backward && block_y1_free(a)) w.gram = c.take<double>((size_t)gram_nrep(a.dtype, a.Cin) * (a.Cin + 8) * a.Cin);
+    if (!backward && p.pw == PW_Y1_FREE) w.gram = c.take<double>((size_t)gram_nrep(a.dtype, a.Cin) * (a.Cin + 8) * a.Cin);
     size_t z1 = c.off;
     if (backward) {
         w.abc1 = c.take<float>(3 * (size_t)a.Cmid);
@@ -268,7 +306,7 @@ BlockWs carve_block(const dwn_block_args& a, int backward, void* base, size_t ca
         w.gacc = c.take<float>(pw_fold_floats(a.Cin));                  // one zeroed range: G accumulator, r3
         w.r3 = w.gacc + (size_t)a.Cin * a.Cin;
         w.tacc = c.take<float>(pw_wgrad_tacc_floats(a.Cmid, a.Cin));
-        if (pwl_bwd_per_sample(a)) w.pb = c.take<float>((size_t)a.B * a.Cout * a.Cmid);
+        if (p.pwl_per_sample) w.pb = c.take<float>((size_t)a.B * a.Cout * a.Cmid);
     }
     w.bytes = c.off + 256;
     if (base) { w.zero_beg = (char*)base + z0; w.zero_end = (char*)base + z1; }
@@ -530,7 +568,7 @@ int dwn_stem_input_grad(const dwn_stem_input_grad_args* a, int device, void* str
 
 // ------------------------------------------------------------------------------------------------ block
 size_t dwn_block_workspace_bytes(const dwn_block_args* a, int backward) {
-    return carve_block(*a, backward, nullptr, 0).bytes;
+    return carve_block(*a, plan_block(*a), backward, nullptr, 0).bytes;
 }
 
 int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
@@ -538,32 +576,26 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
     const dwn_block_args& a = *ap;
     hipStream_t s = (hipStream_t)stream;
     TRY(check_block(a));
-    BlockWs w = carve_block(a, 0, a.ws, a.ws_bytes);
+    const BlockPlan p = plan_block(a);
+    BlockWs w = carve_block(a, p, 0, a.ws, a.ws_bytes);
     if (w.bytes > a.ws_bytes) return dwn_set_error(-6, "block_forward: workspace too small");
-    // tr: the training kernels and their saved intermediates (DWN_BN_TRAIN and DWN_BN_FROZEN); bs: batch statistics (DWN_BN_TRAIN).
-    // Frozen: every BatchNorm's coefficients are known before the first launch (prep, as eval), so the Gram pass, the shortcut's
-    // statistics pass and all finalisers go; the statistics epilogues of the GEMMs / stencils stay (same kernels, same arguments
-    // as training: their sums land in the zeroed arena and nobody reads them)
-    const int dt = a.dtype, tr = a.training != DWN_BN_EVAL;
-    const bool bs = a.training == DWN_BN_TRAIN;
-    const i64 Min = (i64)a.B * a.T * a.Hin * a.Win, Mout = (i64)a.B * a.T * a.Hout * a.Wout;
-    const int S_out = a.T * a.Hout * a.Wout;
-    {   // one launch: zero the statistics arena, pack the four weights
+    const int dt = a.dtype, S_out = p.S_out;
+    const i64 Min = p.Min, Mout = p.Mout;
+    {   // ---- prep, one launch: zero the statistics arena, pack the four weights
         PrepArgs pa;
         bool ok = pa.zero(w.zero_beg, ((size_t)(w.zero_end - w.zero_beg) + 15) & ~(size_t)15);
         ok = ok && pa.packw(a.w_pw, w.wpw, 1, a.Cmid, a.Cin, 0, a.Cmid, a.Cin);
         ok = ok && pa.packw(a.w_pwl, w.wpwl, 1, a.Cout, a.Cmid, 0, a.Cout, a.Cmid);
         ok = ok && pa.packdw(a.w_dws, w.wdws, a.Cmid, a.ks * a.ks);
         ok = ok && pa.packdw(a.w_dwt, w.wdwt, a.Cmid, a.kt);
-        if (!bs) {      // eval / frozen: the five BatchNorm coefficient sets come from running statistics — same launch
+        if (!p.bs) {    // eval / frozen: the five BatchNorm coefficient sets come from running statistics — same launch
             ok = ok && pa.bneval(a.bn1, a.Cmid, a.eps) && pa.bneval(a.bn2, a.Cmid, a.eps) && pa.bneval(a.bn3, a.Cmid, a.eps);
             ok = ok && pa.bneval(a.bn4, a.Cout, a.eps) && pa.bneval(a.bnsc, a.Cout, a.eps);
         }
         if (!ok) return dwn_set_error(-2, "block_forward: workspace arena must be 16-byte aligned");
         TRY(k_prep(pa, dt, s));
     }
-
-    // PositionalEncoding3d (dwiseneuro.py:184-192): normally already folded into x by the producer (stem /
+    // ---- PositionalEncoding3d (dwiseneuro.py:184-192): normally already folded into x by the producer (stem /
     // previous block's residual kernel); stand-alone callers get it materialised here
     const void* a0 = a.x;
     if (!a.x_has_pe) {
@@ -571,119 +603,103 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
         TRY(k_ew_apply(ld_pe(a.x, a.Cin, a.pe_t, a.pe_h, a.pe_w, a.T, a.Hin, a.Win), LD_PE, a.a0, a.Cin, Min, a.Cin, dt, s));
         a0 = a.a0;
     }
-    // conv_pw (dwiseneuro.py:90-93): y1 = a0 @ W1^T, Σ/Σ² for bn1
     LoadDesc xin = ld_plain(a0, a.Cin);
-    const bool identity_sc = a.stride == 1 && a.Hin == a.Hout && a.Win == a.Wout;
-    const bool y1_free = tr && block_y1_free(a);
-    // eval, 64 or 128 input channels, row-walk plane widths: the chained stencil's rebuilt-input form is also the faster way to skip
-    // conv_pw (623 vs 768 us on block 0's shape, 276 vs 308 us on blocks 1-3'; faster than the tile-resident kernel at 128 channels
-    // too: profiles/r5_predict_bf16_kernel_stats.csv); the tile-resident kernel of dwn_dwrc.hip keeps the other geometries
-    bool eval_chain = false;
-    if (DWN_EVAL_CHAIN && !tr && dt == DWN_BF16) {
-        DwSpatialFwd f; memset(&f, 0, sizeof(f));
-        f.planes = a.B * a.T; f.Hin = a.Hin; f.Win = a.Win; f.Hout = a.Hout; f.Wout = a.Wout; f.C = a.Cmid; f.stride = a.stride; f.ks = a.ks;
-        f.in.ld = a.Cmid; f.a0_ld = a.Cin; f.Cin = a.Cin;
-        eval_chain = dw_spatial_fwd_rc_walk_supported(f, dt);
-    }
-    if (eval_chain) {
-        DwSpatialFwd d; memset(&d, 0, sizeof(d));
-        d.in = ld_bnact(nullptr, a.Cmid, a.bn1.coef, a.Cmid, 1, nullptr, 0, 1);
-        d.a0 = a0; d.a0_ld = a.Cin; d.w1 = w.wpw; d.Cin = a.Cin;
-        d.w = w.wdws; d.out = a.y2; d.planes = a.B * a.T; d.Hin = a.Hin; d.Win = a.Win; d.Hout = a.Hout;
-        d.Wout = a.Wout; d.C = a.Cmid; d.stride = a.stride; d.ks = a.ks; d.stats = nullptr;
+    // ---- conv_pw (dwiseneuro.py:90-93) + spat_covn_dw (:96-102), by the plan's route
+    // the chained / generic stencil: on the stored y1, or (rebuilt) on the y1 rows it rebuilds from a0 on the matrix cores
+    auto spatial_fwd = [&](bool rebuilt) -> int {
+        DwSpatialFwd d = dws_desc<DwSpatialFwd>(a, rebuilt);
+        d.in = ld_bnact(rebuilt ? nullptr : a.y1, a.Cmid, a.bn1.coef, a.Cmid, 1, nullptr, 0, 1);
+        if (rebuilt) { d.a0 = a0; d.w1 = w.wpw; }
+        d.w = w.wdws; d.out = a.y2; d.stats = p.tr ? w.st2 : nullptr;
         PROF(DWN_FAM_DWS_FWD, launch_dw_spatial_fwd(d, dt, s));
-    } else if (y1_free) {
-        // y1-free training: BatchNorm-1's batch statistics from the Gram matrix of a0 (one C-wide pass: gemm_tn [a0 | 1]^T a0), then the
-        // chained stencil rebuilds the y1 rows it needs from a0 on the matrix cores: conv_pw is no pass, a.y1 is not written
-        LoadDesc cat = ld_plain(a0, a.Cin);
-        cat.cat_c1 = a.Cin; cat.cat_c2 = 0;
-        if (bs) {                                     // (frozen: BatchNorm-1 is known, no Gram pass)
-        // the streaming kernel of dwn_gram.hip where it is built (bf16, 64 channels: one read of a0, gram_nrep replicas), else gemm_tn
-        bool streamed = false;
-        PROF(DWN_FAM_PW_FWD, k_gram(a0, a.Cin, Min, a.Cin, w.gram, dt, &streamed, s));
-        if (!streamed) {
-        GemmTN g = tn_base(cat, LD_CAT1, ld_plain(a0, a.Cin), LD_PLAIN, (int)Min, a.Cin + 8, a.Cin, reinterpret_cast<float*>(w.gram), a.Cin, 1);
-        g.dw_f64 = 1;                                 // fp64 atomics: the variance is a difference of these sums
-        PROF(DWN_FAM_PW_FWD, launch_gemm_tn(g, dt, s));
+        return 0;
+    };
+    switch (p.pw) {
+    case PW_EVAL_CHAIN:
+        TRY(spatial_fwd(true));
+        break;
+    case PW_Y1_FREE:
+        // BatchNorm-1's batch statistics from the Gram matrix of a0 (one C-wide pass), then the stencil rebuilds the y1 rows it needs:
+        // conv_pw is no pass, a.y1 is not written.  (Frozen: BatchNorm-1 is known, no Gram pass)
+        if (p.bs) {
+            // the streaming kernel of dwn_gram.hip where it is built (bf16, 64 channels: one read, gram_nrep replicas), else gemm_tn [a0 | 1]^T a0
+            bool streamed = false;
+            PROF(DWN_FAM_PW_FWD, k_gram(a0, a.Cin, Min, a.Cin, w.gram, dt, &streamed, s));
+            if (!streamed) {
+                LoadDesc cat = ld_plain(a0, a.Cin);
+                cat.cat_c1 = a.Cin; cat.cat_c2 = 0;
+                GemmTN g = tn_base(cat, LD_CAT1, xin, LD_PLAIN, (int)Min, a.Cin + 8, a.Cin, reinterpret_cast<float*>(w.gram), a.Cin, 1);
+                g.dw_f64 = 1;                         // fp64 atomics: the variance is a difference of these sums
+                PROF(DWN_FAM_PW_FWD, launch_gemm_tn(g, dt, s));
+            }
+            PROF(DWN_FAM_PW_FWD, k_bn1_gram_finalize(w.gram, streamed ? gram_nrep(dt, a.Cin) : 1, a.w_pw, a.Cmid, a.Cin, (double)Min,
+                                                     a.bn1.gamma, a.bn1.beta, a.bn1.running_mean, a.bn1.running_var, a.bn1.num_batches_tracked,
+                                                     a.momentum, a.eps, a.bn1.coef, p.identity_sc ? w.stsc : nullptr, dt, s));
         }
-        PROF(DWN_FAM_PW_FWD, k_bn1_gram_finalize(w.gram, streamed ? gram_nrep(dt, a.Cin) : 1, a.w_pw, a.Cmid, a.Cin, (double)Min, a.bn1.gamma, a.bn1.beta, a.bn1.running_mean,
-                                                 a.bn1.running_var, a.bn1.num_batches_tracked, a.momentum, a.eps, a.bn1.coef,
-                                                 identity_sc ? w.stsc : nullptr, dt, s));
-        }
-        DwSpatialFwd d; memset(&d, 0, sizeof(d));
-        d.in = ld_bnact(nullptr, a.Cmid, a.bn1.coef, a.Cmid, 1, nullptr, 0, 1);
-        d.a0 = a0; d.a0_ld = a.Cin; d.w1 = w.wpw; d.Cin = a.Cin;
-        d.w = w.wdws; d.out = a.y2; d.planes = a.B * a.T; d.Hin = a.Hin; d.Win = a.Win; d.Hout = a.Hout;
-        d.Wout = a.Wout; d.C = a.Cmid; d.stride = a.stride; d.ks = a.ks; d.stats = w.st2;
-        PROF(DWN_FAM_DWS_FWD, launch_dw_spatial_fwd(d, dt, s));
-    } else if (block_fwd_rc(a)) {
-        // eval: BatchNorm-1 needs no batch statistics and nobody reads y1 again, so the stencil kernel rebuilds its y1
-        // tiles from a0 (MFMA) and conv_pw disappears as a pass (a.y1 is not written)
+        TRY(spatial_fwd(true));
+        break;
+    case PW_EVAL_RC: {
+        // BatchNorm-1 needs no batch statistics and nobody reads y1 again, so the stencil kernel rebuilds its y1 tiles from a0
+        // (MFMA) and conv_pw disappears as a pass (a.y1 is not written)
         TRY(dwn_dw_spatial_rc_prep(a.w_pw, w.wdws, a.bn1.coef, a.Cmid, a.Cin, w.rcblob, device, stream));
         dwn_dw_spatial_rc_fwd_args r; memset(&r, 0, sizeof(r));
         r.a0 = a0; r.a0_ld = a.Cin; r.blob = w.rcblob; r.out = a.y2; r.planes = a.B * a.T; r.Hin = a.Hin; r.Win = a.Win;
         r.Hout = a.Hout; r.Wout = a.Wout; r.Cin = a.Cin; r.E = a.Cmid; r.stride = a.stride; r.stats = nullptr;
         r.rows_band = 0; r.round_y1 = 1;
         PROF(DWN_FAM_DWS_FWD, dwn_dw_spatial_fwd_rc(&r, device, stream));
-    } else {
-    {
+        break;
+    }
+    case PW_MATERIALISED: {
+        // y1 = a0 @ W1^T, Σ/Σ² for bn1
         GemmNN g = nn_base(xin, LD_PLAIN, w.wpw, a.Cin, a.y1, a.Cmid, (int)Min, a.Cmid, a.Cin, 1);
-        g.f32_split = f32_split_of(a.f32_products, !tr);      // eval-mode fp32: bf16 hi/lo products (dwn_gemm_nn.h NN_F32_X3) unless NATIVE
-        g.stats = tr ? w.st1 : nullptr; g.stat_nchan = a.Cmid;
+        g.f32_split = f32_split_of(a.f32_products, !p.tr);    // eval-mode fp32: bf16 hi/lo products (dwn_gemm_nn.h NN_F32_X3) unless NATIVE
+        g.stats = p.tr ? w.st1 : nullptr; g.stat_nchan = a.Cmid;
         PROF(DWN_FAM_PW_FWD, launch_gemm_nn(g, dt, s));
-    }
-    if (bs) TRY(bn_finalize(w.st1, a.Cmid, (double)Min, a.bn1, a.Cmid, 1, a.momentum, a.eps, s));
-    // spat_covn_dw (:96-102)
-    {
-        DwSpatialFwd d; memset(&d, 0, sizeof(d));
-        d.in = ld_bnact(a.y1, a.Cmid, a.bn1.coef, a.Cmid, 1, nullptr, 0, 1);
-        d.w = w.wdws; d.out = a.y2; d.planes = a.B * a.T; d.Hin = a.Hin; d.Win = a.Win; d.Hout = a.Hout;
-        d.Wout = a.Wout; d.C = a.Cmid; d.stride = a.stride; d.ks = a.ks; d.stats = tr ? w.st2 : nullptr;
-        PROF(DWN_FAM_DWS_FWD, launch_dw_spatial_fwd(d, dt, s));
+        if (p.bs) TRY(bn_finalize(w.st1, a.Cmid, (double)Min, a.bn1, a.Cmid, 1, a.momentum, a.eps, s));
+        TRY(spatial_fwd(false));
+        break;
     }
     }
-    if (bs) TRY(bn_finalize(w.st2, a.Cmid, (double)Mout, a.bn2, a.Cmid, 1, a.momentum, a.eps, s));
-    // temp_covn_dw (:105-111)
-    const bool eval_z3 = !tr;       // eval: z3 and the SE pooling sums come straight from the temporal pass (integer sums: any order)
-    {
+    if (p.bs) TRY(bn_finalize(w.st2, a.Cmid, (double)Mout, a.bn2, a.Cmid, 1, a.momentum, a.eps, s));
+    {   // ---- temp_covn_dw (:105-111)
         DwTemporalFwd d; memset(&d, 0, sizeof(d));
         d.in = ld_bnact(a.y2, a.Cmid, a.bn2.coef, a.Cmid, 1, nullptr, 0, 1);
         d.w = w.wdwt; d.out = a.y3; d.B = a.B; d.T = a.T; d.HW = a.Hout * a.Wout; d.C = a.Cmid; d.kt = a.kt;
-        d.stats = tr ? w.st3 : nullptr;
-        if (eval_z3) {       // eval: BatchNorm-3 is known -> z3 and the SE pooling sums straight from this pass, y3 never stored
+        d.stats = p.tr ? w.st3 : nullptr;
+        if (p.eval_z3) {     // eval: BatchNorm-3 is known -> z3 and the SE pooling sums (integer sums: any order) straight from this pass
             d.out = a.z3; d.z_scale = a.bn3.coef; d.z_shift = a.bn3.coef + a.Cmid; d.pooled = w.pooled;
         }
         PROF(DWN_FAM_DWT_FWD, launch_dw_temporal_fwd(d, dt, s));
     }
-    if (bs) TRY(bn_finalize(w.st3, a.Cmid, (double)Mout, a.bn3, a.Cmid, 1, a.momentum, a.eps, s));
-    // se (:38-43)
-    if (!eval_z3) {
+    if (p.bs) TRY(bn_finalize(w.st3, a.Cmid, (double)Mout, a.bn3, a.Cmid, 1, a.momentum, a.eps, s));
+    // ---- se (:38-43)
+    if (!p.eval_z3) {
         LoadDesc z3 = ld_bnact(a.y3, a.Cmid, a.bn3.coef, a.Cmid, 1, nullptr, 0, S_out);
         PROF(DWN_FAM_SE_POOL, k_se_pool(z3, a.B, a.Cmid, S_out, w.pooled, a.z3, dt, s));
     }
     // (z3 * gate_b) @ W2^T == z3 @ (W2 . diag(gate_b))^T: where conv_pwl runs on per-sample weights the SE kernel writes them too
     int gate_folded = 0;
     TRY(k_se_mlp_fwd(w.pooled, 1.0f / (float)S_out, a.se_wr, a.se_br, a.se_we, a.se_be, a.B, a.Cmid, a.se_r,
-                     a.se_pmean, a.se_hidpre, a.se_gate, pwl_gated_weights(a) ? a.w_pwl : nullptr, w.wgated, a.Cout, dt, &gate_folded, s));
-    // conv_pwl (:117-120): y4 = (silu(bn3(y3)) * gate) @ W2^T
-    if (pwl_gated_weights(a)) {
-        if (!gate_folded) TRY(k_gate_weights(a.w_pwl, a.se_gate, w.wgated, a.B, a.Cout, a.Cmid, dt, s));
-        GemmNN g = nn_base(ld_plain(a.z3, a.Cmid), LD_PLAIN, w.wgated, a.Cmid, a.y4, a.Cout, (int)Mout, a.Cout, a.Cmid, 1);
-        g.b_sample_stride = (i64)a.Cout * a.Cmid; g.b_rows_per_sample = S_out;
-        g.stats = tr ? w.st4 : nullptr; g.stat_nchan = a.Cout; g.f32_split = f32_split_of(a.f32_products, !tr);
-        PROF(DWN_FAM_PWL_FWD, launch_gemm_nn(g, dt, s));
-    } else {
-        LoadDesc u = ld_plain(a.z3, a.Cmid);
-        u.gate = a.se_gate; u.gate_ld = a.Cmid; u.rows_per_sample = S_out;
-        GemmNN g = nn_base(u, LD_GATE, w.wpwl, a.Cmid, a.y4, a.Cout, (int)Mout, a.Cout, a.Cmid, 1);
-        g.stats = tr ? w.st4 : nullptr; g.stat_nchan = a.Cout; g.f32_split = f32_split_of(a.f32_products, !tr);
+                     a.se_pmean, a.se_hidpre, a.se_gate, p.pwl_gated ? a.w_pwl : nullptr, w.wgated, a.Cout, dt, &gate_folded, s));
+    {   // ---- conv_pwl (:117-120): y4 = (silu(bn3(y3)) * gate) @ W2^T
+        GemmNN g;
+        if (p.pwl_gated) {
+            if (!gate_folded) TRY(k_gate_weights(a.w_pwl, a.se_gate, w.wgated, a.B, a.Cout, a.Cmid, dt, s));
+            g = nn_base(ld_plain(a.z3, a.Cmid), LD_PLAIN, w.wgated, a.Cmid, a.y4, a.Cout, (int)Mout, a.Cout, a.Cmid, 1);
+            g.b_sample_stride = (i64)a.Cout * a.Cmid; g.b_rows_per_sample = S_out;
+        } else {
+            LoadDesc u = ld_plain(a.z3, a.Cmid);
+            u.gate = a.se_gate; u.gate_ld = a.Cmid; u.rows_per_sample = S_out;
+            g = nn_base(u, LD_GATE, w.wpwl, a.Cmid, a.y4, a.Cout, (int)Mout, a.Cout, a.Cmid, 1);
+        }
+        g.stats = p.tr ? w.st4 : nullptr; g.stat_nchan = a.Cout; g.f32_split = f32_split_of(a.f32_products, !p.tr);
         PROF(DWN_FAM_PWL_FWD, launch_gemm_nn(g, dt, s));
     }
-    // shortcut (:125-134) + residual (:143); the two linear BatchNorms (conv_pwl.1.bn, bn_sc.bn) finalise in one launch
+    // ---- shortcut (:125-134) + residual (:143); the two linear BatchNorms (conv_pwl.1.bn, bn_sc.bn) finalise in one launch
     ResGeom gm = geom_of(a);
-    if (bs) {
+    if (p.bs) {
         // (y1-free on an identity-map block: the shortcut's sums came out of the Gram pass, k_bn1_gram_finalize)
-        if (!(y1_free && identity_sc)) PROF(DWN_FAM_RESID_FWD, k_shortcut_stats(xin, gm, w.stsc, dt, s));
+        if (!(p.pw == PW_Y1_FREE && p.identity_sc)) PROF(DWN_FAM_RESID_FWD, k_shortcut_stats(xin, gm, w.stsc, dt, s));
         TRY(k_bn_finalize_train(fin_job(w.st4, a.Cout, (double)Mout, a.bn4, a.Cout),
                                  fin_job(w.stsc, a.Cin, (double)Mout, a.bnsc, a.Cout), a.momentum, a.eps, s));
     }
@@ -738,15 +754,14 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
     if (a.training == DWN_BN_EVAL)
         return dwn_set_error(-7, "block_backward: only training-mode (batch-statistics) and frozen-statistics backward are built");
     ENTER(device);
-    const bool frozen = a.training == DWN_BN_FROZEN;   // BatchNorm backward triples (scale, 0, 0): every consumer below runs unchanged
-    BlockWs w = carve_block(a, 1, a.ws, a.ws_bytes);
+    const BlockPlan p = plan_block(a);
+    BlockWs w = carve_block(a, p, 1, a.ws, a.ws_bytes);
     if (w.bytes > a.ws_bytes) return dwn_set_error(-6, "block_backward: workspace too small");
-    const int dt = a.dtype;
-    const i64 Min = (i64)a.B * a.T * a.Hin * a.Win, Mout = (i64)a.B * a.T * a.Hout * a.Wout;
-    const int S_out = a.T * a.Hout * a.Wout;
+    const int dt = a.dtype, S_out = p.S_out;
+    const i64 Min = p.Min, Mout = p.Mout;
+    const bool y1_free = p.pw == PW_Y1_FREE;         // the forward of these arguments wrote no y1 (BlockPlan::writes)
     float* dg = reinterpret_cast<float*>(w.pooled);
-    const bool y1_free = block_y1_free(a);           // the forward of these arguments wrote no y1 (dwn_block_forward_writes)
-    {   // one launch: zero the statistics arena, W2^T [Cmid][Cout], tap-major depth-wise weights, identity affine
+    {   // ---- prep, one launch: zero the statistics arena, W2^T [Cmid][Cout], tap-major depth-wise weights, identity affine
         PrepArgs pa;
         bool ok = pa.zero(w.zero_beg, ((size_t)(w.zero_end - w.zero_beg) + 15) & ~(size_t)15);
         ok = ok && pa.packw(a.w_pwl, w.wpwl, 1, a.Cout, a.Cmid, 1, a.Cmid, a.Cout);
@@ -760,23 +775,22 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
         ok = ok && pa.zero(a.dw_dws, (size_t)a.Cmid * a.ks * a.ks * sizeof(float));
         ok = ok && pa.zero(a.dw_dwt, (size_t)a.Cmid * a.kt * sizeof(float));
         ok = ok && pa.zero(a.dw_pwl, (size_t)a.Cout * a.Cmid * sizeof(float));
-        if (w.pb) ok = ok && pa.zero(w.pb, (size_t)a.B * a.Cout * a.Cmid * sizeof(float));
+        if (p.pwl_per_sample) ok = ok && pa.zero(w.pb, (size_t)a.B * a.Cout * a.Cmid * sizeof(float));
         ok = ok && pa.zero(w.gacc, pw_fold_floats(a.Cin) * sizeof(float));
         ok = ok && pa.zero(w.tacc, pw_wgrad_tacc_floats(a.Cmid, a.Cin) * sizeof(float));
         if (!ok) return dwn_set_error(-2, "block_backward: workspace arena and dw_* buffers must be 16-byte aligned");
         TRY(k_prep(pa, dt, s));
     }
-
+    // ---- residual + the two linear BNs (bn4 = conv_pwl.1.bn, bnsc = bn_sc.bn)
     LoadDesc xin = ld_plain(a.x_has_pe ? a.x : a.a0, a.Cin);     // block input including its positional encoding
     ResGeom gm = geom_of(a);
-    // residual + the two linear BNs (bn4 = conv_pwl.1.bn, bnsc = bn_sc.bn)
     PROF(DWN_FAM_RESID_BWD, k_residual_bwd_reduce(xin, a.y4, a.dout, a.bn4.coef, a.bnsc.coef, a.drop_scale, gm, w.st4, w.stsc, dt, s));
-    TRY(k_bn_bwd_finalize(bwd_job(w.st4, (double)Mout, a.bn4, w.abc4, a.Cout, frozen),
-                          bwd_job(w.stsc, (double)Mout, a.bnsc, w.abcsc, a.Cout, frozen), s));
+    TRY(k_bn_bwd_finalize(bwd_job(w.st4, (double)Mout, a.bn4, w.abc4, a.Cout, p.frozen),
+                          bwd_job(w.stsc, (double)Mout, a.bnsc, w.abcsc, a.Cout, p.frozen), s));
     PROF(DWN_FAM_RESID_BWD, k_residual_bwd_dy4(a.y4, a.dout, w.abc4, a.drop_scale, gm, a.dy4, dt, s));
-    // conv_pwl backward: du = dy4 @ W2 (+ SE gate gradient), dW2 = dy4^T @ u
+    // ---- conv_pwl + SE backward: du = dy4 @ W2 (+ SE gate gradient), dW2 = dy4^T @ u; both forms leave dh3 in du and its sums in st3
     void* du = a.buf_a;
-    if (w.pb) {
+    if (p.pwl_per_sample) {
         // per-sample products P_b = dy4_b^T z3_b -> dW2 and the SE gate gradient without touching du
         {
             GemmTN g = tn_base(ld_plain(a.dy4, a.Cout), LD_PLAIN, ld_plain(a.z3, a.Cmid), LD_PLAIN, (int)Mout, a.Cout,
@@ -794,32 +808,31 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
         g.stats = w.st3; g.stat_nchan = a.Cmid;
         PROF(DWN_FAM_PWL_DGRAD, launch_gemm_nn(g, dt, s));
     } else {
-    {
-        GemmNN g = nn_base(ld_plain(a.dy4, a.Cout), LD_PLAIN, w.wpwl, a.Cout, du, a.Cmid, (int)Mout, a.Cmid, a.Cout, 1);
-        g.epi = EPI_DG; g.y3 = a.z3; g.ldy3 = a.Cmid; g.s3 = nullptr; g.t3 = nullptr; g.dg = dg;
-        g.dg_ld = a.Cmid; g.rows_per_sample = S_out;
-        PROF(DWN_FAM_PWL_DGRAD, launch_gemm_nn(g, dt, s));
+        // the materialised du
+        {
+            GemmNN g = nn_base(ld_plain(a.dy4, a.Cout), LD_PLAIN, w.wpwl, a.Cout, du, a.Cmid, (int)Mout, a.Cmid, a.Cout, 1);
+            g.epi = EPI_DG; g.y3 = a.z3; g.ldy3 = a.Cmid; g.s3 = nullptr; g.t3 = nullptr; g.dg = dg;
+            g.dg_ld = a.Cmid; g.rows_per_sample = S_out;
+            PROF(DWN_FAM_PWL_DGRAD, launch_gemm_nn(g, dt, s));
+        }
+        {
+            LoadDesc u = ld_plain(a.z3, a.Cmid);
+            u.gate = a.se_gate; u.gate_ld = a.Cmid; u.rows_per_sample = S_out;
+            GemmTN g = tn_base(ld_plain(a.dy4, a.Cout), LD_PLAIN, u, LD_GATE, (int)Mout, a.Cout, a.Cmid, a.dw_pwl, a.Cmid, 1);
+            PROF(DWN_FAM_PWL_WGRAD, launch_gemm_tn(g, dt, s));
+        }
+        TRY(k_se_mlp_bwd(dg, a.se_gate, a.se_hidpre, a.se_pmean, a.se_wr, a.se_we, a.B, a.Cmid, a.se_r,
+                         1.0f / (float)S_out, w.dgp, w.dhp, w.dps, a.dse_wr, a.dse_br, a.dse_we, a.dse_be, s, false));
+        // bn3 backward sums over dh3 = (du*gate + dpS) * silu'(h3)
+        LoadDesc d3; memset(&d3, 0, sizeof(d3));
+        d3.p = du; d3.q = a.y3; d3.ld = a.Cmid; d3.v1 = w.ident3; d3.v2 = w.ident3 + a.Cmid; d3.v3 = w.ident3 + 2 * a.Cmid;
+        d3.v4 = a.bn3.coef; d3.v5 = a.bn3.coef + a.Cmid; d3.gate = a.se_gate; d3.gate2 = w.dps; d3.gate_ld = a.Cmid;
+        d3.rows_per_sample = S_out;
+        // ... and dh3 replaces du in place, so the temporal kernel reads (dh3, y3) with the plain BN-backward affine
+        PROF(DWN_FAM_BN3_REDUCE, k_bn3_bwd_reduce(d3, a.bn3.coef, Mout, a.Cmid, w.st3, du, dt, s));
     }
-    {
-        LoadDesc u = ld_plain(a.z3, a.Cmid);
-        u.gate = a.se_gate; u.gate_ld = a.Cmid; u.rows_per_sample = S_out;
-        GemmTN g = tn_base(ld_plain(a.dy4, a.Cout), LD_PLAIN, u, LD_GATE, (int)Mout, a.Cout, a.Cmid, a.dw_pwl, a.Cmid, 1);
-        PROF(DWN_FAM_PWL_WGRAD, launch_gemm_tn(g, dt, s));
-    }
-    // SE backward
-    TRY(k_se_mlp_bwd(dg, a.se_gate, a.se_hidpre, a.se_pmean, a.se_wr, a.se_we, a.B, a.Cmid, a.se_r,
-                     1.0f / (float)S_out, w.dgp, w.dhp, w.dps, a.dse_wr, a.dse_br, a.dse_we, a.dse_be, s, false));
-    // bn3 backward sums over dh3 = (du*gate + dpS) * silu'(h3)
-    LoadDesc d3; memset(&d3, 0, sizeof(d3));
-    d3.p = du; d3.q = a.y3; d3.ld = a.Cmid; d3.v1 = w.ident3; d3.v2 = w.ident3 + a.Cmid; d3.v3 = w.ident3 + 2 * a.Cmid;
-    d3.v4 = a.bn3.coef; d3.v5 = a.bn3.coef + a.Cmid; d3.gate = a.se_gate; d3.gate2 = w.dps; d3.gate_ld = a.Cmid;
-    d3.rows_per_sample = S_out;
-    // ... and dh3 replaces du in place, so the temporal kernel reads (dh3, y3) with the plain BN-backward affine
-    PROF(DWN_FAM_BN3_REDUCE, k_bn3_bwd_reduce(d3, a.bn3.coef, Mout, a.Cmid, w.st3, du, dt, s));
-    }
-    TRY(k_bn_bwd_finalize(bwd_job(w.st3, (double)Mout, a.bn3, w.abc3, a.Cmid, frozen), BnBwdJob{}, s));
-    // temporal dw backward
-    {
+    TRY(k_bn_bwd_finalize(bwd_job(w.st3, (double)Mout, a.bn3, w.abc3, a.Cmid, p.frozen), BnBwdJob{}, s));
+    {   // ---- temporal dw backward
         DwTemporalBwd d; memset(&d, 0, sizeof(d));
         d.dy = ld_affine2(du, a.y3, a.Cmid, w.abc3, a.Cmid);
         d.dy_kind = LD_PLAIN;                           // y3 is recomputed from y2 inside the kernel (one E-wide pass less)
@@ -828,52 +841,38 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
         d.kt = a.kt; d.stats = w.st2;
         PROF(DWN_FAM_DWT_BWD, launch_dw_temporal_bwd(d, dt, s));
     }
-    TRY(k_bn_bwd_finalize(bwd_job(w.st2, (double)Mout, a.bn2, w.abc2, a.Cmid, frozen), BnBwdJob{}, s));
-    // spatial dw backward (du is dead: reuse buf_a for dh1)
+    TRY(k_bn_bwd_finalize(bwd_job(w.st2, (double)Mout, a.bn2, w.abc2, a.Cmid, p.frozen), BnBwdJob{}, s));
+    // ---- spatial dw backward (du is dead: reuse buf_a for dh1)
     void* dh1 = a.buf_a;
     {
-        DwSpatialBwd d; memset(&d, 0, sizeof(d));
+        DwSpatialBwd d = dws_desc<DwSpatialBwd>(a, y1_free);
         d.dy = ld_affine2(a.buf_b, a.y2, a.Cmid, w.abc2, a.Cmid);
         d.y1 = ld_ycoef(y1_free ? nullptr : a.y1, a.Cmid, a.bn1.coef, a.Cmid);
-        if (y1_free) { d.a0 = xin.p; d.a0_ld = a.Cin; d.w1 = w.wpw; d.Cin = a.Cin; }      // y1 rebuilt from the block input
-        d.w = w.wdws; d.dh1 = dh1; d.dw = a.dw_dws; d.planes = a.B * a.T; d.Hin = a.Hin; d.Win = a.Win;
-        d.Hout = a.Hout; d.Wout = a.Wout; d.C = a.Cmid; d.stride = a.stride; d.ks = a.ks; d.stats = w.st1;
+        if (y1_free) { d.a0 = xin.p; d.w1 = w.wpw; }                                      // y1 rebuilt from the block input
+        d.w = w.wdws; d.dh1 = dh1; d.dw = a.dw_dws; d.stats = w.st1;
         PROF(DWN_FAM_DWS_BWD, launch_dw_spatial_bwd(d, dt, s));
     }
-    TRY(k_bn_bwd_finalize(bwd_job(w.st1, (double)Min, a.bn1, w.abc1, a.Cmid, frozen), BnBwdJob{}, s));
-    // conv_pw backward WITHOUT y1.  dy1 = A1*dh1 + A2*y1 + A3 is linear and y1 = a0.W1^T, so the y1 terms fold into Cin x Cin
+    TRY(k_bn_bwd_finalize(bwd_job(w.st1, (double)Min, a.bn1, w.abc1, a.Cmid, p.frozen), BnBwdJob{}, s));
+    // ---- conv_pw backward WITHOUT y1.  dy1 = A1*dh1 + A2*y1 + A3 is linear and y1 = a0.W1^T, so the y1 terms fold into Cin x Cin
     // matrices on either side:  da0 = [dh1 | a0] . [diag(A1) W1 ; G] + r3  (Bp, r3: k_pw_bwd_prep) and
     // dW1 = diag(A1) (dh1^T a0) + diag(A2) W1 (a0^T a0) + A3 (1^T a0)  (raw products in tacc, folded by k_pw_wgrad_fold)
     // On a stride-1 block (identity shortcut map, output channels = input channels tiled once or twice) the shortcut branch's
-    // gradient is folded into this GEMM and its result IS dx: no pass over (da0, x, dout) -> dx.
+    // gradient is folded into this GEMM and its result IS dx: no pass over (da0, x, dout) -> dx (BlockPlan::dx_folded).
     // (one-pass kernel only: as an epilogue of the two-GEMM path's data-gradient GEMM it cost 30-60 us where the pass it replaces
     // takes 20-35.)  On a strided block the epilogue gathers: only the rows the nearest map samples carry the shortcut's terms.
-    const bool identity_sc = a.stride == 1 && a.Hin == a.Hout && a.Win == a.Wout;
-    const bool dx_folded = a.Cout % a.Cin == 0 && a.Cout / a.Cin <= 2 && dwn_pw_bwd_fused_supported(dt, Min, a.Cmid, a.Cin) &&
-                           (identity_sc || (gm.hinv && gm.winv && a.Hin + a.Win <= 512));
-    TRY(pw_backward(dt, dh1, xin.p, a.w_pw, w.abc1, a.Cmid, a.Cin, Min, w.bp, w.gacc, w.r3, w.tacc, dx_folded ? a.dx : a.da0, a.dw_pw,
-                    dx_folded ? a.dout : nullptr, w.abcsc, a.Cout, (dx_folded && !identity_sc) ? &gm : nullptr, s, false));
-    if (!dx_folded) PROF(DWN_FAM_RESID_BWD, k_residual_bwd_dx(xin, a.da0, a.dout, w.abcsc, gm, a.dx, dt, s));
-    // the parameter-gradient tail, last launch of the block: the SE MLP's parameter gradients (from dgp / dhp, k_se_mlp_bwd above)
+    TRY(pw_backward(dt, dh1, xin.p, a.w_pw, w.abc1, a.Cmid, a.Cin, Min, w.bp, w.gacc, w.r3, w.tacc, p.dx_folded ? a.dx : a.da0, a.dw_pw,
+                    p.dx_folded ? a.dout : nullptr, w.abcsc, a.Cout, p.sc_gathered ? &gm : nullptr, s, false));
+    if (!p.dx_folded) PROF(DWN_FAM_RESID_BWD, k_residual_bwd_dx(xin, a.da0, a.dout, w.abcsc, gm, a.dx, dt, s));
+    // ---- the parameter-gradient tail, last launch of the block: the SE MLP's parameter gradients (from dgp / dhp, k_se_mlp_bwd above)
     // and dW1 folded from tacc.  Nothing in the block reads them, so they leave the chain between the SE kernel and the dh3 GEMM
     return k_block_param_tail(w.dgp, w.dhp, a.se_pmean, a.se_hidpre, a.B, a.Cmid, a.se_r, a.dse_wr, a.dse_br, a.dse_we, a.dse_be,
                               w.tacc, w.abc1, a.w_pw, a.Cmid, a.Cin, a.dw_pw, dt, s);
 }
 
-// Which of the intermediates dwn_block_forward will write for these arguments: bit 0 = y1, bit 1 = y3.  Training writes
-// both; the eval-mode forward skips y1 where the stencil rebuilds it (block_fwd_rc) and y3 where the temporal pass emits z3
-// directly — the caller need not allocate what is not written (and may pass NULL for it).
+// Which of the intermediates dwn_block_forward will write for these arguments: bit 0 = y1, bit 1 = y3 (BlockPlan::writes) — the
+// caller need not allocate what is not written (and may pass NULL for it).
 int dwn_block_forward_writes(const dwn_block_args* ap) {
-    const dwn_block_args& a = *ap;
-    if (a.training) return block_y1_free(a) ? 2 : 3;
-    if (block_fwd_rc(a)) return 0;
-    if (DWN_EVAL_CHAIN && a.dtype == DWN_BF16) {        // the chained stencil's rebuilt-input form (dwn_block_forward, eval_chain)
-        DwSpatialFwd f; memset(&f, 0, sizeof(f));
-        f.planes = a.B * a.T; f.Hin = a.Hin; f.Win = a.Win; f.Hout = a.Hout; f.Wout = a.Wout; f.C = a.Cmid; f.stride = a.stride; f.ks = a.ks;
-        f.in.ld = a.Cmid; f.a0_ld = a.Cin; f.Cin = a.Cin;
-        if (dw_spatial_fwd_rc_walk_supported(f, a.dtype)) return 0;
-    }
-    return 1;
+    return plan_block(*ap).writes;
 }
 
 // ------------------------------------------------------------------------------------------------ pool

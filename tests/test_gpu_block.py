@@ -73,7 +73,11 @@ CASES = [
     (64, 64, 2, 6, 32, 2, 4, 12, 16),
     (128, 256, 1, 6, 32, 2, 4, 9, 16),
     (256, 256, 2, 6, 32, 1, 4, 9, 16),
+    # a plane the tile-resident y1-rebuilding eval stencil (dwn_dwrc.hip) is built for and the chained row-walk stencil is not (12
+    # output columns): the one eval case that takes it through the block composite (test_block_eval_forward asserts that it does)
+    (64, 64, 1, 7, 32, 1, 2, 4, 12),
 ]
+RC_EVAL_CASE = 22
 
 
 def y1_free_case(case, dtype, mode="auto"):
@@ -178,11 +182,21 @@ def _train_forward_backward(case, dtype, drop, y1, temporal_kernel=5):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("case_id", [1, 3, 4, 9, 10, 12, 14, 15, 16, 17, 18, 19, 20, 21])
+@pytest.mark.parametrize("case_id", [1, 3, 4, 9, 10, 12, 14, 15, 16, 17, 18, 19, 20, 21, RC_EVAL_CASE])
 def test_block_eval_forward(dtype, case_id):
-    """Eval-mode forward.  The cases with 64 / 128 input channels take, in bf16, the y1-recomputing stencil
-    (dwn_dw_spatial_fwd_rc: conv_pw never runs as its own pass) — except case 14, whose 130-pixel rows fit neither register
-    geometry of that kernel and must fall back to conv_pw + stencil; case 1 and every fp32 run take the materialised path."""
+    """Eval-mode forward.  In bf16, the cases with 64 / 128 input channels and a row-walk plane width (3, 4, 9, 10, 12, 19, 20) take
+    the chained stencil's rebuilt-input form and RC_EVAL_CASE, whose 12-pixel rows that stencil is not built for, the tile-resident
+    y1-recomputing stencil (dwn_dw_spatial_fwd_rc): conv_pw never runs as its own pass.  Case 14, whose 130-pixel rows fit neither,
+    falls back to conv_pw + stencil, as do case 1, the 256-channel cases and every fp32 run."""
+    if case_id == RC_EVAL_CASE and dtype == torch.bfloat16:      # the case must not drift onto another route
+        import ctypes as C
+        import sensorium_amd._lib as L
+        cin, cout, stride, exp, ser, B, T, H, W = CASES[case_id]
+        assert L.lib.dwn_dw_spatial_rc_supported(L.DWN_BF16, cin, cin * exp, 3, stride, H, W) == 1
+        f = L.DwSpatialFwdArgs()
+        f.planes = B * T; f.Hin = H; f.Win = W; f.Hout = (H - 1) // stride + 1; f.Wout = (W - 1) // stride + 1; f.C = cin * exp
+        f.stride = stride; f.ks = 3; f.inp.ld = cin * exp; f.a0_ld = cin; f.Cin = cin
+        assert L.lib.dwn_dw_spatial_fwd_rc_supported(C.byref(f), L.DWN_BF16) == 0
     _eval_forward(CASES[case_id], dtype)
 
 
