@@ -1167,6 +1167,69 @@ int dwn_pair_syrk(const dwn_pair_args* a, int device, void* stream);
 int dwn_pair_corr_finalize(const dwn_pair_args* a, int device, void* stream);
 int dwn_pair_compare(const dwn_pair_compare_args* a, int device, void* stream);
 
+/* ---- Population modes (ABI 7, appended; csrc/dwn_modes.hip): the k leading eigenpairs of a symmetric N x N float64
+ * matrix `scale * A` by block subspace iteration with Rayleigh-Ritz extraction, stage by stage and as one driver, and the principal
+ * angles between two subspaces.  A: double [N][lda], lda >= N, SYMMETRIC (the product reads A[j][i] where it needs A[i][j]; for an
+ * unsymmetric A it computes A^T Q), intended positive semi-definite up to rounding (for an indefinite matrix the iteration finds the
+ * subspace dominant in magnitude).  A block is double [N][ld] with ld >= p rounded up to 16; columns [p, p rounded up to 16) are
+ * written as zeros by every entry that writes a block.  Small matrices (H, W) are double [p][DWN_MODES_MAXP] row-major.
+ *
+ * dwn_modes_symm: needs A, Q, Y.  Y = scale * A Q on v_mfma_f64_16x16x4_f64; the sum over j is cut into four quarters of
+ *   ((N + 3) / 4 rounded up to 4) terms, each summed in ascending j, and the quarters are added in ascending order.
+ * dwn_modes_moments: needs A, moments, ws (dwn_modes_moments_ws_bytes).  moments[0] = scale * sum_i A_ii, moments[1] = scale^2 *
+ *   sum_ij A_ij^2, both in float64 in a fixed order (rows strided over 256 threads and closed by a fixed tree).
+ * dwn_modes_orth: needs Y, Q (Q may be Y).  Q = orth(Y) by classical Gram-Schmidt applied twice, column by column; a column whose
+ *   norm after the projections is at most DWN_MODES_ORTH_C * N * 2^-53 * ||Y||_F becomes an exact zero column.  A NaN stays a NaN.
+ * dwn_modes_small_eigh: needs H, W, values.  The eigenpairs of the symmetric p x p matrix H (both triangles are read) by cyclic
+ *   Jacobi in one workgroup, at most 30 sweeps: values[DWN_MODES_MAXP] descending (zero beyond p), column c of W the eigenvector
+ *   of values[c] with its entry of largest magnitude (lowest index on ties) positive.  A non-finite H gives NaN values and NaN W.
+ * dwn_modes_ritz: needs Q, Y, values (theta, as small_eigh wrote them), W, V, residuals, status, ws (dwn_modes_ritz_ws_bytes).
+ *   V = Q W, residuals[c] = ||Y W e_c - theta_c V e_c||_2, then status[0] (done) = status[1] (converged) = 1 when
+ *   max_{i < k} residuals[i] <= tol * |theta_0|; status[2] (rounds) = 1.  status is int32 [4].
+ * dwn_modes_solve: needs A, V, values, residuals, moments, status, ws (dwn_modes_solve_ws_bytes).  The start block (entry (i, c) =
+ *   ((double) w + 0.5) * 2^-31 - 1 with w word c & 3 of philox4x32-10(counter = (i, c >> 2, 0, 0), key = (seed & 0xffffffff, seed
+ *   >> 32))), its orth, the moments, Q = orth(scale A Q) once, then max_iters rounds of symm, H = sym(Q^T Y), small_eigh, ritz, Q = orth(Y) on one stream;
+ *   the decision is taken on the device and the kernels of the rounds after it return at once: nothing is read back.  At the
+ *   end the sign rule is applied to the columns of V.  A NaN or Inf in A gives NaN values and converged = 0.
+ * dwn_modes_overlap: needs Q (Va), Y (Vb), k, values, ws (dwn_modes_overlap_ws_bytes); values[k] = the singular values of Va^T Vb,
+ *   descending, as the square roots of the eigenvalues of (Va^T Vb)^T (Va^T Vb).  With A (B of the comparison) also moments:
+ *   [0], [1] as dwn_modes_moments of B and moments[2] = tr(Va^T (scale B) Va).
+ *
+ * Errors, answered before the device is entered: -1 null pointer; -2 N outside [1, 65535], p outside [1, min(N, DWN_MODES_MAXP)], k
+ * outside [1, p], a leading dimension too small, max_iters < 1, scale or tol not finite, tol < 0, misaligned pointer; -3 workspace
+ * too small or not 16-byte aligned.  The size queries return 0 for what the entries refuse. */
+#define DWN_MODES_MAXP 64
+#define DWN_MODES_ORTH_C 8.0
+typedef struct dwn_modes_args {
+    int N, p, k, max_iters;           /* p: columns of the block, k <= p: the columns the decision looks at */
+    long long lda, ldq, ldy, ldv;
+    double scale, tol;
+    unsigned long long seed;
+    const double* A;
+    double* Q;
+    double* Y;
+    double* V;
+    double* H;
+    double* W;
+    double* values;                   /* [DWN_MODES_MAXP] */
+    double* residuals;                /* [DWN_MODES_MAXP] */
+    double* moments;                  /* [4]: trace, squared Frobenius norm, (overlap) captured numerator, unused */
+    int* status;                      /* [4]: done, converged, rounds, unused */
+    void* ws;
+    size_t ws_bytes;
+} dwn_modes_args;
+size_t dwn_modes_moments_ws_bytes(const dwn_modes_args* a);
+size_t dwn_modes_ritz_ws_bytes(const dwn_modes_args* a);
+size_t dwn_modes_solve_ws_bytes(const dwn_modes_args* a);
+size_t dwn_modes_overlap_ws_bytes(const dwn_modes_args* a);
+int dwn_modes_symm(const dwn_modes_args* a, int device, void* stream);
+int dwn_modes_moments(const dwn_modes_args* a, int device, void* stream);
+int dwn_modes_orth(const dwn_modes_args* a, int device, void* stream);
+int dwn_modes_small_eigh(const dwn_modes_args* a, int device, void* stream);
+int dwn_modes_ritz(const dwn_modes_args* a, int device, void* stream);
+int dwn_modes_solve(const dwn_modes_args* a, int device, void* stream);
+int dwn_modes_overlap(const dwn_modes_args* a, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

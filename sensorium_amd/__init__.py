@@ -17,9 +17,10 @@ from .receptive_fields import GAUSS_FIT_COLUMNS, GaussianFits, ReceptiveFields, 
 from .evaluation import FrameCut, TrialScorer, evaluate_trials  # noqa: F401
 from . import population  # noqa: F401
 from .population import CorrelationMatrices, PairwiseComparison, PairwiseCorrelation, population_structure  # noqa: F401
+from .population import ModesComparison, PopulationModes, compare_modes  # noqa: F401
 
 __all__ = ["DwiseNeuro", "DwiseNeuroGaze", "GazeShifter", "DwiseNeuroBehavior", "BehaviorModulator", "DwiseNeuroSpatial", "SpatialGain", "MicePoissonLoss", "MiceCorrelationLoss", "MicePoissonCorrelationLoss",
            "DriftingGabor", "PARAM_NAMES", "tuning_curve", "optimal_gabor", "FrameCut", "TrialScorer", "evaluate_trials",
            "NoiseStimulus", "receptive_fields", "StaAccumulator", "ReceptiveFields",
            "GaussianFits", "GAUSS_FIT_COLUMNS", "fit_gaussian2d", "population", "PairwiseCorrelation", "CorrelationMatrices",
-           "PairwiseComparison", "population_structure"]
+           "PairwiseComparison", "population_structure", "PopulationModes", "ModesComparison", "compare_modes"]

@@ -256,6 +256,12 @@ class PairCompareArgs(C.Structure):       # (include/dwn.h dwn_pair_compare_args
                 ("per_neuron", c_p), ("summary", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
 
 
+class ModesArgs(C.Structure):             # population modes (include/dwn.h dwn_modes_args)
+    _fields_ = [("N", c_i), ("p", c_i), ("k", c_i), ("max_iters", c_i), ("lda", c_ll), ("ldq", c_ll), ("ldy", c_ll), ("ldv", c_ll),
+                ("scale", c_d), ("tol", c_d), ("seed", C.c_ulonglong), ("A", c_p), ("Q", c_p), ("Y", c_p), ("V", c_p), ("H", c_p),
+                ("W", c_p), ("values", c_p), ("residuals", c_p), ("moments", c_p), ("status", c_p), ("ws", c_p), ("ws_bytes", c_sz)]
+
+
 class SpatialGainArgs(C.Structure):       # retinotopic readout gain (include/dwn.h dwn_spatial_gain_args)
     _fields_ = [("B", c_i), ("N", c_i), ("T", c_i), ("Hf", c_i), ("Wf", c_i), ("K", c_i), ("g_dtype", c_i), ("max_log_gain", c_f),
                 ("y", c_p), ("g", c_p), ("pos", c_p), ("weight", c_p), ("bias", c_p), ("out", c_p), ("dout", c_p), ("dy", c_p),
@@ -299,6 +305,7 @@ STA_SUMMARY = 8                            # DWN_STA_SUMMARY
 GAUSS_PARAMS, GAUSS_TABLE = 7, 16          # DWN_GAUSS_*
 PAIR_TOTAL, PAIR_SIGNAL, PAIR_NOISE = 0, 1, 2                  # DWN_PAIR_*
 PAIR_TILE, PAIR_KSTEP, PAIR_SUMMARY, PAIR_ROW_STATS = 64, 4, 8, 8
+MODES_MAXP, MODES_ORTH_C = 64, 8.0                             # DWN_MODES_*
 MIX_BOX, MIX_BLEND = 0, 1
 VID_U8, VID_F32 = 0, 1
 
@@ -322,6 +329,7 @@ _NEW_STRUCTS = {
     "dwn_spatial_gain_args": SpatialGainArgs, "dwn_noise_args": NoiseArgs, "dwn_sta_args": StaArgs,
     "dwn_gauss2d_args": Gauss2dArgs, "dwn_gauss2d_profile_args": Gauss2dProfileArgs,
     "dwn_pair_seg": PairSeg, "dwn_pair_args": PairArgs, "dwn_pair_compare_args": PairCompareArgs,
+    "dwn_modes_args": ModesArgs,
 }
 _STRUCTS = {**_OLD_STRUCTS, **_NEW_STRUCTS}
 
@@ -426,6 +434,18 @@ SYMBOLS = {
     "dwn_pair_syrk": _new(c_i, [_P(PairArgs), c_i, c_p]),
     "dwn_pair_corr_finalize": _new(c_i, [_P(PairArgs), c_i, c_p]),
     "dwn_pair_compare": _new(c_i, [_P(PairCompareArgs), c_i, c_p]),
+    # (the population modes of dwn_modes.hip)
+    "dwn_modes_moments_ws_bytes": _new(c_sz, [_P(ModesArgs)]),
+    "dwn_modes_ritz_ws_bytes": _new(c_sz, [_P(ModesArgs)]),
+    "dwn_modes_solve_ws_bytes": _new(c_sz, [_P(ModesArgs)]),
+    "dwn_modes_overlap_ws_bytes": _new(c_sz, [_P(ModesArgs)]),
+    "dwn_modes_symm": _new(c_i, [_P(ModesArgs), c_i, c_p]),
+    "dwn_modes_moments": _new(c_i, [_P(ModesArgs), c_i, c_p]),
+    "dwn_modes_orth": _new(c_i, [_P(ModesArgs), c_i, c_p]),
+    "dwn_modes_small_eigh": _new(c_i, [_P(ModesArgs), c_i, c_p]),
+    "dwn_modes_ritz": _new(c_i, [_P(ModesArgs), c_i, c_p]),
+    "dwn_modes_solve": _new(c_i, [_P(ModesArgs), c_i, c_p]),
+    "dwn_modes_overlap": _new(c_i, [_P(ModesArgs), c_i, c_p]),
     # (the parametric fits of dwn_rf_fit.hip; tests/test_host_rf.py keeps the five receptive-field entries last)
     "dwn_gauss2d_ws_bytes": _new(c_sz, [_P(Gauss2dArgs)]),
     "dwn_gauss2d_fit": _new(c_i, [_P(Gauss2dArgs), c_i, c_p]),
@@ -445,8 +465,8 @@ class DwnError(RuntimeError):
 # csrc/Makefile HASH_SRCS, in its order
 HASH_SRCS = ("dwn_api.hip", "dwn_gemm.hip", "dwn_gemm_nn_1.hip", "dwn_gemm_nn_2.hip", "dwn_gemm_nn_3.hip", "dwn_gemm_nn_4.hip", "dwn_gemm_nn_5.hip",
              "dwn_gemm_nn_6.hip", "dwn_gemm_tn.hip", "dwn_gram.hip", "dwn_pw_bwd.hip", "dwn_gemm_xl.hip", "dwn_gemm_kd.hip", "dwn_dwconv.hip", "dwn_dwrc.hip",
-             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_spatial.hip", "dwn_mei.hip", "dwn_rf_fit.hip", "dwn_pairwise.hip", "dwn_trial_score.hip", "dwn_rf.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
-             "dwn_kernels.h", "dwn_launch.h", "dwn_gemm_nn.h", "dwn_gain.h", "dwn_reduce.h",
+             "dwn_dwbwd.hip", "dwn_dwfwd.hip", "dwn_elementwise.hip", "dwn_data.hip", "dwn_gaze.hip", "dwn_modulator.hip", "dwn_spatial.hip", "dwn_mei.hip", "dwn_rf_fit.hip", "dwn_pairwise.hip", "dwn_modes.hip", "dwn_trial_score.hip", "dwn_rf.hip", "dwn_corr.hip", "dwn_stim.hip", "dwn_common.h", "dwn_internal.h",
+             "dwn_kernels.h", "dwn_launch.h", "dwn_gemm_nn.h", "dwn_gain.h", "dwn_reduce.h", "dwn_philox.h",
              "../../include/dwn.h")
 
 

@@ -350,7 +350,7 @@ int dwn_sizeof(const char* name) {
     SZ(dwn_blur3d_args); SZ(dwn_clip_moments_args); SZ(dwn_mei_update_args);
     SZ(dwn_trial_desc); SZ(dwn_trial_group); SZ(dwn_trial_score_args);
     SZ(dwn_noise_args); SZ(dwn_sta_args); SZ(dwn_gauss2d_args); SZ(dwn_gauss2d_profile_args);
-    SZ(dwn_pair_seg); SZ(dwn_pair_args); SZ(dwn_pair_compare_args);
+    SZ(dwn_pair_seg); SZ(dwn_pair_args); SZ(dwn_pair_compare_args); SZ(dwn_modes_args);
 #undef SZ
     return -1;
 }
@@ -1524,6 +1524,111 @@ int dwn_pair_compare(const dwn_pair_compare_args* a, int device, void* stream) {
     WS_CHECK(a, -3, "pair_compare", k_pair_compare_ws_bytes(a->M), "dwn_pair_compare_ws_bytes", 8);
     ENTER(device);
     return k_pair_compare(*a, (hipStream_t)stream);
+}
+
+// ---- population modes: the argument checks need no device
+enum { MO_A = 1, MO_Q = 2, MO_Y = 4, MO_V = 8, MO_K = 16 };
+static int pad16i(int p) { return (p + 15) / 16 * 16; }
+static const char* modes_geometry(const dwn_modes_args* a, int parts) {
+    if (a->N <= 0 || a->N > 65535) return "N outside [1, 65535]";
+    if (a->p < 1 || a->p > DWN_MODES_MAXP || a->p > a->N) return "p outside [1, min(N, DWN_MODES_MAXP)]";
+    if ((parts & MO_K) && (a->k < 1 || a->k > a->p)) return "k outside [1, p]";
+    if ((parts & MO_A) && a->lda < a->N) return "lda below N";
+    if ((parts & MO_A) && !(fabs(a->scale) <= 1.7976931348623157e308)) return "scale is not finite";
+    if ((parts & MO_Q) && a->ldq < pad16i(a->p)) return "ldq below p rounded up to 16";
+    if ((parts & MO_Y) && a->ldy < pad16i(a->p)) return "ldy below p rounded up to 16";
+    if ((parts & MO_V) && a->ldv < pad16i(a->p)) return "ldv below p rounded up to 16";
+    return nullptr;
+}
+static int modes_check(const dwn_modes_args* a, int parts, const char* who) {
+    static char msg[128];
+    const char* what = modes_geometry(a, parts);
+    if (!what) return 0;
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return dwn_set_error(-2, msg);
+}
+static bool modes_aligned(const dwn_modes_args* a) {
+    return !(((size_t)a->A | (size_t)a->Q | (size_t)a->Y | (size_t)a->V | (size_t)a->H | (size_t)a->W | (size_t)a->values |
+              (size_t)a->residuals | (size_t)a->moments) & 7) && !((size_t)a->status & 3);
+}
+size_t dwn_modes_moments_ws_bytes(const dwn_modes_args* a) { return a && a->N > 0 && a->N <= 65535 ? k_modes_moments_ws_bytes(a->N) : 0; }
+size_t dwn_modes_ritz_ws_bytes(const dwn_modes_args* a) { return a && a->N > 0 && a->N <= 65535 ? k_modes_ritz_ws_bytes(a->N) : 0; }
+size_t dwn_modes_solve_ws_bytes(const dwn_modes_args* a) { return a && !modes_geometry(a, 0) ? k_modes_solve_ws_bytes(a->N, a->p) : 0; }
+size_t dwn_modes_overlap_ws_bytes(const dwn_modes_args* a) {
+    if (!a || a->N <= 0 || a->N > 65535 || a->k < 1 || a->k > DWN_MODES_MAXP || a->k > a->N) return 0;
+    return k_modes_overlap_ws_bytes(a->N, a->k, a->A != nullptr);
+}
+int dwn_modes_symm(const dwn_modes_args* a, int device, void* stream) {
+    ARGS(a, "modes_symm");
+    TRY(modes_check(a, MO_A | MO_Q | MO_Y, "modes_symm"));
+    if (!a->A || !a->Q || !a->Y) return dwn_set_error(-1, "modes_symm: null pointer (A, Q, Y)");
+    if (!modes_aligned(a)) return dwn_set_error(-2, "modes_symm: misaligned pointer");
+    ENTER(device);
+    return k_modes_symm(*a, (hipStream_t)stream);
+}
+int dwn_modes_moments(const dwn_modes_args* a, int device, void* stream) {
+    ARGS(a, "modes_moments");
+    if (a->N <= 0 || a->N > 65535) return dwn_set_error(-2, "modes_moments: N outside [1, 65535]");
+    if (a->lda < a->N) return dwn_set_error(-2, "modes_moments: lda below N");
+    if (!(fabs(a->scale) <= 1.7976931348623157e308)) return dwn_set_error(-2, "modes_moments: scale is not finite");
+    if (!a->A || !a->moments || !a->ws) return dwn_set_error(-1, "modes_moments: null pointer (A, moments, ws)");
+    if (!modes_aligned(a)) return dwn_set_error(-2, "modes_moments: misaligned pointer");
+    WS_CHECK(a, -3, "modes_moments", k_modes_moments_ws_bytes(a->N), "dwn_modes_moments_ws_bytes", 16);
+    ENTER(device);
+    return k_modes_moments(*a, (hipStream_t)stream);
+}
+int dwn_modes_orth(const dwn_modes_args* a, int device, void* stream) {
+    ARGS(a, "modes_orth");
+    TRY(modes_check(a, MO_Q | MO_Y, "modes_orth"));
+    if (!a->Q || !a->Y) return dwn_set_error(-1, "modes_orth: null pointer (Q, Y)");
+    if (!modes_aligned(a)) return dwn_set_error(-2, "modes_orth: misaligned pointer");
+    ENTER(device);
+    return k_modes_orth(*a, (hipStream_t)stream);
+}
+int dwn_modes_small_eigh(const dwn_modes_args* a, int device, void* stream) {
+    ARGS(a, "modes_small_eigh");
+    if (a->p < 1 || a->p > DWN_MODES_MAXP) return dwn_set_error(-2, "modes_small_eigh: p outside [1, DWN_MODES_MAXP]");
+    if (!a->H || !a->W || !a->values) return dwn_set_error(-1, "modes_small_eigh: null pointer (H, W, values)");
+    if (!modes_aligned(a)) return dwn_set_error(-2, "modes_small_eigh: misaligned pointer");
+    ENTER(device);
+    return k_modes_small_eigh(*a, (hipStream_t)stream);
+}
+int dwn_modes_ritz(const dwn_modes_args* a, int device, void* stream) {
+    ARGS(a, "modes_ritz");
+    TRY(modes_check(a, MO_Q | MO_Y | MO_V | MO_K, "modes_ritz"));
+    if (!(a->tol >= 0.0) || !(a->tol <= 1.7976931348623157e308)) return dwn_set_error(-2, "modes_ritz: tol must be finite and not negative");
+    if (!a->Q || !a->Y || !a->V || !a->W || !a->values || !a->residuals || !a->status || !a->ws)
+        return dwn_set_error(-1, "modes_ritz: null pointer (Q, Y, V, W, values, residuals, status, ws)");
+    if (!modes_aligned(a)) return dwn_set_error(-2, "modes_ritz: misaligned pointer");
+    WS_CHECK(a, -3, "modes_ritz", k_modes_ritz_ws_bytes(a->N), "dwn_modes_ritz_ws_bytes", 16);
+    ENTER(device);
+    return k_modes_ritz(*a, (hipStream_t)stream);
+}
+int dwn_modes_solve(const dwn_modes_args* a, int device, void* stream) {
+    ARGS(a, "modes_solve");
+    TRY(modes_check(a, MO_A | MO_V | MO_K, "modes_solve"));
+    if (a->max_iters < 1 || a->max_iters > 4096) return dwn_set_error(-2, "modes_solve: max_iters outside [1, 4096]");
+    if (!(a->tol >= 0.0) || !(a->tol <= 1.7976931348623157e308)) return dwn_set_error(-2, "modes_solve: tol must be finite and not negative");
+    if (!a->A || !a->V || !a->values || !a->residuals || !a->moments || !a->status || !a->ws)
+        return dwn_set_error(-1, "modes_solve: null pointer (A, V, values, residuals, moments, status, ws)");
+    if (!modes_aligned(a)) return dwn_set_error(-2, "modes_solve: misaligned pointer");
+    WS_CHECK(a, -3, "modes_solve", k_modes_solve_ws_bytes(a->N, a->p), "dwn_modes_solve_ws_bytes", 16);
+    ENTER(device);
+    return k_modes_solve(*a, (hipStream_t)stream);
+}
+int dwn_modes_overlap(const dwn_modes_args* a, int device, void* stream) {
+    ARGS(a, "modes_overlap");
+    if (a->N <= 0 || a->N > 65535) return dwn_set_error(-2, "modes_overlap: N outside [1, 65535]");
+    if (a->k < 1 || a->k > DWN_MODES_MAXP || a->k > a->N) return dwn_set_error(-2, "modes_overlap: k outside [1, min(N, DWN_MODES_MAXP)]");
+    if (a->ldq < pad16i(a->k) || a->ldy < pad16i(a->k)) return dwn_set_error(-2, "modes_overlap: a leading dimension below k rounded up to 16");
+    if (a->A && a->lda < a->N) return dwn_set_error(-2, "modes_overlap: lda below N");
+    if (a->A && !(fabs(a->scale) <= 1.7976931348623157e308)) return dwn_set_error(-2, "modes_overlap: scale is not finite");
+    if (!a->Q || !a->Y || !a->values || !a->ws || (a->A && !a->moments))
+        return dwn_set_error(-1, "modes_overlap: null pointer (Q, Y, values, ws; moments with A)");
+    if (!modes_aligned(a)) return dwn_set_error(-2, "modes_overlap: misaligned pointer");
+    WS_CHECK(a, -3, "modes_overlap", k_modes_overlap_ws_bytes(a->N, a->k, a->A != nullptr), "dwn_modes_overlap_ws_bytes", 16);
+    ENTER(device);
+    return k_modes_overlap(*a, (hipStream_t)stream);
 }
 
 // ---- retinotopic readout gain: the argument checks need no device

@@ -171,6 +171,18 @@ int k_pair_stage(const dwn_pair_args& a, hipStream_t s);                      //
 int k_pair_syrk(const dwn_pair_args& a, hipStream_t s);                       // C += Z Z^T
 int k_pair_corr_finalize(const dwn_pair_args& a, hipStream_t s);
 int k_pair_compare(const dwn_pair_compare_args& a, hipStream_t s);            // row moments into a.ws, then the one-workgroup merge
+// population modes (dwn.h dwn_modes_args; dwn_modes.hip): arguments checked by the C-ABI layer
+size_t k_modes_moments_ws_bytes(int N);
+size_t k_modes_ritz_ws_bytes(int N);
+size_t k_modes_solve_ws_bytes(int N, int p);
+size_t k_modes_overlap_ws_bytes(int N, int k, int with_matrix);
+int k_modes_symm(const dwn_modes_args& a, hipStream_t s);                     // Y = scale A Q
+int k_modes_moments(const dwn_modes_args& a, hipStream_t s);
+int k_modes_orth(const dwn_modes_args& a, hipStream_t s);
+int k_modes_small_eigh(const dwn_modes_args& a, hipStream_t s);
+int k_modes_ritz(const dwn_modes_args& a, hipStream_t s);                     // clears status, rotates, decides
+int k_modes_solve(const dwn_modes_args& a, hipStream_t s);
+int k_modes_overlap(const dwn_modes_args& a, hipStream_t s);
 int k_pw_bwd_prep(const float* w1, const float* abc, int E, int C, void* bp, float* gacc, float* r3, int dtype,
                   const float* res_abc, int res_C, hipStream_t s);
 // conv_pw weight gradient from the raw products (see pw_bwd_fused_kernel): tacc [(E + C + 8)][C] fp32 = rows T1 = dh1^T a0,

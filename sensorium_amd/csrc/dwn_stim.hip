@@ -15,6 +15,7 @@
 #include "dwn_internal.h"
 #include "dwn_kernels.h"
 #include "dwn_launch.h"
+#include "dwn_philox.h"
 #include "dwn_reduce.h"
 
 namespace {
@@ -238,17 +239,6 @@ struct NoiseGeom {
     float v_lo, v_mid, v_hi, pad;              // background - contrast, background, background + contrast: formed once on the host
     unsigned k0, k1, thr, clip0;               // key, floor(density 2^31), first clip number
 };
-
-__device__ __forceinline__ unsigned philox_word(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, int word) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return word == 0 ? c0 : word == 1 ? c1 : word == 2 ? c2 : c3;
-}
 
 __global__ __launch_bounds__(GB_NT) void noise_stream_kernel(const float* __restrict__ in, float* __restrict__ out, i64 planes, int Cin,
                                                              int T, int H, int W, int vc, NoiseGeom gm, int vec) {

@@ -1341,6 +1341,174 @@ def pair_compare(A: torch.Tensor, B: torch.Tensor, sel: Optional[torch.Tensor] =
 
 
 # ------------------------------------------------------------------------------------------------
+# population modes (sensorium_amd/population.py)
+# ------------------------------------------------------------------------------------------------
+def modes_pad(p: int) -> int:
+    """The columns a block of ``p`` columns is stored with: ``p`` rounded up to the MFMA tile width."""
+    return -(-int(p) // 16) * 16
+
+
+def _modes_matrix(A: torch.Tensor, what: str):
+    _require_gpu(A, what)
+    if A.dtype != torch.float64:
+        raise RuntimeError(f"sensorium_amd.{what}: the matrix must be float64 (got {A.dtype})")
+    if A.dim() != 2 or A.shape[0] != A.shape[1] or A.shape[0] < 1:
+        raise ValueError(f"sensorium_amd.{what}: the matrix must be square [N, N], got {tuple(A.shape)}")
+    if (A.shape[1] > 1 and A.stride(1) != 1) or (A.shape[0] > 1 and A.stride(0) < A.shape[1]):
+        raise ValueError(f"sensorium_amd.{what}: rows must have unit stride and must not overlap")
+    return A.device, int(A.shape[0])
+
+
+def _modes_block(X: torch.Tensor, N: int, dev, what: str, name: str) -> int:
+    """A block ``[N, >= p]`` float64 whose row stride is at least the padded width; returns its row stride."""
+    _require_gpu(X, what)
+    if X.dtype != torch.float64 or X.dim() != 2 or X.shape[0] != N or X.device != dev:
+        raise ValueError(f"sensorium_amd.{what}: {name} must be a float64 [N = {N}, p] tensor on {dev}")
+    if X.shape[1] > 1 and X.stride(1) != 1:
+        raise ValueError(f"sensorium_amd.{what}: {name} must have unit stride along its columns")
+    return int(X.stride(0)) if N > 1 else max(int(X.stride(0)), modes_pad(X.shape[1]))
+
+
+def modes_block(N: int, p: int, dev) -> torch.Tensor:
+    """A zeroed block of ``p`` columns: the ``[N, p]`` view of a ``[N, modes_pad(p)]`` tensor."""
+    return torch.zeros(N, modes_pad(p), dtype=torch.float64, device=dev)[:, :p]
+
+
+def _modes_args(N: int, p: int, k: int = 0) -> "L.ModesArgs":
+    a = L.ModesArgs()
+    a.N, a.p, a.k, a.scale = N, p, k, 1.0
+    return a
+
+
+def _modes_ws(a, query, dev) -> torch.Tensor:
+    ws = torch.empty(max(int(query(C.byref(a))) // 8, 2), dtype=torch.float64, device=dev)
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 8
+    return ws
+
+
+def modes_symm(A: torch.Tensor, Q: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """dwn_modes_symm: ``scale * A @ Q`` for a symmetric float64 ``[N, N]`` matrix (any row stride ``>= N``) and a block ``Q``
+    (``modes_block``), as a new block."""
+    dev, N = _modes_matrix(A, "modes_symm")
+    ldq = _modes_block(Q, N, dev, "modes_symm", "Q")
+    p = int(Q.shape[1])
+    Y = modes_block(N, p, dev)
+    a = _modes_args(N, p)
+    a.lda, a.ldq, a.ldy, a.scale = int(A.stride(0)) if N > 1 else max(int(A.stride(0)), 1), ldq, modes_pad(p), float(scale)
+    a.A, a.Q, a.Y = A.data_ptr(), Q.data_ptr(), Y.data_ptr()
+    L.check(L.lib.dwn_modes_symm(C.byref(a), dev.index, _stream(dev)), "dwn_modes_symm")
+    return Y
+
+
+def modes_moments(A: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """dwn_modes_moments: float64 ``[2]`` device tensor, the trace and the squared Frobenius norm of ``scale * A``."""
+    dev, N = _modes_matrix(A, "modes_moments")
+    out = torch.zeros(4, dtype=torch.float64, device=dev)
+    a = _modes_args(N, 1)
+    a.lda, a.scale, a.A, a.moments = (int(A.stride(0)) if N > 1 else max(int(A.stride(0)), 1)), float(scale), A.data_ptr(), out.data_ptr()
+    ws = _modes_ws(a, L.lib.dwn_modes_moments_ws_bytes, dev)       # noqa: F841  (alive until the launch is enqueued)
+    L.check(L.lib.dwn_modes_moments(C.byref(a), dev.index, _stream(dev)), "dwn_modes_moments")
+    return out[:2]
+
+
+def modes_orth(Y: torch.Tensor) -> torch.Tensor:
+    """dwn_modes_orth: an orthonormal basis of the columns of the block ``Y`` (a dependent column becomes an exact zero
+    column), as a new block."""
+    _require_gpu(Y, "modes_orth")
+    dev, N = Y.device, int(Y.shape[0])
+    ldy = _modes_block(Y, N, dev, "modes_orth", "Y")
+    p = int(Y.shape[1])
+    Q = modes_block(N, p, dev)
+    a = _modes_args(N, p)
+    a.ldq, a.ldy, a.Q, a.Y = modes_pad(p), ldy, Q.data_ptr(), Y.data_ptr()
+    L.check(L.lib.dwn_modes_orth(C.byref(a), dev.index, _stream(dev)), "dwn_modes_orth")
+    return Q
+
+
+def modes_small_eigh(H: torch.Tensor):
+    """dwn_modes_small_eigh: ``(values [p] descending, W [p, p])`` of a symmetric float64 ``[p, p]`` device matrix, ``p <= 64``."""
+    _require_gpu(H, "modes_small_eigh")
+    if H.dtype != torch.float64 or H.dim() != 2 or H.shape[0] != H.shape[1]:
+        raise ValueError("sensorium_amd.modes_small_eigh: H must be a float64 [p, p] matrix")
+    p, dev = int(H.shape[0]), H.device
+    Hp = torch.zeros(max(p, 1), L.MODES_MAXP, dtype=torch.float64, device=dev)
+    if 1 <= p <= L.MODES_MAXP:
+        Hp[:, :p] = H
+    W = torch.zeros_like(Hp)
+    values = torch.zeros(L.MODES_MAXP, dtype=torch.float64, device=dev)
+    a = _modes_args(1, p)
+    a.H, a.W, a.values = Hp.data_ptr(), W.data_ptr(), values.data_ptr()
+    L.check(L.lib.dwn_modes_small_eigh(C.byref(a), dev.index, _stream(dev)), "dwn_modes_small_eigh")
+    return values[:p], W[:, :p]
+
+
+def modes_ritz(Q: torch.Tensor, Y: torch.Tensor, theta: torch.Tensor, W: torch.Tensor, k: int, tol: float):
+    """dwn_modes_ritz: ``(V, residuals [p], status int32 [4] = done, converged, rounds, 0)`` for the blocks ``Q`` and ``Y = A Q``
+    and the eigenpairs ``theta [p]``, ``W [p, p]`` of ``Q^T Y``."""
+    _require_gpu(Q, "modes_ritz")
+    dev, N, p = Q.device, int(Q.shape[0]), int(Q.shape[1])
+    ldq, ldy = _modes_block(Q, N, dev, "modes_ritz", "Q"), _modes_block(Y, N, dev, "modes_ritz", "Y")
+    if Y.shape != Q.shape or tuple(theta.shape) != (p,) or tuple(W.shape) != (p, p):
+        raise ValueError("sensorium_amd.modes_ritz: Q and Y [N, p], theta [p], W [p, p]")
+    Wp = torch.zeros(p, L.MODES_MAXP, dtype=torch.float64, device=dev)
+    Wp[:, :p] = W
+    values = torch.zeros(L.MODES_MAXP, dtype=torch.float64, device=dev)
+    values[:p] = theta
+    residuals = torch.zeros(L.MODES_MAXP, dtype=torch.float64, device=dev)
+    status = torch.zeros(4, dtype=torch.int32, device=dev)
+    V = modes_block(N, p, dev)
+    a = _modes_args(N, p, int(k))
+    a.ldq, a.ldy, a.ldv, a.tol = ldq, ldy, modes_pad(p), float(tol)
+    a.Q, a.Y, a.V, a.W, a.values, a.residuals, a.status = (Q.data_ptr(), Y.data_ptr(), V.data_ptr(), Wp.data_ptr(), values.data_ptr(),
+                                                           residuals.data_ptr(), status.data_ptr())
+    ws = _modes_ws(a, L.lib.dwn_modes_ritz_ws_bytes, dev)          # noqa: F841
+    L.check(L.lib.dwn_modes_ritz(C.byref(a), dev.index, _stream(dev)), "dwn_modes_ritz")
+    return V, residuals[:p], status
+
+
+def modes_solve(A: torch.Tensor, k: int, p: int, max_iters: int = 64, tol: float = 1e-10, seed: int = 0, scale: float = 1.0):
+    """dwn_modes_solve: block subspace iteration on ``scale * A`` with a block of ``p`` columns, stopping on the first ``k``.
+    Returns ``(values [p], V [N, p], residuals [p], moments [2], status int32 [4])``, all on the device; nothing is read back."""
+    dev, N = _modes_matrix(A, "modes_solve")
+    k, p = int(k), int(p)
+    V = modes_block(N, max(p, 1), dev)
+    values = torch.zeros(L.MODES_MAXP, dtype=torch.float64, device=dev)
+    residuals = torch.zeros(L.MODES_MAXP, dtype=torch.float64, device=dev)
+    moments = torch.zeros(4, dtype=torch.float64, device=dev)
+    status = torch.zeros(4, dtype=torch.int32, device=dev)
+    a = _modes_args(N, p, k)
+    a.max_iters, a.tol, a.seed, a.scale = int(max_iters), float(tol), int(seed) & (2 ** 64 - 1), float(scale)
+    a.lda, a.ldv = (int(A.stride(0)) if N > 1 else max(int(A.stride(0)), 1)), modes_pad(max(p, 1))
+    a.A, a.V, a.values, a.residuals, a.moments, a.status = (A.data_ptr(), V.data_ptr(), values.data_ptr(), residuals.data_ptr(),
+                                                            moments.data_ptr(), status.data_ptr())
+    ws = _modes_ws(a, L.lib.dwn_modes_solve_ws_bytes, dev)         # noqa: F841
+    L.check(L.lib.dwn_modes_solve(C.byref(a), dev.index, _stream(dev)), "dwn_modes_solve")
+    return values[:p], V, residuals[:p], moments[:2], status
+
+
+def modes_overlap(Va: torch.Tensor, Vb: torch.Tensor, B: Optional[torch.Tensor] = None, scale: float = 1.0):
+    """dwn_modes_overlap: the singular values ``[k]`` of ``Va^T Vb`` (descending) for two blocks of ``k`` columns, and with ``B``
+    also ``moments [3]`` = trace and squared Frobenius norm of ``scale * B`` and ``tr(Va^T (scale B) Va)``; else ``None``."""
+    _require_gpu(Va, "modes_overlap")
+    dev, N, k = Va.device, int(Va.shape[0]), int(Va.shape[1])
+    lda_, ldb_ = _modes_block(Va, N, dev, "modes_overlap", "Va"), _modes_block(Vb, N, dev, "modes_overlap", "Vb")
+    if Vb.shape != Va.shape:
+        raise ValueError("sensorium_amd.modes_overlap: Va and Vb must have one shape")
+    values = torch.zeros(L.MODES_MAXP, dtype=torch.float64, device=dev)
+    moments = torch.zeros(4, dtype=torch.float64, device=dev)
+    a = _modes_args(N, k, k)
+    a.ldq, a.ldy, a.Q, a.Y, a.values, a.moments, a.scale = lda_, ldb_, Va.data_ptr(), Vb.data_ptr(), values.data_ptr(), moments.data_ptr(), float(scale)
+    if B is not None:
+        devb, Nb = _modes_matrix(B, "modes_overlap")
+        if Nb != N or devb != dev:
+            raise ValueError("sensorium_amd.modes_overlap: B must be [N, N] on the device of the blocks")
+        a.A, a.lda = B.data_ptr(), (int(B.stride(0)) if N > 1 else max(int(B.stride(0)), 1))
+    ws = _modes_ws(a, L.lib.dwn_modes_overlap_ws_bytes, dev)       # noqa: F841
+    L.check(L.lib.dwn_modes_overlap(C.byref(a), dev.index, _stream(dev)), "dwn_modes_overlap")
+    return values[:k], (moments[:3] if B is not None else None)
+
+
+# ------------------------------------------------------------------------------------------------
 # retinotopic readout gain (DESIGN.md 12p; sensorium_amd/spatial.py)
 # ------------------------------------------------------------------------------------------------
 def _spatial_gain_args(y, g, pos, weight, bias, max_log_gain: float) -> L.SpatialGainArgs:

@@ -38,6 +38,19 @@ class CorrelationMatrices:
     def mean(self, kind: str) -> torch.Tensor:
         return self._states[kind][-1]
 
+    def modes(self, kind: str, of: str = "correlation", **kw) -> "PopulationModes":
+        """The leading modes (``modes``) of the correlation matrix of ``kind`` or, ``of="covariance"``, of its co-moments scaled
+        by ``1 / counts[kind]``.  Keywords as ``modes`` (``k`` is required)."""
+        if kind not in KINDS or kind not in self._states:
+            raise ValueError(f"CorrelationMatrices.modes: kind must be one of {tuple(self._states)}, got {kind!r}")
+        if of == "correlation":
+            return modes(getattr(self, kind), **kw)
+        if of != "covariance":
+            raise ValueError(f"CorrelationMatrices.modes: of must be 'correlation' or 'covariance', got {of!r}")
+        if self.counts[kind] < 1:
+            raise ValueError(f"CorrelationMatrices.modes: no sample of kind {kind!r}")
+        return modes(self.comoments(kind), scale=1.0 / self.counts[kind], **kw)
+
 
 class PairwiseCorrelation:
     """Accumulates the responses of ONE mouse into one co-moment state per kind.  ``add`` keeps references to device tensors,
@@ -204,3 +217,93 @@ def population_structure(predictor, trials: Iterable, mouse_index: int, *, cut: 
         raise ValueError("population_structure: no trials")
     model, data = model_acc.compute(), data_acc.compute()
     return model, data, {k: compare(getattr(model, k), getattr(data, k)) for k in model_acc.kinds}
+
+
+MODES_SUMMARY_NAMES = ("k", "rounds", "converged", "trace", "participation_ratio", "leading_explained", "worst_relative_residual")
+
+
+class PopulationModes:
+    """The ``k`` leading eigenpairs of a symmetric matrix (``modes``), device tensors only: ``.values`` ``[k]`` descending,
+    ``.vectors`` ``[N, k]`` with orthonormal columns (the entry of largest magnitude of a column, lowest index on ties, is
+    positive; the mode of a rank the matrix does not have is an exact zero column with value 0), ``.residuals`` ``[k]`` =
+    ``||A v - theta v||_2``, ``.trace`` and ``.frobenius2`` (0-d), ``.converged`` (0-d bool), ``.rounds`` (0-d int32)."""
+
+    def __init__(self, values, vectors, residuals, moments, status):
+        self.values, self.vectors, self.residuals = values, vectors, residuals
+        self.trace, self.frobenius2 = moments[0], moments[1]
+        self.converged, self.rounds = status[1] != 0, status[2]
+
+    def explained(self) -> torch.Tensor:
+        """``values / trace``: the share of the total variance each mode carries."""
+        return self.values / self.trace
+
+    def participation_ratio(self) -> torch.Tensor:
+        """``tr(A)^2 / ||A||_F^2`` (0-d): the effective number of dimensions of the whole matrix."""
+        return self.trace * self.trace / self.frobenius2
+
+    def summary(self) -> Dict[str, float]:
+        """One read-back."""
+        worst = (self.residuals / self.values[0].abs()).max()
+        row = torch.stack([self.rounds.to(torch.float64), self.converged.to(torch.float64), self.trace, self.participation_ratio(),
+                           self.values[0] / self.trace, worst]).cpu().tolist()
+        return dict(zip(MODES_SUMMARY_NAMES, [int(self.values.shape[0]), int(row[0]), bool(row[1])] + row[2:]))
+
+    def project(self, responses: torch.Tensor, mean: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``[k, L]`` float64 time courses of the modes in ``responses`` ``[N, L]`` (``mean`` ``[N]`` is subtracted first)."""
+        x = responses.to(torch.float64)
+        if mean is not None:
+            x = x - mean.to(torch.float64)[:, None]
+        return self.vectors.t() @ x
+
+
+def modes(matrix: torch.Tensor, k: int, *, oversample: int = 8, max_iters: int = 64, tol: float = 1e-10, seed: int = 0,
+          scale: float = 1.0) -> PopulationModes:
+    """The ``k`` leading eigenpairs of the symmetric ``[N, N]`` float64 device matrix ``scale * matrix`` (any row stride ``>= N``;
+    no copy is made) by block subspace iteration with Rayleigh-Ritz extraction on a block of ``min(k + oversample, N)``
+    columns (``dwn_modes_solve``).  The run stops, on the device, once every residual of the first ``k`` pairs is at most ``tol *
+    |values[0]|``; nothing is read back.  The intended input is positive semi-definite up to rounding (a correlation or
+    covariance matrix); for an indefinite matrix the iteration finds the subspace dominant in magnitude."""
+    if not isinstance(matrix, torch.Tensor) or not matrix.is_cuda:
+        raise RuntimeError("sensorium_amd.population.modes: the matrix must be a GPU tensor; the HIP path has no CPU fallback")
+    if matrix.dtype != torch.float64:
+        raise RuntimeError(f"sensorium_amd.population.modes: the matrix must be float64 (got {matrix.dtype})")
+    if matrix.dim() != 2 or matrix.shape[0] != matrix.shape[1]:
+        raise ValueError(f"population.modes: the matrix must be square, got {tuple(matrix.shape)}")
+    k, oversample, N = int(k), int(oversample), int(matrix.shape[0])
+    if k < 1 or k > N:
+        raise ValueError(f"population.modes: k must lie in [1, N = {N}], got {k}")
+    if oversample < 0 or k + oversample > ops.L.MODES_MAXP:
+        raise ValueError(f"population.modes: k + oversample must lie in [k, {ops.L.MODES_MAXP}], got {k + oversample}")
+    values, V, residuals, moments, status = ops.modes_solve(matrix, k, min(k + oversample, N), max_iters, tol, seed, scale)
+    return PopulationModes(values[:k], V[:, :k], residuals[:k], moments, status)
+
+
+class ModesComparison:
+    """``.cosines`` ``[k]``: the cosines of the principal angles between two subspaces, descending; with a matrix ``B``,
+    ``.captured`` = ``tr(Va^T B Va) / tr(B)`` (0-d) next to ``.own`` = ``sum(b.values) / b.trace``."""
+
+    def __init__(self, cosines, captured, own):
+        self.cosines, self.captured, self.own = cosines, captured, own
+
+    def summary(self) -> Dict[str, float]:
+        """One read-back."""
+        parts = [self.cosines.max(), self.cosines.min(), self.own]
+        if self.captured is not None:
+            parts.append(self.captured)
+        row = torch.stack(parts).cpu().tolist()
+        out = {"k": int(self.cosines.shape[0]), "max_cosine": row[0], "min_cosine": row[1], "own": row[2]}
+        if self.captured is not None:
+            out["captured"] = row[3]
+        return out
+
+
+def compare_modes(a: PopulationModes, b: PopulationModes, matrix_b: Optional[torch.Tensor] = None,
+                  scale_b: float = 1.0) -> ModesComparison:
+    """The principal-angle cosines between the subspaces of ``a`` (model) and ``b`` (data): the singular values of ``Va^T Vb``
+    (``dwn_modes_overlap``).  With ``matrix_b`` (and its ``scale_b``) also the share of the data's variance that lies in the
+    model's subspace."""
+    if a.vectors.shape != b.vectors.shape:
+        raise ValueError(f"compare_modes: the two sets of modes differ in shape: {tuple(a.vectors.shape)} and {tuple(b.vectors.shape)}")
+    cosines, moments = ops.modes_overlap(a.vectors, b.vectors, matrix_b, scale_b)
+    own = b.values.sum() / b.trace
+    return ModesComparison(cosines, None if moments is None else moments[2] / moments[0], own)
