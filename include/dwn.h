@@ -488,6 +488,10 @@ int dwn_block_backward(const dwn_block_args* a, int device, void* stream);
 /* bit 0: dwn_block_forward writes y1; bit 1: it writes y3 (eval mode skips them where the stencil rebuilds y1 / the temporal
  * pass emits z3 directly: the caller may leave those pointers NULL) */
 int dwn_block_forward_writes(const dwn_block_args* a);
+/* bit 0: dwn_block_backward's conv_pw data gradient is dx itself — the shortcut branch's gradient is folded into the one-pass
+ * kernel (dwn_pw_bwd_fused_supported; da0 is not written); bit 1: ... through the inverse nearest maps hinv / winv of a strided
+ * block.  Answered from the arguments alone, no device (additive under ABI 7). */
+int dwn_block_backward_route(const dwn_block_args* a);
 int dwn_pool_forward(const dwn_pool_args* a, int device, void* stream);
 int dwn_pool_backward(const dwn_pool_args* a, int device, void* stream);
 size_t dwn_cortex_workspace_bytes(const dwn_cortex_args* a, int backward);
@@ -547,7 +551,8 @@ int dwn_adamw_ema_multi_guarded(const dwn_guarded_entry* list, int ntensors, int
  * both products fold the y1 term into Cin x Cin matrices:
  *   da0[M][Cin] = dy1 . W1    = [dh1 | a0] . [diag(abc0) W1 ; W1^T diag(abc1) W1] + abc2 . W1
  *   dw[E][Cin]  = dy1^T . a0  = diag(abc0) (dh1^T a0) + diag(abc1) W1 (a0^T a0) + abc2 (1^T a0)     (fp32, overwritten)
- * so the E-wide traffic is one read of dh1 (dtype == DWN_BF16, Cin == 64, E == 448 or 384, M % 128 == 0 — see
+ * so the E-wide traffic is one read of dh1 (dtype == DWN_BF16, M % 128 == 0, and Cin == 64 with E == 448 or 384, or Cin == 128
+ * with E == 896 — see
  * dwn_pw_bwd_fused_supported — one kernel computes both products from a single pass) or two (dwn_gemm_nn with the
  * K-concatenated operand + dwn_gemm_tn with the DWN_LD_CAT1 loader).  w_pw = conv_pw.0.weight [E][Cin] fp32 (used as rounded
  * to `dtype`, the values the forward multiplied with).  ws: dwn_pw_backward_workspace_bytes(E, Cin, dtype) bytes, 256-aligned. */
@@ -559,7 +564,7 @@ typedef struct dwn_pw_bwd_args {
     /* optional: the gradient of a stride-1 block's shortcut branch (BatchNorm of the channel-tiled block input, dwiseneuro.py:125-134)
      * folded in, so that da0 becomes the block's input gradient:
      *   da0[m][c] += sum_{c' = c + j*Cin < res_C} (res_abc[0][c']*res[m][c'] + res_abc[1][c']*a0[m][c] + res_abc[2][c'])
-     * res = the block's output gradient [M][res_C] (`dtype`), res_abc = [3][res_C]; res_C in {Cin, 2*Cin}.  Only where
+     * res = the block's output gradient [M][res_C] (`dtype`), res_abc = [3][res_C]; res_C in {Cin, 2*Cin}, Cin 64 / 128.  Only where
      * dwn_pw_bwd_fused_supported (the one-pass kernel's epilogue adds it; on the two-GEMM path it measured slower than the
      * separate pass it replaces: -3 there).  NULL = off. */
     const void* res; const float* res_abc; int res_C;

@@ -372,6 +372,7 @@ SYMBOLS = {
     "dwn_block_forward": (c_i, [_P(BlockArgs), c_i, c_p]),
     "dwn_block_backward": (c_i, [_P(BlockArgs), c_i, c_p]),
     "dwn_block_forward_writes": (c_i, [_P(BlockArgs)]),
+    "dwn_block_backward_route": _new(c_i, [_P(BlockArgs)]),
     "dwn_pool_forward": (c_i, [_P(PoolArgs), c_i, c_p]),
     "dwn_pool_backward": (c_i, [_P(PoolArgs), c_i, c_p]),
     "dwn_cortex_workspace_bytes": (c_sz, [_P(CortexArgs), c_i]),

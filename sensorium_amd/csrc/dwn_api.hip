@@ -725,7 +725,7 @@ static int pw_backward(int dt, const void* dh1, const void* a0, const float* w_p
         return dwn_set_error(-3, "pw_backward: the shortcut term is built into the one-pass kernel only (dwn_pw_bwd_fused_supported)");
     TRY(k_pw_bwd_prep(w_pw, abc, E, Cin, bp, gacc, r3, dt, (res && !gathered) ? res_abc : nullptr, res_C, s));
     if (pw_bwd_fused_supported(dt, M, E, Cin)) {
-        // 64-channel blocks: both products from ONE pass over dh1
+        // 64- and 128-channel blocks (0-3, 4-6): both products from ONE pass over dh1
         PROF(DWN_FAM_PW_DGRAD, launch_pw_bwd_fused(dh1, a0, bp, r3, da0, tacc, M, E, Cin, dt, res, res_abc, res_n,
                                                    gathered ? rg->hinv : nullptr, gathered ? rg->winv : nullptr, gathered ? rg->Hin : 0,
                                                    gathered ? rg->Win : 0, gathered ? rg->Hout : 0, gathered ? rg->Wout : 0, s));
@@ -856,7 +856,7 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
     // ---- conv_pw backward WITHOUT y1.  dy1 = A1*dh1 + A2*y1 + A3 is linear and y1 = a0.W1^T, so the y1 terms fold into Cin x Cin
     // matrices on either side:  da0 = [dh1 | a0] . [diag(A1) W1 ; G] + r3  (Bp, r3: k_pw_bwd_prep) and
     // dW1 = diag(A1) (dh1^T a0) + diag(A2) W1 (a0^T a0) + A3 (1^T a0)  (raw products in tacc, folded by k_pw_wgrad_fold)
-    // On a stride-1 block (identity shortcut map, output channels = input channels tiled once or twice) the shortcut branch's
+    // On a stride-1 block of 64 or 128 channels (identity shortcut map, output channels = input channels tiled once or twice) the shortcut branch's
     // gradient is folded into this GEMM and its result IS dx: no pass over (da0, x, dout) -> dx (BlockPlan::dx_folded).
     // (one-pass kernel only: as an epilogue of the two-GEMM path's data-gradient GEMM it cost 30-60 us where the pass it replaces
     // takes 20-35.)  On a strided block the epilogue gathers: only the rows the nearest map samples carry the shortcut's terms.
@@ -873,6 +873,11 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
 // caller need not allocate what is not written (and may pass NULL for it).
 int dwn_block_forward_writes(const dwn_block_args* ap) {
     return plan_block(*ap).writes;
+}
+// How dwn_block_backward forms dx for these arguments: bit 0 = BlockPlan::dx_folded, bit 1 = BlockPlan::sc_gathered
+int dwn_block_backward_route(const dwn_block_args* ap) {
+    const BlockPlan p = plan_block(*ap);
+    return (p.dx_folded ? 1 : 0) | (p.sc_gathered ? 2 : 0);
 }
 
 // ------------------------------------------------------------------------------------------------ pool
