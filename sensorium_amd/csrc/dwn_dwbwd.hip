@@ -1004,21 +1004,13 @@ static int launch_s2(const DwSpatialBwd& a, hipStream_t s) {
     typedef S2Lds<LPW, CIN> L;
     // rebuilt-y1 form: two workgroups per CU (registers), so the tile may be larger
     const size_t budget = CIN > 0 ? (size_t)(WK_LDS_BUDGET * 3 / 2) : (size_t)WK_LDS_BUDGET;
-    int R = a.rows_band;                              // input rows per band, even
-    if (R <= 0) {
-        R = 2;
-        while (R < a.Hin && (size_t)((R + 2) / 2 + 1) * L::ROW_BYTES <= budget) R += 2;
-        const int nb = (a.Hin + R - 1) / R;
-        R = (a.Hin + nb - 1) / nb;                    // even split
-    }
-    R = (R + 1) & ~1;
-    if (R > a.Hin) R = (a.Hin + 1) & ~1;
-    const int rows_qmax = R / 2 + 1;
-    const size_t lds = L::total(rows_qmax);
-    if (lds > 150 * 1024) return dwn_set_error(-5, "dw_spatial_bwd: rows_band too large for the LDS tile");
-    const int nbands = (a.Hin + R - 1) / R;
-    return launch_resident(dw_spatial_bwd_s2_kernel<LPW, CIN>, 256, lds, 2, (a.C + 63) / 64,
-                           (i64)((a.planes + L::NG - 1) / L::NG) * nbands, CIN > 0, s, a, R, rows_qmax);
+    // input rows per band, even (step 2): R / 2 + 1 staged rows; the W1 copy behind the tile counts towards the limit only
+    const BandPlan bp = plan_bands(a.Hin, [](int R) { return (size_t)(R / 2 + 1) * L::ROW_BYTES; }, budget, 150 * 1024 - L::W1_BYTES,
+                                   2, a.rows_band);
+    if (!bp.ok) return dwn_set_error(-5, "dw_spatial_bwd: rows_band too large for the LDS tile");
+    const int R = bp.rows, rows_qmax = R / 2 + 1;
+    return launch_resident(dw_spatial_bwd_s2_kernel<LPW, CIN>, 256, L::total(rows_qmax), 2, (a.C + 63) / 64,
+                           (i64)((a.planes + L::NG - 1) / L::NG) * bp.nbands, CIN > 0, s, a, R, rows_qmax);
 }
 
 template <int LPW, int RB, int CIN>

@@ -12,11 +12,18 @@
 // Loads are issued in batches of 4 independent 8/16-byte vectors per tensor so that, at 3-5 waves per SIMD,
 // each CU keeps tens of KB in flight (the HBM latency-bandwidth product).
 //
-// Kernel families in this file:
-//   dw_spatial_fwd_kernel / dw_spatial_bwd_kernel      generic (fp32 parity mode, any stride): packed-fp32 taps
-//   dw_spatial_fwd_pair_kernel (stride 1, 2)            bf16: x-pair-packed LDS tile + v_dot2c_f32_bf16 taps
-//   dw_spatial_bwd_pair_kernel (stride 1)               bf16: same idea for the data and weight gradients
-//   dw_temporal_fwd_kernel / dw_temporal_bwd_kernel     register sliding window along T
+// Kernel families in this file, in its order (3x3 spatial row-walk kernels: dwn_dwfwd.hip / dwn_dwbwd.hip; dwn_dwrc.hip):
+//   dw_spatial_fwd_kernel<T, 3, ST, NT>                 3x3 generic, packed-fp32 taps: fp32 at any stride, bf16 at the generic stride only
+//   dw_spatial_fwd_pair_kernel<ST, NT> (stride 1, 2)    3x3 bf16: x-pair-packed LDS tile + v_dot2c_f32_bf16 taps
+//   dw_spatial_bwd_kernel<T, 3, ST>                     3x3 generic: fp32 at any stride, bf16 at stride 2 and the generic stride
+//   dw_temporal_fwd_kernel<T, KT, ZOUT>                 KT 3, 5, 7, 9: register sliding window along T; ZOUT: the eval z3 epilogue
+//   dw_temporal_bwd_kernel<T, KT, LD_*, 4>              KT 3, 5 with a stored y3 (LD_AFFINE2, LD_DY3)
+//   dw_spatial_fwd_ks_kernel / dw_spatial_bwd_ks_kernel 5x5 and 7x7, both storage types, every stride: weights in LDS
+//   dw_spatial_bwd_pair_kernel (stride 1)               3x3 bf16: the pair-packed tile for the data and weight gradients
+//   dw_temporal_bwd_rc_kernel<T, KT>                    KT 3, 5, y3 recomputed (LD_PLAIN)
+//   dw_temporal_bwd_wide_kernel<T, KT>                  KT 7, 9, y3 recomputed, rings in LDS
+// Launchers: row bands from plan_bands (dwn_launch.h), the (stride, workgroup size) instantiation from by_stride / by_stride_threads,
+// one temporal launcher per direction switching on kt.  Only what a launch can reach is instantiated.
 // Integer index math is kept off the per-tap path (FastDiv / 24-bit multiplies / per-pixel tile index): on gfx950 an
 // integer VALU op costs ~1.5 FMAs and a bf16->fp32 unpack is such an op (profiles/r1c_valu_rates.txt).
 #include "dwn_internal.h"
@@ -26,9 +33,6 @@
 
 extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
 
-#ifndef DWS_THREADS
-#define DWS_THREADS 512      // threads per workgroup of the spatial forward kernel (more waves per LDS tile)
-#endif
 #define DWS_BWD_THREADS 256
 #ifndef DWS_BWD_PAIR_MINW
 #define DWS_BWD_PAIR_MINW 3       // waves per SIMD the pair-packed stride-1 backward is compiled for
@@ -41,9 +45,6 @@ extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
 #endif
 #ifndef DWT_RC_MINW
 #define DWT_RC_MINW 2        // waves per SIMD the y3-recomputing temporal backward is compiled for
-#endif
-#ifndef DWT_BWD_TB
-#define DWT_BWD_TB 4          // timesteps of loads in flight per thread in the temporal backward (4 or 8)
 #endif
 // LDS tile budgets of the spatial kernels (bytes); tuned on MI355X with tools/microbench.py
 #ifndef DWS_FWD_LDS_BUDGET
@@ -1053,6 +1054,21 @@ template <typename K, typename A>
 static int launch_dw(K kernel, int threads, size_t dyn_lds, int slices, i64 work, hipStream_t s, const A& a) {
     return launch_resident(kernel, threads, dyn_lds, 2, slices, work, false, s, a);
 }
+// The instantiation ladder of the banded spatial kernels: f gets the stride as a compile-time constant (1, 2, or 0 = read a.stride)
+// and, forward, the workgroup size: 512 threads on planes of 512 pixels and more (`big`), else 256; the generic stride is built for 256
+template <typename F>
+static int by_stride(int stride, F f) {
+    if (stride == 1) return f(std::integral_constant<int, 1>{});
+    if (stride == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 0>{});
+}
+template <typename F>
+static int by_stride_threads(int stride, bool big, F f) {
+    return by_stride(stride, [&](auto st) {
+        if constexpr (st.value != 0) if (big) return f(st, std::integral_constant<int, 512>{});
+        return f(st, std::integral_constant<int, 256>{});
+    });
+}
 
 // ------------------------------------------------------------------------------------------------
 // spatial kernel sizes 5 and 7 (P = KS/2 = 2, 3), both storage types, stride 1, 2 and generic.
@@ -1505,33 +1521,22 @@ __global__ __launch_bounds__(DWS_KS_BWD_THREADS, DWS_KS_BWD_THREADS / 128) void 
     DET_EXIT();
 }
 
-// launchers of the two kernels above: tile bytes and band from P; the LDS limit and its error as for 3x3
+// launchers of the two kernels above: tile bytes from P, the band from plan_bands; the LDS limit and its error as for 3x3
 template <typename T, int KS>
 static int spatial_fwd_ks_t(DwSpatialFwd a, hipStream_t s) {
     constexpr int CS = SL<T>::CS, P = KS / 2;
     constexpr size_t STATIC = (size_t)(KS * KS + 2) * CS * sizeof(float);
     const int Wp = a.Win + 2 * P;
-    auto tile_bytes = [&](int rb) { return (size_t)((rb - 1) * a.stride + KS) * Wp * 128; };
-    if (a.rows_band <= 0) {
-        size_t budget = (size_t)DWS_FWD_LDS_BUDGET;
-        if (budget > (size_t)DWS_KS_LDS_BUDGET(STATIC)) budget = (size_t)DWS_KS_LDS_BUDGET(STATIC);
-        int rb = 1;
-        while (rb < a.Hout && tile_bytes(rb + 1) <= budget) ++rb;
-        const int nb = (a.Hout + rb - 1) / rb;          // even split: no ragged last band
-        a.rows_band = (a.Hout + nb - 1) / nb;
-    }
-    if (a.rows_band > a.Hout) a.rows_band = a.Hout;
-    const size_t lds = tile_bytes(a.rows_band);
-    if (lds + STATIC > 156 * 1024) return dwn_set_error(-5, "dw_spatial: plane too wide for the LDS tile");
-    const int nbands = (a.Hout + a.rows_band - 1) / a.rows_band;
+    const size_t fwd = (size_t)DWS_FWD_LDS_BUDGET, ksb = (size_t)DWS_KS_LDS_BUDGET(STATIC), budget = fwd < ksb ? fwd : ksb;
+    const BandPlan bp = plan_bands(a.Hout, [&](int rb) { return (size_t)((rb - 1) * a.stride + KS) * Wp * 128; }, budget,
+                                   156 * 1024 - STATIC, 1, a.rows_band);
+    if (!bp.ok) return dwn_set_error(-5, "dw_spatial: plane too wide for the LDS tile");
+    a.rows_band = bp.rows;
     const int slices = (a.C + CS - 1) / CS;
-    const i64 work = (i64)a.planes * nbands;
-    const bool big = a.Hin * a.Win >= 512;
-    if (a.stride == 1) return big ? launch_dw(dw_spatial_fwd_ks_kernel<T, KS, 1, 512>, 512, lds, slices, work, s, a)
-                                  : launch_dw(dw_spatial_fwd_ks_kernel<T, KS, 1, 256>, 256, lds, slices, work, s, a);
-    if (a.stride == 2) return big ? launch_dw(dw_spatial_fwd_ks_kernel<T, KS, 2, 512>, 512, lds, slices, work, s, a)
-                                  : launch_dw(dw_spatial_fwd_ks_kernel<T, KS, 2, 256>, 256, lds, slices, work, s, a);
-    return launch_dw(dw_spatial_fwd_ks_kernel<T, KS, 0, 256>, 256, lds, slices, work, s, a);
+    const i64 work = (i64)a.planes * bp.nbands;
+    return by_stride_threads(a.stride, a.Hin * a.Win >= 512, [&](auto st, auto nt) {
+        return launch_dw(dw_spatial_fwd_ks_kernel<T, KS, st.value, nt.value>, nt.value, bp.lds, slices, work, s, a);
+    });
 }
 
 template <typename T, int KS>
@@ -1541,22 +1546,15 @@ static int spatial_bwd_ks_t(DwSpatialBwd a, hipStream_t s) {
     const int HL = (P + a.stride - 1) / a.stride;
     const int Wq = a.Wout + 2 * HL, Wz = a.Win + 2 * P;
     auto rows_q = [&](int rb) { return a.stride == 1 ? rb + 2 * P : (rb - 1 + 2 * P) / a.stride + 2; };   // staged output rows (bound)
-    auto tile_bytes = [&](int rb) { return ((size_t)rows_q(rb) * Wq + (size_t)rb * Wz) * 128; };          // gradient tile + z1 tile
-    if (a.rows_band <= 0) {
-        int rb = 1;
-        while (rb < a.Hin && tile_bytes(rb + 1) <= (size_t)DWS_KS_LDS_BUDGET(STATIC)) ++rb;
-        const int nb = (a.Hin + rb - 1) / rb;
-        a.rows_band = (a.Hin + nb - 1) / nb;
-    }
-    if (a.rows_band > a.Hin) a.rows_band = a.Hin;
-    const size_t lds = tile_bytes(a.rows_band);
-    if (lds + STATIC > 156 * 1024) return dwn_set_error(-5, "dw_spatial_bwd: plane too wide for the LDS tile");
-    const int nbands = (a.Hin + a.rows_band - 1) / a.rows_band;
+    const BandPlan bp = plan_bands(a.Hin, [&](int rb) { return ((size_t)rows_q(rb) * Wq + (size_t)rb * Wz) * 128; },      // gradient tile + z1 tile
+                                   (size_t)DWS_KS_LDS_BUDGET(STATIC), 156 * 1024 - STATIC, 1, a.rows_band);
+    if (!bp.ok) return dwn_set_error(-5, "dw_spatial_bwd: plane too wide for the LDS tile");
+    a.rows_band = bp.rows;
     const int slices = (a.C + CS - 1) / CS;
-    const i64 work = (i64)a.planes * nbands;
-    if (a.stride == 1) return launch_dw(dw_spatial_bwd_ks_kernel<T, KS, 1>, DWS_KS_BWD_THREADS, lds, slices, work, s, a);
-    if (a.stride == 2) return launch_dw(dw_spatial_bwd_ks_kernel<T, KS, 2>, DWS_KS_BWD_THREADS, lds, slices, work, s, a);
-    return launch_dw(dw_spatial_bwd_ks_kernel<T, KS, 0>, DWS_KS_BWD_THREADS, lds, slices, work, s, a);
+    const i64 work = (i64)a.planes * bp.nbands;
+    return by_stride(a.stride, [&](auto st) {
+        return launch_dw(dw_spatial_bwd_ks_kernel<T, KS, st.value>, DWS_KS_BWD_THREADS, bp.lds, slices, work, s, a);
+    });
 }
 
 #define DWS_KS_BUILT "dw_spatial: spatial_kernel must be 3, 5 or 7 (the built set)"
@@ -1571,37 +1569,20 @@ static int spatial_fwd_t(DwSpatialFwd a, hipStream_t s) {
     const int Wp = a.Win + 2;
     // bf16, stride 1/2: x-pair-packed tile (dot2 kernel), rows of ceil(Wp/2) pairs x 256 bytes
     const bool pair = TT<T>::IS_BF16 && (a.stride == 1 || a.stride == 2);
-    auto tile_bytes = [&](int rb) {
-        return pair ? (size_t)((rb - 1) * a.stride + 3) * ((Wp + 1) / 2) * 256 : (size_t)((rb - 1) * a.stride + 3) * Wp * 128;
-    };
-    if (a.rows_band <= 0) {
-        // largest band whose tile fits the LDS budget: fewer halo rows re-read, fewer barriers per byte
-        int rb = 1;
-        while (rb < a.Hout && tile_bytes(rb + 1) <= (size_t)DWS_FWD_LDS_BUDGET) ++rb;
-        const int nb = (a.Hout + rb - 1) / rb;          // even split: no ragged last band
-        a.rows_band = (a.Hout + nb - 1) / nb;
-    }
-    if (a.rows_band > a.Hout) a.rows_band = a.Hout;
-    const size_t lds = tile_bytes(a.rows_band);
-    if (lds > 156 * 1024) return dwn_set_error(-5, "dw_spatial: plane too wide for the LDS tile");
-    const int nbands = (a.Hout + a.rows_band - 1) / a.rows_band;
+    const size_t row_bytes = pair ? (size_t)((Wp + 1) / 2) * 256 : (size_t)Wp * 128;
+    const BandPlan bp = plan_bands(a.Hout, [&](int rb) { return (size_t)((rb - 1) * a.stride + 3) * row_bytes; },
+                                   (size_t)DWS_FWD_LDS_BUDGET, 156 * 1024, 1, a.rows_band);
+    if (!bp.ok) return dwn_set_error(-5, "dw_spatial: plane too wide for the LDS tile");
+    a.rows_band = bp.rows;
     const int slices = (a.C + CS - 1) / CS;
-    const i64 work = (i64)a.planes * nbands;
+    const i64 work = (i64)a.planes * bp.nbands;
     // 512-thread workgroups (twice the waves per LDS tile) pay off on large planes; tiny planes prefer 256
-    const bool big = a.Hin * a.Win >= 512;
-    if constexpr (TT<T>::IS_BF16) {
-        if (pair) {
-            if (a.stride == 1) return big ? launch_dw(dw_spatial_fwd_pair_kernel<1, 512>, 512, lds, slices, work, s, a)
-                                          : launch_dw(dw_spatial_fwd_pair_kernel<1, 256>, 256, lds, slices, work, s, a);
-            return big ? launch_dw(dw_spatial_fwd_pair_kernel<2, 512>, 512, lds, slices, work, s, a)
-                       : launch_dw(dw_spatial_fwd_pair_kernel<2, 256>, 256, lds, slices, work, s, a);
-        }
-    }
-    if (a.stride == 1) return big ? launch_dw(dw_spatial_fwd_kernel<T, 3, 1, 512>, 512, lds, slices, work, s, a)
-                                  : launch_dw(dw_spatial_fwd_kernel<T, 3, 1, 256>, 256, lds, slices, work, s, a);
-    if (a.stride == 2) return big ? launch_dw(dw_spatial_fwd_kernel<T, 3, 2, 512>, 512, lds, slices, work, s, a)
-                                  : launch_dw(dw_spatial_fwd_kernel<T, 3, 2, 256>, 256, lds, slices, work, s, a);
-    return launch_dw(dw_spatial_fwd_kernel<T, 3, 0, 256>, 256, lds, slices, work, s, a);
+    return by_stride_threads(a.stride, a.Hin * a.Win >= 512, [&](auto st, auto nt) {
+        if constexpr (TT<T>::IS_BF16 && st.value != 0)       // == pair: the generic kernel is not built for bf16 at strides 1, 2
+            return launch_dw(dw_spatial_fwd_pair_kernel<st.value, nt.value>, nt.value, bp.lds, slices, work, s, a);
+        else
+            return launch_dw(dw_spatial_fwd_kernel<T, 3, st.value, nt.value>, nt.value, bp.lds, slices, work, s, a);
+    });
 }
 bool dw_spatial_fwd_walk_supported(const DwSpatialFwd& a, int dtype);
 int launch_dw_spatial_fwd_walk(const DwSpatialFwd& a, hipStream_t s);
@@ -1845,22 +1826,18 @@ static int spatial_bwd_t(DwSpatialBwd a, hipStream_t s) {
     // bf16, stride 1: x-pair-packed gradient tile (dot2 kernel), rows of ceil(Wq/2) pairs x 256 bytes
     const bool pair = TT<T>::IS_BF16 && a.stride == 1;
     const size_t row_bytes = pair ? (size_t)((Wq + 1) / 2) * 256 : (size_t)Wq * 128;
-    if (a.rows_band <= 0) {
-        int rb = 1;
-        while (rb < a.Hin && (size_t)rows_q(rb + 1) * row_bytes <= (size_t)DWS_BWD_LDS_BUDGET) ++rb;
-        const int nb = (a.Hin + rb - 1) / rb;
-        a.rows_band = (a.Hin + nb - 1) / nb;
-    }
-    if (a.rows_band > a.Hin) a.rows_band = a.Hin;
-    const size_t lds = (size_t)rows_q(a.rows_band) * row_bytes;
-    if (lds > 150 * 1024) return dwn_set_error(-5, "dw_spatial_bwd: plane too wide for the LDS tile");
-    const int nbands = (a.Hin + a.rows_band - 1) / a.rows_band;
+    const BandPlan bp = plan_bands(a.Hin, [&](int rb) { return (size_t)rows_q(rb) * row_bytes; }, (size_t)DWS_BWD_LDS_BUDGET,
+                                   150 * 1024, 1, a.rows_band);
+    if (!bp.ok) return dwn_set_error(-5, "dw_spatial_bwd: plane too wide for the LDS tile");
+    a.rows_band = bp.rows;
     const int slices = (a.C + CS - 1) / CS;
-    const i64 work = (i64)a.planes * nbands;
-    if (pair) return launch_dw(dw_spatial_bwd_pair_kernel, DWS_BWD_THREADS, lds, slices, work, s, a);
-    if (a.stride == 1) return launch_dw(dw_spatial_bwd_kernel<T, 3, 1>, DWS_BWD_THREADS, lds, slices, work, s, a);
-    if (a.stride == 2) return launch_dw(dw_spatial_bwd_kernel<T, 3, 2>, DWS_BWD_THREADS, lds, slices, work, s, a);
-    return launch_dw(dw_spatial_bwd_kernel<T, 3, 0>, DWS_BWD_THREADS, lds, slices, work, s, a);
+    const i64 work = (i64)a.planes * bp.nbands;
+    return by_stride(a.stride, [&](auto st) {
+        if constexpr (TT<T>::IS_BF16 && st.value == 1)       // == pair: the generic kernel is not built for bf16 at stride 1
+            return launch_dw(dw_spatial_bwd_pair_kernel, DWS_BWD_THREADS, bp.lds, slices, work, s, a);
+        else
+            return launch_dw(dw_spatial_bwd_kernel<T, 3, st.value>, DWS_BWD_THREADS, bp.lds, slices, work, s, a);
+    });
 }
 bool dw_spatial_bwd_walk_supported(const DwSpatialBwd& a, int dtype);
 int launch_dw_spatial_bwd_walk(const DwSpatialBwd& a, hipStream_t s);
@@ -1876,20 +1853,24 @@ static int temporal_fwd_t(const DwTemporalFwd& a, hipStream_t s) {
     constexpr int CS = SL<T>::CS, LP = SL<T>::LP;
     if (a.C % 8) return dwn_set_error(-2, "dw_temporal: C must be a multiple of 8");
     const int slices = (a.C + CS - 1) / CS;
-    const i64 npos = (i64)a.B * a.HW;
-    const i64 work = (npos + LP - 1) / LP;
-    if (a.z_scale) {
-        if (!a.z_shift || a.stats) return dwn_set_error(-2, "dw_temporal: the z3 epilogue needs z_shift and no statistics (eval mode)");
-        if (a.kt == 5) return launch_dw(dw_temporal_fwd_kernel<T, 5, true>, 256, 0, slices, work, s, a);
-        if (a.kt == 3) return launch_dw(dw_temporal_fwd_kernel<T, 3, true>, 256, 0, slices, work, s, a);
-        return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
+    const i64 work = ((i64)a.B * a.HW + LP - 1) / LP;
+    const bool zout = a.z_scale != nullptr;
+    if (zout && (!a.z_shift || a.stats)) return dwn_set_error(-2, "dw_temporal: the z3 epilogue needs z_shift and no statistics (eval mode)");
+    auto go = [&](auto plain, auto z3) { return zout ? launch_dw(z3, 256, 0, slices, work, s, a) : launch_dw(plain, 256, 0, slices, work, s, a); };
+    switch (a.kt) {        // 7 and 9 arrive through launch_dw_temporal_wide_fwd, which refuses first what those sizes refuse
+        case 3: return go(dw_temporal_fwd_kernel<T, 3>, dw_temporal_fwd_kernel<T, 3, true>);
+        case 5: return go(dw_temporal_fwd_kernel<T, 5>, dw_temporal_fwd_kernel<T, 5, true>);
+        case 7: return go(dw_temporal_fwd_kernel<T, 7>, dw_temporal_fwd_kernel<T, 7, true>);
+        case 9: return go(dw_temporal_fwd_kernel<T, 9>, dw_temporal_fwd_kernel<T, 9, true>);
     }
-    if (a.kt == 5) return launch_dw(dw_temporal_fwd_kernel<T, 5>, 256, 0, slices, work, s, a);
-    if (a.kt == 3) return launch_dw(dw_temporal_fwd_kernel<T, 3>, 256, 0, slices, work, s, a);
     return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
 }
 int launch_dw_temporal_fwd(const DwTemporalFwd& a, int dtype, hipStream_t s) {
-    if (a.kt == 7 || a.kt == 9) return launch_dw_temporal_wide_fwd(a, dtype, s);       // sizes 7 and 9: at the end of this file
+    if (a.kt == 7 || a.kt == 9) return launch_dw_temporal_wide_fwd(a, dtype, s);       // dw_temporal_wide_check first
+    return dtype == DWN_BF16 ? temporal_fwd_t<bf16_t>(a, s) : temporal_fwd_t<float>(a, s);
+}
+int launch_dw_temporal_wide_fwd(const DwTemporalFwd& a, int dtype, hipStream_t s) {
+    if (int rc = dw_temporal_wide_check(a.kt, a.C, LD_PLAIN)) return rc;
     return dtype == DWN_BF16 ? temporal_fwd_t<bf16_t>(a, s) : temporal_fwd_t<float>(a, s);
 }
 
@@ -2041,37 +2022,6 @@ __global__ __launch_bounds__(256, DWT_RC_MINW) void dw_temporal_bwd_rc_kernel(co
     }
     if (a.stats) block_stats_flush<T>(lstat, st0, st1, cv, c0, a.C, a.stats, blockIdx.x % DWN_NREP);
     DET_EXIT();
-}
-
-template <typename T>
-static int temporal_bwd_t(const DwTemporalBwd& a, hipStream_t s) {
-    constexpr int CS = SL<T>::CS, LP = SL<T>::LP;
-    if (a.C % 8) return dwn_set_error(-2, "dw_temporal: C must be a multiple of 8");
-    const int slices = (a.C + CS - 1) / CS;
-    const i64 npos = (i64)a.B * a.HW;
-    const i64 work = (npos + LP - 1) / LP;
-    const bool dy3 = a.dy_kind == LD_DY3;
-    if (a.dy_kind == LD_PLAIN) {       // dy.p = dh3 only: y3 is recomputed from y2 (three passes instead of four)
-        if (a.kt == 5) return launch_dw(dw_temporal_bwd_rc_kernel<T, 5>, 256, 0, slices, work, s, a);
-        if (a.kt == 3) return launch_dw(dw_temporal_bwd_rc_kernel<T, 3>, 256, 0, slices, work, s, a);
-        return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
-    }
-    if (!dy3 && a.dy_kind != LD_AFFINE2) return dwn_set_error(-3, "dw_temporal_bwd: unsupported dy loader");
-    const bool tb8 = DWT_BWD_TB == 8;
-    if (a.kt == 5) {
-        if (dy3) return launch_dw(dw_temporal_bwd_kernel<T, 5, LD_DY3, 4>, 256, 0, slices, work, s, a);
-        if (tb8) return launch_dw(dw_temporal_bwd_kernel<T, 5, LD_AFFINE2, 8>, 256, 0, slices, work, s, a);
-        return launch_dw(dw_temporal_bwd_kernel<T, 5, LD_AFFINE2, 4>, 256, 0, slices, work, s, a);
-    }
-    if (a.kt == 3) {
-        if (dy3) return launch_dw(dw_temporal_bwd_kernel<T, 3, LD_DY3, 4>, 256, 0, slices, work, s, a);
-        return launch_dw(dw_temporal_bwd_kernel<T, 3, LD_AFFINE2, 4>, 256, 0, slices, work, s, a);
-    }
-    return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
-}
-int launch_dw_temporal_bwd(const DwTemporalBwd& a, int dtype, hipStream_t s) {
-    if (a.kt == 7 || a.kt == 9) return launch_dw_temporal_wide_bwd(a, dtype, s);       // sizes 7 and 9: below
-    return dtype == DWN_BF16 ? temporal_bwd_t<bf16_t>(a, s) : temporal_bwd_t<float>(a, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2276,7 +2226,7 @@ __global__ __launch_bounds__(256, DWT_RC_MINW) void dw_temporal_bwd_wide_kernel(
     DET_EXIT();
 }
 
-// what the two launchers below refuse, in this order; host only, so the C entries ask it before they enter the device
+// what launch_dw_temporal_wide_fwd / _bwd refuse, in this order; host only, so the C entries ask it before they enter the device
 int dw_temporal_wide_check(int kt, int C, int dy_kind) {
     if (kt != 7 && kt != 9) return dwn_set_error(-4, "dw_temporal_wide: only temporal_kernel 7 or 9 is built (3 and 5: dwn_dw_temporal_fwd / _bwd)");
     if (C % 8) return dwn_set_error(-2, "dw_temporal_wide: C must be a multiple of 8");
@@ -2285,33 +2235,35 @@ int dw_temporal_wide_check(int kt, int C, int dy_kind) {
     return 0;
 }
 
+// temporal backward, every size and loader (the forward's launcher stands behind its kernel, above)
 template <typename T>
-static int temporal_wide_fwd_t(const DwTemporalFwd& a, hipStream_t s) {
+static int temporal_bwd_t(const DwTemporalBwd& a, hipStream_t s) {
     constexpr int CS = SL<T>::CS, LP = SL<T>::LP;
+    if (a.C % 8) return dwn_set_error(-2, "dw_temporal: C must be a multiple of 8");
     const int slices = (a.C + CS - 1) / CS;
     const i64 work = ((i64)a.B * a.HW + LP - 1) / LP;
-    if (a.z_scale) {
-        if (!a.z_shift || a.stats) return dwn_set_error(-2, "dw_temporal: the z3 epilogue needs z_shift and no statistics (eval mode)");
-        if (a.kt == 9) return launch_dw(dw_temporal_fwd_kernel<T, 9, true>, 256, 0, slices, work, s, a);
-        return launch_dw(dw_temporal_fwd_kernel<T, 7, true>, 256, 0, slices, work, s, a);
+    auto go = [&](auto kernel) { return launch_dw(kernel, 256, 0, slices, work, s, a); };
+    if (a.dy_kind == LD_PLAIN) {       // dy.p = dh3 only: y3 is recomputed from y2 (three passes instead of four)
+        switch (a.kt) {                // 7 and 9 arrive through launch_dw_temporal_wide_bwd, which refuses the other loaders first
+            case 3: return go(dw_temporal_bwd_rc_kernel<T, 3>);
+            case 5: return go(dw_temporal_bwd_rc_kernel<T, 5>);
+            case 7: return go(dw_temporal_bwd_wide_kernel<T, 7>);
+            case 9: return go(dw_temporal_bwd_wide_kernel<T, 9>);
+        }
+        return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
     }
-    if (a.kt == 9) return launch_dw(dw_temporal_fwd_kernel<T, 9>, 256, 0, slices, work, s, a);
-    return launch_dw(dw_temporal_fwd_kernel<T, 7>, 256, 0, slices, work, s, a);
-}
-int launch_dw_temporal_wide_fwd(const DwTemporalFwd& a, int dtype, hipStream_t s) {
-    if (int rc = dw_temporal_wide_check(a.kt, a.C, LD_PLAIN)) return rc;
-    return dtype == DWN_BF16 ? temporal_wide_fwd_t<bf16_t>(a, s) : temporal_wide_fwd_t<float>(a, s);
-}
-
-template <typename T>
-static int temporal_wide_bwd_t(const DwTemporalBwd& a, hipStream_t s) {
-    constexpr int CS = SL<T>::CS, LP = SL<T>::LP;
-    const int slices = (a.C + CS - 1) / CS;
-    const i64 work = ((i64)a.B * a.HW + LP - 1) / LP;
-    if (a.kt == 9) return launch_dw(dw_temporal_bwd_wide_kernel<T, 9>, 256, 0, slices, work, s, a);
-    return launch_dw(dw_temporal_bwd_wide_kernel<T, 7>, 256, 0, slices, work, s, a);
+    const bool dy3 = a.dy_kind == LD_DY3;
+    if (!dy3 && a.dy_kind != LD_AFFINE2) return dwn_set_error(-3, "dw_temporal_bwd: unsupported dy loader");
+    if (a.kt == 5) return dy3 ? go(dw_temporal_bwd_kernel<T, 5, LD_DY3, 4>) : go(dw_temporal_bwd_kernel<T, 5, LD_AFFINE2, 4>);
+    if (a.kt == 3) return dy3 ? go(dw_temporal_bwd_kernel<T, 3, LD_DY3, 4>) : go(dw_temporal_bwd_kernel<T, 3, LD_AFFINE2, 4>);
+    return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
 }
 int launch_dw_temporal_wide_bwd(const DwTemporalBwd& a, int dtype, hipStream_t s) {
     if (int rc = dw_temporal_wide_check(a.kt, a.C, a.dy_kind)) return rc;
-    return dtype == DWN_BF16 ? temporal_wide_bwd_t<bf16_t>(a, s) : temporal_wide_bwd_t<float>(a, s);
+    return dtype == DWN_BF16 ? temporal_bwd_t<bf16_t>(a, s) : temporal_bwd_t<float>(a, s);
 }
+int launch_dw_temporal_bwd(const DwTemporalBwd& a, int dtype, hipStream_t s) {
+    if (a.kt == 7 || a.kt == 9) return launch_dw_temporal_wide_bwd(a, dtype, s);       // dw_temporal_wide_check first
+    return dtype == DWN_BF16 ? temporal_bwd_t<bf16_t>(a, s) : temporal_bwd_t<float>(a, s);
+}
+

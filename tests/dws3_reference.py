@@ -118,6 +118,37 @@ def s2_band(Hin, LPW, cin, rows_band):
     return R
 
 
+def banded_plan(direction, dtype, Hin, Win, stride, rows_band=0):
+    """spatial_fwd_t / spatial_bwd_t (the pair and generic kernels): -> (greedy band, None for a given rows_band; band; bands per
+    plane; LDS tile bytes).  Bands are output rows forward, input rows backward."""
+    Hout, Wout = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
+    if direction == "fwd":
+        pair = dtype == "bf16" and stride in (1, 2)
+        Wp = Win + 2
+        rows, budget = Hout, (80 if stride >= 2 else 48) * 1024
+
+        def tile_bytes(rb):
+            return ((rb - 1) * stride + 3) * ((Wp + 1) // 2) * 256 if pair else ((rb - 1) * stride + 3) * Wp * 128
+    else:
+        pair = dtype == "bf16" and stride == 1
+        Wq = Wout + 2
+        row_bytes = ((Wq + 1) // 2) * 256 if pair else Wq * 128
+        rows, budget = Hin, 44 * 1024
+
+        def tile_bytes(rb):
+            return ((rb - 1 + 2) // stride + 2) * row_bytes
+    greedy, rb = None, rows_band
+    if rb <= 0:
+        rb = 1
+        while rb < rows and tile_bytes(rb + 1) <= budget:
+            rb += 1
+        greedy = rb
+        nb = (rows + rb - 1) // rb
+        rb = (rows + nb - 1) // nb
+    rb = min(rb, rows)
+    return greedy, rb, (rows + rb - 1) // rb, tile_bytes(rb)
+
+
 def dws3_dispatch(direction, dtype, planes, Hin, Win, C, stride, impl=0, rows_band=0, cin=0, ld=None):
     """-> (path name, template parameters) of the kernel dwn_dw_spatial_fwd / _bwd launches for ks = 3, or ("refuse", code).
     ld = in.ld (forward) / dy.ld = y1.ld (backward), default C; the rebuilt forms' a0_ld is cin + (ld - C)."""
@@ -153,43 +184,17 @@ def dws3_dispatch(direction, dtype, planes, Hin, Win, C, stride, impl=0, rows_ba
     # spatial_fwd_t / spatial_bwd_t
     if C % 8:
         return ("refuse", -2)
+    lds = banded_plan(direction, dtype, Hin, Win, stride, rows_band)[3]
     if fwd:
-        pair = dtype == "bf16" and stride in (1, 2)
-        Wp = Win + 2
-
-        def tile_bytes(rb):
-            return ((rb - 1) * stride + 3) * ((Wp + 1) // 2) * 256 if pair else ((rb - 1) * stride + 3) * Wp * 128
-        rb = rows_band
-        if rb <= 0:
-            rb, budget = 1, (80 if stride >= 2 else 48) * 1024
-            while rb < Hout and tile_bytes(rb + 1) <= budget:
-                rb += 1
-            nb = (Hout + rb - 1) // rb
-            rb = (Hout + nb - 1) // nb
-        rb = min(rb, Hout)
-        if tile_bytes(rb) > 156 * 1024:
+        if lds > 156 * 1024:
             return ("refuse", -5)
         nt = 512 if Hin * Win >= 512 else 256
-        if pair:
+        if dtype == "bf16" and stride in (1, 2):
             return ("fwd_pair", (stride, nt))
         return ("fwd_generic", (dtype, 3, stride, nt)) if stride in (1, 2) else ("fwd_generic", (dtype, 3, 0, 256))
-    pair = dtype == "bf16" and stride == 1
-    Wq = Wout + 2
-    row_bytes = ((Wq + 1) // 2) * 256 if pair else Wq * 128
-
-    def rows_q(rb):
-        return (rb - 1 + 2) // stride + 2
-    rb = rows_band
-    if rb <= 0:
-        rb = 1
-        while rb < Hin and rows_q(rb + 1) * row_bytes <= 44 * 1024:
-            rb += 1
-        nb = (Hin + rb - 1) // rb
-        rb = (Hin + nb - 1) // nb
-    rb = min(rb, Hin)
-    if rows_q(rb) * row_bytes > 150 * 1024:
+    if lds > 150 * 1024:
         return ("refuse", -5)
-    if pair:
+    if dtype == "bf16" and stride == 1:
         return ("bwd_pair", ())
     return ("bwd_generic", (dtype, 3, stride if stride in (1, 2) else 0))
 
@@ -335,6 +340,14 @@ def _cases(kind):
                 for rb in (1, 2, 3):
                     add(d, dt, P3, 18 * st, 32 * st, 72, st, impl=1, rows_band=rb, rule="bands")
             add(d, dt, P3, 10, 13, 72, 3, rule="stride3")
+    # -- the library's own band plan (rows_band = 0) on planes that need more than one band, where the even split moves the band off
+    # the largest that fits (banded_plan; the CPU test asserts it case by case): fp32 generic at strides 1 and 2, the bf16 pair
+    # kernels, the bf16 generic backward at stride 2.  25 rows; the stride-2 backward stages half the rows, so it needs 62 columns
+    P2 = 2 if rnd else 1
+    for dt in ("f32", "bf16"):
+        for st in (1, 2):
+            add("fwd", dt, P2, 25, 30, 72, st, impl=1, rule="auto_bands")
+            add("bwd", dt, P2, 25, 30 if st == 1 else 62, 72, st, impl=1, rule="auto_bands")
     # -- leading dimensions: one case per kernel family (the rebuilt chain has its own above)
     for st in (1, 2):
         for d in ("fwd", "bwd"):

@@ -84,6 +84,28 @@ def test_wrap_cases_take_a_second_iteration_of_the_persistent_loop():
     assert R.resident_grid_x(1, 512, 9) == 1 and R.resident_grid_x(2, 7, 3, True) == 8
 
 
+def test_auto_band_cases_take_more_than_one_band_and_the_even_split_moves_it():
+    """The auto_bands cases leave rows_band to the library on a plane that needs at least two bands, and the even split gives
+    another height than the largest band that fits; the last band is then shorter than the others or equal to them."""
+    want = {("fwd", "f32", 1): (10, 9, 3), ("fwd", "f32", 2): (9, 7, 2), ("fwd", "bf16", 1): (10, 9, 3), ("fwd", "bf16", 2): (9, 7, 2),
+            ("bwd", "f32", 1): (8, 7, 4), ("bwd", "f32", 2): (16, 13, 2), ("bwd", "bf16", 1): (8, 7, 4), ("bwd", "bf16", 2): (16, 13, 2)}
+    paths = set()
+    for cases in (R.RANDOM_CASES, R.EXACT_CASES):
+        auto = [c for c in cases if c.rule == "auto_bands"]
+        assert len(auto) == 8 and {(c.direction, c.dtype, c.stride) for c in auto} == set(want)
+        for c in auto:
+            assert c.rows_band == 0
+            greedy, rb, nb, _ = R.banded_plan(c.direction, c.dtype, c.Hin, c.Win, c.stride)
+            rows = c.Hin if c.direction == "bwd" else (c.Hin - 1) // c.stride + 1
+            print("DWS3-AUTO", R.case_id(c), f"rows={rows} greedy={greedy} band={rb} bands={nb} last={rows - (nb - 1) * rb}", flush=True)
+            assert (greedy, rb, nb) == want[(c.direction, c.dtype, c.stride)]             # worked by hand from the launchers' rule
+            assert nb >= 2 and rb != greedy and 0 < rows - (nb - 1) * rb <= rb
+            paths.add(R.case_dispatch(c) + (c.dtype,))
+    assert paths == {("fwd_generic", ("f32", 3, 1, 512), "f32"), ("fwd_generic", ("f32", 3, 2, 512), "f32"),
+                     ("fwd_pair", (1, 512), "bf16"), ("fwd_pair", (2, 512), "bf16"), ("bwd_generic", ("f32", 3, 1), "f32"),
+                     ("bwd_generic", ("f32", 3, 2), "f32"), ("bwd_pair", (), "bf16"), ("bwd_generic", ("bf16", 3, 2), "bf16")}
+
+
 def test_dispatch_restates_the_launchers():
     d = R.dws3_dispatch
     # library chunk heights (launch_fc_rb, launch_s1c_rb) and the rounding of rows_band to a built height

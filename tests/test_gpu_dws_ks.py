@@ -233,6 +233,21 @@ def test_forced_bands(stride, ks, dtype):
         _check(case, rows_band=rows_band, tag="bands")
 
 
+# The library's own band plan (rows_band = 0) at stride 1 on planes of 28 columns that need several bands and whose height the
+# largest band that fits does not divide, so that the even split lowers the band.  Worked by hand from the launchers' rule (tile
+# bytes ((rb - 1) + k) * (28 + 2P) * 128 forward against 48 KB; ((rb + 2P) + rb) * (28 + 2P) * 128 backward against 79 KB less the
+# static weight and sum tables, (k * k + 6) * 64 or 32 channels * 4 bytes).  Hin: largest band -> band x bands
+#   k 5  25: forward 8 -> 7 x 4 (both types), backward bf16 6 -> 5 x 5 (fp32: 7 x 4 as it is)    22: backward fp32 7 -> 6 x 4
+#   k 7  16: forward 5 -> 4 x 4 (both types), backward fp32 5 -> 4 x 4 (bf16: 4 x 4 as it is)     9: backward bf16 4 -> 3 x 3
+AUTO_HIN = {5: (25, 22), 7: (16, 9)}
+
+
+@pytest.mark.parametrize("ks,dtype", KS_DT, ids=KS_DT_IDS)
+def test_automatic_bands(ks, dtype):
+    for Hin in AUTO_HIN[ks]:
+        _check(Case(2, Hin, 28, 72, 1, ks, dtype, seed=3), tag="auto_bands")
+
+
 # ---- exact cases: small integers that bf16 holds, as tests/test_gpu_fullsize.py builds its 3x3 stencil cases -------------------------
 #   y1 integers 0 .. 16, BatchNorm-1 scale 1, shift 17  ->  h >= 17, where the fp32 SiLU is the identity to the last bit bf16 keeps
 #   and SiLU' = 1  ->  z1 = h in 17 .. 33; three non-zero taps of +-1 per channel  ->  |y2| <= 99; g = dh2 in {-1, 0, 1}
