@@ -13,7 +13,11 @@
  *    (hipGraph-capturable).  Every call takes an explicit `device` because autograd calls backward from a
  *    worker thread whose current device is not the caller's.
  *  - return value: 0 ok; < 0 argument / unsupported-configuration error; > 0 a hipError_t.
- *    `dwn_last_error()` returns a thread-local message.
+ *    `dwn_last_error()` returns a thread-local message.  Every entry answers its argument errors from the arguments alone, before it
+ *    enters the device and with nothing queued or written: -1 null struct or required pointer, -7 a mode it is not built for, -2
+ *    geometry (sizes positive, divisibility, dtype / training values, row and grid counts below 2^31), -4 a size that is not
+ *    built, then the workspace (-6 for the model's composites, -3 for the analysis entries).  A size entry (*_workspace_bytes,
+ *    *_ws_bytes, *_wt_bytes) answers 0 for bad arguments — null, or a geometry its entries refuse — and leaves no error behind.
  *  - activations are channels-last matrices [rows = (b,t,h,w)][C] in `dtype` storage
  *    (DWN_F32 = fp32 parity mode, DWN_BF16 = bf16 storage / fp32 accumulate).  Parameters, BN
  *    coefficients, statistics and gradients of parameters are always fp32.
@@ -467,7 +471,7 @@ int dwn_conv_pw_bn_stats(const void* a0, long long a0_ld, long long M, const flo
                          void* stream);
 
 /* composites (forward / backward of one reference module each) */
-size_t dwn_stem_workspace_bytes(const dwn_stem_args* a);
+size_t dwn_stem_workspace_bytes(const dwn_stem_args* a);     /* 0 for bad arguments */
 int dwn_stem_forward(const dwn_stem_args* a, int device, void* stream);
 int dwn_stem_backward(const dwn_stem_args* a, int device, void* stream);
 int dwn_stem_input_grad(const dwn_stem_input_grad_args* a, int device, void* stream);
@@ -482,11 +486,12 @@ int dwn_stem_input_grad(const dwn_stem_input_grad_args* a, int device, void* str
  * dwn_stem_backward + dwn_stem_input_grad).  dx: [B][Cin][S] fp32, written whole.  Null dx / x / xmom / dout / dw / ws: -1.
  * The argument checks answer before the device is entered.  C0 and Cin as dwn_stem_input_grad. */
 int dwn_stem_backward_input(const dwn_stem_args* a, float* dx, int device, void* stream);
-size_t dwn_block_workspace_bytes(const dwn_block_args* a, int backward);
+size_t dwn_block_workspace_bytes(const dwn_block_args* a, int backward);     /* 0 for bad arguments */
 int dwn_block_forward(const dwn_block_args* a, int device, void* stream);
 int dwn_block_backward(const dwn_block_args* a, int device, void* stream);
 /* bit 0: dwn_block_forward writes y1; bit 1: it writes y3 (eval mode skips them where the stencil rebuilds y1 / the temporal
- * pass emits z3 directly: the caller may leave those pointers NULL) */
+ * pass emits z3 directly: the caller may leave those pointers NULL).  Null arguments or a geometry dwn_block_forward refuses: its
+ * negative code, with the error set (dwn_block_backward_route likewise) */
 int dwn_block_forward_writes(const dwn_block_args* a);
 /* bit 0: dwn_block_backward's conv_pw data gradient is dx itself — the shortcut branch's gradient is folded into the one-pass
  * kernel (dwn_pw_bwd_fused_supported; da0 is not written); bit 1: ... through the inverse nearest maps hinv / winv of a strided
@@ -494,11 +499,11 @@ int dwn_block_forward_writes(const dwn_block_args* a);
 int dwn_block_backward_route(const dwn_block_args* a);
 int dwn_pool_forward(const dwn_pool_args* a, int device, void* stream);
 int dwn_pool_backward(const dwn_pool_args* a, int device, void* stream);
-size_t dwn_cortex_workspace_bytes(const dwn_cortex_args* a, int backward);
+size_t dwn_cortex_workspace_bytes(const dwn_cortex_args* a, int backward);   /* 0 for bad arguments */
 int dwn_cortex_forward(const dwn_cortex_args* a, int device, void* stream);
 int dwn_cortex_backward(const dwn_cortex_args* a, int device, void* stream);
-size_t dwn_readout_workspace_bytes(const dwn_readout_args* a, int backward);
-size_t dwn_readout_wt_bytes(const dwn_readout_args* a);
+size_t dwn_readout_workspace_bytes(const dwn_readout_args* a, int backward); /* 0 for bad arguments */
+size_t dwn_readout_wt_bytes(const dwn_readout_args* a);                      /* 0 for bad arguments */
 int dwn_readout_forward(const dwn_readout_args* a, int device, void* stream);
 int dwn_readout_backward(const dwn_readout_args* a, int device, void* stream);
 
@@ -574,7 +579,7 @@ typedef struct dwn_pw_bwd_args {
     const int* res_hinv; const int* res_winv; int res_Hin, res_Win, res_Hout, res_Wout;
 } dwn_pw_bwd_args;
 int dwn_pw_bwd_fused_supported(int dtype, long long M, int E, int Cin);
-size_t dwn_pw_backward_workspace_bytes(int E, int Cin, int dtype);
+size_t dwn_pw_backward_workspace_bytes(int E, int Cin, int dtype);           /* 0 for bad arguments */
 int dwn_pw_backward(const dwn_pw_bwd_args* a, int dtype, int device, void* stream);
 
 /* ---- spat_covn_dw WITHOUT a materialised conv_pw output (dwiseneuro.py:90-102; bf16 storage, 3x3, stride 1 or 2,

@@ -78,6 +78,24 @@ struct ProfScope {
 #define HIP_TRY(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return dwn_set_error((int)e__, hipGetErrorString(e__)); } while (0)
 #define ENTER(device) do { g_err[0] = 0; HIP_TRY(hipSetDevice(device)); } while (0)
 
+// ---- every entry opens in one order (DESIGN.md "The entry contract"): ARGS and the null scalar arguments (-1), the mode refusals
+// (-7), the family's *_geometry (-2 / -4), the required pointers (-1), the workspace, ENTER.  No argument check needs a device,
+// nothing in front of ENTER calls the runtime, and a refused call has launched and written nothing.
+// the prologue: clear the error, reject a null argument struct
+#define ARGS(a, who) do { g_err[0] = 0; if (!(a)) return dwn_set_error(-1, who ": null arguments"); } while (0)
+// ... of an entry that takes its arguments one by one: clear the error, reject the null ones among the pointers it cannot do without
+#define NEEDS(ok, who_and_names) do { g_err[0] = 0; if (!(ok)) return dwn_set_error(-1, who_and_names); } while (0)
+// the workspace a->ws / a->ws_bytes against `need` bytes (what `getter` answers) and an alignment.  The code is -3 everywhere but
+// in the two *_backward entries of the gains (-2), and the alignment is the entry's own: both are part of the interface.  (The model's
+// composites keep their older answer: -6 "workspace too small".)
+#define WS_CHECK(a, code, who, need, getter, align) do { \
+    if ((a)->ws_bytes < (need) || ((size_t)(a)->ws & ((align) - 1))) \
+        return dwn_set_error(code, who ": workspace smaller than " getter " or not " #align "-byte aligned"); } while (0)
+// a *_ws_bytes entry: 0 and no error left behind when the arguments are null or their geometry is bad
+#define WS_BYTES_OR_0(a, geometry, bytes) do { if (!(a) || geometry(a) != 0) { g_err[0] = 0; return 0; } return (bytes); } while (0)
+// the largest value of a product that the code below holds in an `int`
+constexpr long long INT_LIMIT = 0x7fffffffLL;
+
 namespace {
 
 struct Carver {
@@ -325,13 +343,57 @@ ResGeom geom_of(const dwn_block_args& a) {
     return gm;
 }
 
-int check_block(const dwn_block_args& a) {
+// does the product of these positive factors stay an int?  (no overflow on the way: the running product is cut at INT_LIMIT)
+inline bool fits_int(std::initializer_list<long long> f) {
+    long long p = 1;
+    for (long long v : f) { if (v > INT_LIMIT) return false; p *= v; if (p > INT_LIMIT) return false; }
+    return true;
+}
+inline bool dtype_ok(int dtype) { return dtype == DWN_F32 || dtype == DWN_BF16; }
+inline bool bn_mode_ok(int training) { return training == DWN_BN_EVAL || training == DWN_BN_TRAIN || training == DWN_BN_FROZEN; }
+
+// the block's geometry: the two size entries, the two route entries, forward and backward
+int check_block(const dwn_block_args* ap) {
+    const dwn_block_args& a = *ap;
+    if (a.B <= 0 || a.T <= 0 || a.Hin <= 0 || a.Win <= 0 || a.Hout <= 0 || a.Wout <= 0 || a.Cin <= 0 || a.Cmid <= 0 || a.Cout <= 0 ||
+        a.stride <= 0 || a.se_r <= 0)
+        return dwn_set_error(-2, "block: B, T, Hin, Win, Hout, Wout, Cin, Cmid, Cout, stride, se_r must be positive");
     if (a.Cin % 8 || a.Cmid % 8 || a.Cout % 8) return dwn_set_error(-2, "block: channel counts must be multiples of 8");
     if (a.ks != 3 && a.ks != 5 && a.ks != 7) return dwn_set_error(-4, "block: spatial_kernel must be 3, 5 or 7 (the built set)");
     if (a.kt != 3 && a.kt != 5 && a.kt != 7 && a.kt != 9) return dwn_set_error(-4, "block: temporal_kernel must be 3, 5, 7 or 9 (the built set)");
     if (a.Hout != (a.Hin - 1) / a.stride + 1 || a.Wout != (a.Win - 1) / a.stride + 1)
         return dwn_set_error(-2, "block: Hout/Wout inconsistent with stride");
+    if (!dtype_ok(a.dtype)) return dwn_set_error(-2, "block: dtype must be DWN_F32 or DWN_BF16");
+    if (!bn_mode_ok(a.training)) return dwn_set_error(-2, "block: training must be DWN_BN_EVAL, DWN_BN_TRAIN or DWN_BN_FROZEN");
+    // the rows of the block's input are an int wherever a GEMM takes them — (int)Min, (int)Mout as GemmNN::M / GemmTN::M — and bound
+    // the other int products of the entries: planes and gm.BT (B * T), BlockPlan::S_out and rows_per_sample (T * Hout * Wout),
+    // DwTemporalFwd::HW (Hout * Wout); Hout <= Hin and Wout <= Win by the line above
+    if (!fits_int({a.B, a.T, a.Hin, a.Win})) return dwn_set_error(-2, "block: B * T * Hin * Win must stay below 2^31");
     return 0;
+}
+
+// the stem's geometry, from the fields its two argument structs share: the size entry, forward, backward and the two input-gradient
+// entries (`who` keeps each entry's own message prefix)
+int stem_geometry(const char* who, int dtype, int training, int B, int Cin, int C0, i64 S) {
+    char msg[128];
+    const char* bad = nullptr;
+    if (C0 <= 0 || C0 % 8 || Cin <= 0 || B <= 0 || S <= 0) bad = "C0 must be a positive multiple of 8; B, Cin, S positive";
+    else if (!dtype_ok(dtype)) bad = "dtype";
+    else if (!bn_mode_ok(training)) bad = "training must be DWN_BN_EVAL, DWN_BN_TRAIN or DWN_BN_FROZEN";
+    // the launchers (k_stem_out, k_stem_bwd_acc) refuse 2^31 rows and more: B * S, `M` in the entries
+    else if (!fits_int({B, S})) bad = "B * S must stay below 2^31";
+    if (!bad) return 0;
+    snprintf(msg, sizeof msg, "%s: %s", who, bad);
+    return dwn_set_error(-2, msg);
+}
+int stem_geometry(const dwn_stem_args* a) {
+    TRY(stem_geometry("stem", a->dtype, a->training, a->B, a->Cin, a->C0, a->S));
+    if (a->pe_t && (i64)a->T * a->H * a->W != a->S) return dwn_set_error(-2, "stem: T*H*W != S");
+    return 0;
+}
+size_t stem_ws_bytes(const dwn_stem_args* a) {
+    return ((size_t)DWN_NREP * stem_moment_count() * sizeof(double) + 256 +
+            (size_t)DWN_NREP * a->C0 * stem_acc_stride() * sizeof(double) + 1024);
 }
 
 }  // namespace
@@ -385,54 +447,64 @@ int dwn_profile_collect(int family, double* total_ms, long long* launches) {
     return 0;
 }
 
+// ---- the kernel families' thin entries: the null refusals and the entry's own checks here, every other refusal is the launcher's
 int dwn_gemm_nn(const dwn_gemm_nn_args* a, int dtype, int device, void* stream) {
+    ARGS(a, "gemm_nn");
     ENTER(device);
     return launch_gemm_nn(*a, dtype, (hipStream_t)stream);
 }
 int dwn_gemm_tn(const dwn_gemm_tn_args* a, int dtype, int device, void* stream) {
+    ARGS(a, "gemm_tn");
     ENTER(device);
     return launch_gemm_tn(*a, dtype, (hipStream_t)stream);
 }
 int dwn_dw_spatial_fwd(const dwn_dw_spatial_fwd_args* a, int dtype, int device, void* stream) {
+    ARGS(a, "dw_spatial_fwd");
     ENTER(device);
     return launch_dw_spatial_fwd(*a, dtype, (hipStream_t)stream);
 }
 int dwn_dw_spatial_bwd(const dwn_dw_spatial_bwd_args* a, int dtype, int device, void* stream) {
+    ARGS(a, "dw_spatial_bwd");
     ENTER(device);
     return launch_dw_spatial_bwd(*a, dtype, (hipStream_t)stream);
 }
-int dwn_dw_spatial_bwd_rc_supported(const dwn_dw_spatial_bwd_args* a, int dtype) { return dw_spatial_bwd_rc_supported(*a, dtype) ? 1 : 0; }
-int dwn_dw_spatial_fwd_rc_supported(const dwn_dw_spatial_fwd_args* a, int dtype) { return dw_spatial_fwd_rc_walk_supported(*a, dtype) ? 1 : 0; }
+// (the probes answer 0 / 1: null arguments are not supported)
+int dwn_dw_spatial_bwd_rc_supported(const dwn_dw_spatial_bwd_args* a, int dtype) { return a && dw_spatial_bwd_rc_supported(*a, dtype) ? 1 : 0; }
+int dwn_dw_spatial_fwd_rc_supported(const dwn_dw_spatial_fwd_args* a, int dtype) { return a && dw_spatial_fwd_rc_walk_supported(*a, dtype) ? 1 : 0; }
 int dwn_dw_temporal_fwd(const dwn_dw_temporal_fwd_args* a, int dtype, int device, void* stream) {
-    ENTER(device);
+    ARGS(a, "dw_temporal_fwd");
     // this entry's built set stays {3, 5}: the launcher behind it also serves the block path, where 7 and 9 go on to the wide kernels
     if (a->kt != 3 && a->kt != 5) return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
+    ENTER(device);
     return launch_dw_temporal_fwd(*a, dtype, (hipStream_t)stream);
 }
 int dwn_dw_temporal_bwd(const dwn_dw_temporal_bwd_args* a, int dtype, int device, void* stream) {
-    ENTER(device);
+    ARGS(a, "dw_temporal_bwd");
     if (a->kt != 3 && a->kt != 5) return dwn_set_error(-4, "dw_temporal: only temporal_kernel 3 or 5 is built");
+    ENTER(device);
     return launch_dw_temporal_bwd(*a, dtype, (hipStream_t)stream);
 }
 int dwn_dw_temporal_wide_fwd(const dwn_dw_temporal_fwd_args* a, int dtype, int device, void* stream) {
-    g_err[0] = 0;
-    if (int rc = dw_temporal_wide_check(a->kt, a->C, LD_PLAIN)) return rc;
+    ARGS(a, "dw_temporal_wide_fwd");
+    TRY(dw_temporal_wide_check(a->kt, a->C, LD_PLAIN));
     ENTER(device);
     return launch_dw_temporal_wide_fwd(*a, dtype, (hipStream_t)stream);
 }
 int dwn_dw_temporal_wide_bwd(const dwn_dw_temporal_bwd_args* a, int dtype, int device, void* stream) {
-    g_err[0] = 0;
-    if (int rc = dw_temporal_wide_check(a->kt, a->C, a->dy_kind)) return rc;
+    ARGS(a, "dw_temporal_wide_bwd");
+    TRY(dw_temporal_wide_check(a->kt, a->C, a->dy_kind));
     ENTER(device);
     return launch_dw_temporal_wide_bwd(*a, dtype, (hipStream_t)stream);
 }
 int dwn_bn_finalize(const double* stats, int stat_c, double count, const dwn_bn* bn, int C, int training,
                     float momentum, float eps, int device, void* stream) {
+    NEEDS(bn && (stats || !training), "bn_finalize: null pointer (bn; stats in training mode)");
     ENTER(device);
     return bn_finalize(stats, stat_c, count, *bn, C, training, momentum, eps, (hipStream_t)stream);
 }
 int dwn_bn_bwd_finalize(const double* stats, double count, const dwn_bn* bn, float* abc, int C, int device,
                         void* stream) {
+    NEEDS(stats && bn && abc, "bn_bwd_finalize: null pointer (stats, bn, abc)");
     ENTER(device);
     return k_bn_bwd_finalize(bwd_job(stats, count, *bn, abc, C, false), BnBwdJob{}, (hipStream_t)stream);
 }
@@ -444,11 +516,12 @@ size_t dwn_conv_pw_bn_stats_workspace_bytes(int Cin) {
 }
 int dwn_conv_pw_bn_stats(const void* a0, long long a0_ld, long long M, const float* w_pw, int E, int Cin, const dwn_bn* bn,
                          float momentum, float eps, double* sc_stats, void* ws, size_t ws_bytes, int dtype, int device, void* stream) {
+    NEEDS(bn, "conv_pw_bn_stats: null pointer (bn)");
+    if (Cin % 8 || E <= 0 || M <= 0 || M >= (1ll << 31)) return dwn_set_error(-2, "conv_pw_bn_stats: Cin % 8 == 0, 0 < M < 2^31");
+    if (!a0 || !w_pw || !bn->coef || !ws) return dwn_set_error(-1, "conv_pw_bn_stats: null pointer (a0, w_pw, bn.coef, ws)");
+    if (ws_bytes < dwn_conv_pw_bn_stats_workspace_bytes(Cin)) return dwn_set_error(-6, "conv_pw_bn_stats: workspace too small");
     ENTER(device);
     hipStream_t s = (hipStream_t)stream;
-    if (!a0 || !w_pw || !bn || !bn->coef || !ws) return dwn_set_error(-1, "conv_pw_bn_stats: null pointer");
-    if (Cin % 8 || E <= 0 || M <= 0 || M >= (1ll << 31)) return dwn_set_error(-2, "conv_pw_bn_stats: Cin % 8 == 0, 0 < M < 2^31");
-    if (ws_bytes < dwn_conv_pw_bn_stats_workspace_bytes(Cin)) return dwn_set_error(-6, "conv_pw_bn_stats: workspace too small");
     double* gram = reinterpret_cast<double*>(((size_t)ws + 255) & ~(size_t)255);
     const int nrep = gram_nrep(dtype, Cin);
     TRY(k_zero(gram, (size_t)nrep * (Cin + 8) * Cin * sizeof(double), s));
@@ -466,29 +539,30 @@ int dwn_conv_pw_bn_stats(const void* a0, long long a0_ld, long long M, const flo
 }
 int dwn_pack_weight(const float* src, void* dst, int groups, int R, int C, int transpose, int Rd, int Cd, int dtype,
                     int device, void* stream) {
+    NEEDS(src && dst, "pack_weight: null pointer (src, dst)");
     ENTER(device);
     return k_pack_weight(src, dst, groups, R, C, transpose, Rd, Cd, dtype, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------ stem
 size_t dwn_stem_workspace_bytes(const dwn_stem_args* a) {
-    return ((size_t)DWN_NREP * stem_moment_count() * sizeof(double) + 256 +
-            (size_t)DWN_NREP * a->C0 * stem_acc_stride() * sizeof(double) + 1024);
+    WS_BYTES_OR_0(a, stem_geometry, stem_ws_bytes(a));
 }
 // Conv3d(Cin -> C0, 1x1x1) + BatchNorm3d (dwiseneuro.py:306-309).  y0 = W0 x is linear in the Cin <= 8 input channels, so the
 // batch statistics come from the input moments (xmom) and y0 is never written: a->y0 is ignored (kept in the struct for
 // layout compatibility), a->xmom receives [8] sums + [8][8] second moments (doubles) that the backward reads.
 int dwn_stem_forward(const dwn_stem_args* a, int device, void* stream) {
+    ARGS(a, "stem_forward");
+    TRY(stem_geometry(a));
+    if (!a->x || !a->w || !a->bn.coef || !a->out || !a->ws) return dwn_set_error(-1, "stem_forward: null pointer (x, w, bn.coef, out, ws)");
+    if (a->training == DWN_BN_TRAIN && !a->xmom) return dwn_set_error(-1, "stem_forward: xmom buffer required in training mode");
+    if (a->ws_bytes < stem_ws_bytes(a)) return dwn_set_error(-6, "stem: workspace too small");
     ENTER(device);
     hipStream_t s = (hipStream_t)stream;
-    if (a->C0 % 8) return dwn_set_error(-2, "stem: C0 must be a multiple of 8");
-    if (a->pe_t && (i64)a->T * a->H * a->W != a->S) return dwn_set_error(-2, "stem: T*H*W != S");
     Carver c(a->ws, a->ws_bytes);
     double* mom = c.take<double>((size_t)DWN_NREP * stem_moment_count());
-    if (!c.ok()) return dwn_set_error(-6, "stem: workspace too small");
     const i64 M = (i64)a->B * a->S;
     if (a->training == DWN_BN_TRAIN) {
-        if (!a->xmom) return dwn_set_error(-1, "stem_forward: xmom buffer required in training mode");
         TRY(k_zero(mom, (size_t)DWN_NREP * stem_moment_count() * sizeof(double), s));
         TRY(k_stem_xmom(a->x, a->B, a->Cin, a->S, mom, s));
         TRY(k_stem_bn_finalize(mom, (double)M, a->w, a->bn.gamma, a->bn.beta, a->bn.running_mean, a->bn.running_var,
@@ -500,14 +574,18 @@ int dwn_stem_forward(const dwn_stem_args* a, int device, void* stream) {
                       a->dtype, s);
 }
 int dwn_stem_backward(const dwn_stem_args* a, int device, void* stream) {
+    ARGS(a, "stem_backward");
+    TRY(stem_geometry(a));
+    const bool frozen = a->training == DWN_BN_FROZEN;
+    if (!a->x || !a->w || !a->bn.coef || !a->dout || !a->dw || !a->ws)
+        return dwn_set_error(-1, "stem_backward: null pointer (x, w, bn.coef, dout, dw, ws)");
+    if (!frozen && !a->xmom) return dwn_set_error(-1, "stem_backward: xmom (saved by the forward) required");
+    if (a->ws_bytes < stem_ws_bytes(a)) return dwn_set_error(-6, "stem: workspace too small");
     ENTER(device);
     hipStream_t s = (hipStream_t)stream;
-    const bool frozen = a->training == DWN_BN_FROZEN;
-    if (!frozen && !a->xmom) return dwn_set_error(-1, "stem_backward: xmom (saved by the forward) required");
     Carver c(a->ws, a->ws_bytes);
     double* mom = c.take<double>((size_t)DWN_NREP * stem_moment_count());
     double* acc = c.take<double>((size_t)DWN_NREP * a->C0 * stem_acc_stride());
-    if (!c.ok()) return dwn_set_error(-6, "stem: workspace too small");
     const i64 M = (i64)a->B * a->S;
     if (frozen) {
         // frozen statistics: the same accumulation pass with zero input means (the workspace's moment slot, cleared with the
@@ -525,24 +603,21 @@ int dwn_stem_backward(const dwn_stem_args* a, int device, void* stream) {
 // argument for argument; Q, q0, x̄ (80 floats) go to the workspace's moment slot, which only the forward and the frozen backward
 // use — dwn_stem_workspace_bytes does not grow.
 int dwn_stem_backward_input(const dwn_stem_args* a, float* dx, int device, void* stream) {
-    g_err[0] = 0;                    // the argument checks need no device
-    if (!a || !dx) return dwn_set_error(-1, "stem_backward_input: null pointer (args, dx)");
+    NEEDS(a && dx, "stem_backward_input: null pointer (args, dx)");
     if (a->training != DWN_BN_TRAIN)
         return dwn_set_error(-7, "stem_backward_input: built for batch statistics (DWN_BN_TRAIN) only; the frozen-statistics input "
                                  "gradient is dwn_stem_backward + dwn_stem_input_grad");
-    if (!a->x || !a->w || !a->bn.coef || !a->dout || !a->dw || !a->xmom || !a->ws)
-        return dwn_set_error(-1, "stem_backward_input: null pointer (x, w, bn.coef, dout, dw, xmom, ws)");
-    if (a->C0 <= 0 || a->C0 % 8 || a->Cin <= 0 || a->B <= 0 || a->S <= 0)
-        return dwn_set_error(-2, "stem_backward_input: C0 must be a positive multiple of 8; B, Cin, S positive");
-    if (a->dtype != DWN_F32 && a->dtype != DWN_BF16) return dwn_set_error(-2, "stem_backward_input: dtype");
+    TRY(stem_geometry("stem_backward_input", a->dtype, a->training, a->B, a->Cin, a->C0, a->S));
     if (a->C0 > (a->dtype == DWN_BF16 ? 128 : 64) || a->Cin > 8)
         return dwn_set_error(-4, "stem_backward_input: more than 128 (bf16) / 64 (fp32) stem channels or 8 input channels not built");
+    if (!a->x || !a->w || !a->bn.coef || !a->dout || !a->dw || !a->xmom || !a->ws)
+        return dwn_set_error(-1, "stem_backward_input: null pointer (x, w, bn.coef, dout, dw, xmom, ws)");
+    if (a->ws_bytes < stem_ws_bytes(a)) return dwn_set_error(-6, "stem: workspace too small");
     ENTER(device);
     hipStream_t s = (hipStream_t)stream;
     Carver c(a->ws, a->ws_bytes);
     double* mom = c.take<double>((size_t)DWN_NREP * stem_moment_count());
     double* acc = c.take<double>((size_t)DWN_NREP * a->C0 * stem_acc_stride());
-    if (!c.ok()) return dwn_set_error(-6, "stem: workspace too small");
     float* qx = reinterpret_cast<float*>(mom);
     const i64 M = (i64)a->B * a->S;
     TRY(k_zero(acc, (size_t)DWN_NREP * a->C0 * stem_acc_stride() * sizeof(double), s));
@@ -554,35 +629,42 @@ int dwn_stem_backward_input(const dwn_stem_args* a, float* dx, int device, void*
 
 // dx of the stem with BatchNorm as a fixed affine map (dwn.h): one streaming pass over dout
 int dwn_stem_input_grad(const dwn_stem_input_grad_args* a, int device, void* stream) {
-    g_err[0] = 0;
-    if (!a || !a->w || !a->coef || !a->dout || !a->dx) return dwn_set_error(-1, "stem_input_grad: null pointer");
-    if (a->C0 <= 0 || a->C0 % 8 || a->Cin <= 0 || a->B <= 0 || a->S <= 0)
-        return dwn_set_error(-2, "stem_input_grad: C0 must be a positive multiple of 8; B, Cin, S positive");
-    if (a->dtype != DWN_F32 && a->dtype != DWN_BF16) return dwn_set_error(-2, "stem_input_grad: dtype");
+    ARGS(a, "stem_input_grad");
     if (a->training != DWN_BN_FROZEN)
         return dwn_set_error(-7, "stem_input_grad: this entry is the frozen-statistics (DWN_BN_FROZEN) input gradient; through batch "
                                  "statistics (DWN_BN_TRAIN) it is dwn_stem_backward_input");
+    TRY(stem_geometry("stem_input_grad", a->dtype, a->training, a->B, a->Cin, a->C0, a->S));
+    if (!a->w || !a->coef || !a->dout || !a->dx) return dwn_set_error(-1, "stem_input_grad: null pointer (w, coef, dout, dx)");
     ENTER(device);
     return k_stem_input_grad(a->dout, a->w, a->coef, a->B, a->Cin, a->S, a->C0, a->dx, a->dtype, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------ block
 size_t dwn_block_workspace_bytes(const dwn_block_args* a, int backward) {
-    return carve_block(*a, plan_block(*a), backward, nullptr, 0).bytes;
+    WS_BYTES_OR_0(a, check_block, carve_block(*a, plan_block(*a), backward, nullptr, 0).bytes);
+}
+
+// the pointers every route of a direction reads or writes (the SE biases, BatchNorm parameters and optional tables are the kernels' own)
+static bool block_common_pointers(const dwn_block_args& a) {
+    return a.y2 && a.y4 && a.z3 && a.w_pw && a.w_dws && a.w_dwt && a.w_pwl && a.se_wr && a.se_we && a.se_pmean && a.se_hidpre &&
+           a.se_gate && a.bn1.coef && a.bn2.coef && a.bn3.coef && a.bn4.coef && a.bnsc.coef && a.ws;
 }
 
 int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
-    ENTER(device);
+    ARGS(ap, "block_forward");
     const dwn_block_args& a = *ap;
-    hipStream_t s = (hipStream_t)stream;
-    TRY(check_block(a));
+    TRY(check_block(ap));
     const BlockPlan p = plan_block(a);
+    if (!block_common_pointers(a) || !a.x || !a.out || ((p.writes & 1) && !a.y1) || ((p.writes & 2) && !a.y3))
+        return dwn_set_error(-1, "block_forward: null pointer (x, out, y2, y4, z3, the four weights, se_wr, se_we, se_pmean, se_hidpre, "
+                                 "se_gate, the five bn coef, ws; y1 / y3 where dwn_block_forward_writes names them)");
+    if (!a.x_has_pe && !a.a0) return dwn_set_error(-2, "block_forward: a0 buffer required when x_has_pe == 0");
     BlockWs w = carve_block(a, p, 0, a.ws, a.ws_bytes);
     if (w.bytes > a.ws_bytes) return dwn_set_error(-6, "block_forward: workspace too small");
     const int dt = a.dtype, S_out = p.S_out;
     const i64 Min = p.Min, Mout = p.Mout;
+    PrepArgs pa;
     {   // ---- prep, one launch: zero the statistics arena, pack the four weights
-        PrepArgs pa;
         bool ok = pa.zero(w.zero_beg, ((size_t)(w.zero_end - w.zero_beg) + 15) & ~(size_t)15);
         ok = ok && pa.packw(a.w_pw, w.wpw, 1, a.Cmid, a.Cin, 0, a.Cmid, a.Cin);
         ok = ok && pa.packw(a.w_pwl, w.wpwl, 1, a.Cout, a.Cmid, 0, a.Cout, a.Cmid);
@@ -593,13 +675,14 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
             ok = ok && pa.bneval(a.bn4, a.Cout, a.eps) && pa.bneval(a.bnsc, a.Cout, a.eps);
         }
         if (!ok) return dwn_set_error(-2, "block_forward: workspace arena must be 16-byte aligned");
-        TRY(k_prep(pa, dt, s));
     }
+    ENTER(device);
+    hipStream_t s = (hipStream_t)stream;
+    TRY(k_prep(pa, dt, s));
     // ---- PositionalEncoding3d (dwiseneuro.py:184-192): normally already folded into x by the producer (stem /
     // previous block's residual kernel); stand-alone callers get it materialised here
     const void* a0 = a.x;
     if (!a.x_has_pe) {
-        if (!a.a0) return dwn_set_error(-2, "block_forward: a0 buffer required when x_has_pe == 0");
         TRY(k_ew_apply(ld_pe(a.x, a.Cin, a.pe_t, a.pe_h, a.pe_w, a.T, a.Hin, a.Win), LD_PE, a.a0, a.Cin, Min, a.Cin, dt, s));
         a0 = a.a0;
     }
@@ -717,12 +800,8 @@ int dwn_block_forward(const dwn_block_args* ap, int device, void* stream) {
 static int pw_backward(int dt, const void* dh1, const void* a0, const float* w_pw, const float* abc, int E, int Cin, i64 M,
                        void* bp, float* gacc, float* r3, float* tacc, void* da0, float* dw, const void* res,
                        const float* res_abc, int res_C, const ResGeom* rg, hipStream_t s, bool fold = true) {
-    const int res_n = res ? res_C / Cin : 0;
+    const int res_n = res ? res_C / Cin : 0;         // (dwn_pw_backward has checked the shortcut term; the block's plan grants it)
     const bool gathered = res && rg && rg->hinv;
-    if (res && (!res_abc || res_C % Cin || res_n < 1 || res_n > 2))
-        return dwn_set_error(-2, "pw_backward: the shortcut term needs res_abc and res_C in {Cin, 2 Cin}");
-    if (res && !pw_bwd_fused_supported(dt, M, E, Cin))
-        return dwn_set_error(-3, "pw_backward: the shortcut term is built into the one-pass kernel only (dwn_pw_bwd_fused_supported)");
     TRY(k_pw_bwd_prep(w_pw, abc, E, Cin, bp, gacc, r3, dt, (res && !gathered) ? res_abc : nullptr, res_C, s));
     if (pw_bwd_fused_supported(dt, M, E, Cin)) {
         // 64- and 128-channel blocks (0-3, 4-6): both products from ONE pass over dh1
@@ -747,22 +826,26 @@ static int pw_backward(int dt, const void* dh1, const void* a0, const float* w_p
 }
 
 int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
+    ARGS(ap, "block_backward");
     const dwn_block_args& a = *ap;
-    hipStream_t s = (hipStream_t)stream;
-    g_err[0] = 0;                    // the argument checks need no device: they answer the same on a host without one
-    TRY(check_block(a));
     if (a.training == DWN_BN_EVAL)
         return dwn_set_error(-7, "block_backward: only training-mode (batch-statistics) and frozen-statistics backward are built");
-    ENTER(device);
+    TRY(check_block(ap));
     const BlockPlan p = plan_block(a);
+    const bool y1_free = p.pw == PW_Y1_FREE;         // the forward of these arguments wrote no y1 (BlockPlan::writes)
+    if (!block_common_pointers(a) || !(a.x_has_pe ? a.x : a.a0) || !a.y3 || !a.dout || !a.dx || !a.buf_a || !a.buf_b || !a.dy4 ||
+        !a.dw_pw || !a.dw_dws || !a.dw_dwt || !a.dw_pwl || !a.dse_wr || !a.dse_br || !a.dse_we || !a.dse_be ||
+        (!y1_free && !a.y1) || (!p.dx_folded && !a.da0))
+        return dwn_set_error(-1, "block_backward: null pointer (the block input, y2, y3, y4, z3, dout, dx, buf_a, buf_b, dy4, the weights "
+                                 "and saved SE tensors, the dw_* and dse_* gradients, the five bn coef, ws; y1 where the forward wrote it; "
+                                 "da0 unless dwn_block_backward_route bit 0)");
     BlockWs w = carve_block(a, p, 1, a.ws, a.ws_bytes);
     if (w.bytes > a.ws_bytes) return dwn_set_error(-6, "block_backward: workspace too small");
     const int dt = a.dtype, S_out = p.S_out;
     const i64 Min = p.Min, Mout = p.Mout;
-    const bool y1_free = p.pw == PW_Y1_FREE;         // the forward of these arguments wrote no y1 (BlockPlan::writes)
     float* dg = reinterpret_cast<float*>(w.pooled);
+    PrepArgs pa;
     {   // ---- prep, one launch: zero the statistics arena, W2^T [Cmid][Cout], tap-major depth-wise weights, identity affine
-        PrepArgs pa;
         bool ok = pa.zero(w.zero_beg, ((size_t)(w.zero_end - w.zero_beg) + 15) & ~(size_t)15);
         ok = ok && pa.packw(a.w_pwl, w.wpwl, 1, a.Cout, a.Cmid, 1, a.Cmid, a.Cout);
         if (y1_free) ok = ok && pa.packw(a.w_pw, w.wpw, 1, a.Cmid, a.Cin, 0, a.Cmid, a.Cin);      // W1 as rounded: the stencil rebuilds y1 with it
@@ -779,8 +862,10 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
         ok = ok && pa.zero(w.gacc, pw_fold_floats(a.Cin) * sizeof(float));
         ok = ok && pa.zero(w.tacc, pw_wgrad_tacc_floats(a.Cmid, a.Cin) * sizeof(float));
         if (!ok) return dwn_set_error(-2, "block_backward: workspace arena and dw_* buffers must be 16-byte aligned");
-        TRY(k_prep(pa, dt, s));
     }
+    ENTER(device);
+    hipStream_t s = (hipStream_t)stream;
+    TRY(k_prep(pa, dt, s));
     // ---- residual + the two linear BNs (bn4 = conv_pwl.1.bn, bnsc = bn_sc.bn)
     LoadDesc xin = ld_plain(a.x_has_pe ? a.x : a.a0, a.Cin);     // block input including its positional encoding
     ResGeom gm = geom_of(a);
@@ -871,24 +956,40 @@ int dwn_block_backward(const dwn_block_args* ap, int device, void* stream) {
 
 // Which of the intermediates dwn_block_forward will write for these arguments: bit 0 = y1, bit 1 = y3 (BlockPlan::writes) — the
 // caller need not allocate what is not written (and may pass NULL for it).
+// Null arguments or a refused geometry: check_block's negative code, with the error set (both entries).
 int dwn_block_forward_writes(const dwn_block_args* ap) {
+    ARGS(ap, "block_forward_writes");
+    TRY(check_block(ap));
     return plan_block(*ap).writes;
 }
 // How dwn_block_backward forms dx for these arguments: bit 0 = BlockPlan::dx_folded, bit 1 = BlockPlan::sc_gathered
 int dwn_block_backward_route(const dwn_block_args* ap) {
+    ARGS(ap, "block_backward_route");
+    TRY(check_block(ap));
     const BlockPlan p = plan_block(*ap);
     return (p.dx_folded ? 1 : 0) | (p.sc_gathered ? 2 : 0);
 }
 
 // ------------------------------------------------------------------------------------------------ pool
+// (BT and the rows BT * HW are 64-bit in the launchers and their grids are capped: no int product to bound)
+static int pool_geometry(const dwn_pool_args* a) {
+    if (a->C % 8) return dwn_set_error(-2, "pool: C must be a multiple of 8");      // (the kernels move whole 16-byte channel vectors)
+    if (a->BT <= 0 || a->HW <= 0 || a->C <= 0) return dwn_set_error(-2, "pool: BT, HW, C must be positive");
+    if (!dtype_ok(a->dtype)) return dwn_set_error(-2, "pool: dtype must be DWN_F32 or DWN_BF16");
+    return 0;
+}
 int dwn_pool_forward(const dwn_pool_args* a, int device, void* stream) {
+    ARGS(a, "pool_forward");
+    TRY(pool_geometry(a));
+    if (!a->x || !a->out) return dwn_set_error(-1, "pool_forward: null pointer (x, out)");
     ENTER(device);
-    if (a->C % 8) return dwn_set_error(-2, "pool: C must be a multiple of 8");
     return k_pool_fwd(a->x, a->out, a->BT, a->HW, a->C, a->dtype, (hipStream_t)stream);
 }
 int dwn_pool_backward(const dwn_pool_args* a, int device, void* stream) {
+    ARGS(a, "pool_backward");
+    TRY(pool_geometry(a));
+    if (!a->dout || !a->dx) return dwn_set_error(-1, "pool_backward: null pointer (dout, dx)");
     ENTER(device);
-    if (a->C % 8) return dwn_set_error(-2, "pool: C must be a multiple of 8");      // (the kernel stores whole 16-byte channel vectors)
     return k_pool_bwd(a->dout, a->dx, a->BT, a->HW, a->C, a->dtype, (hipStream_t)stream);
 }
 
@@ -916,29 +1017,45 @@ CortexWs carve_cortex(const dwn_cortex_args& a, int backward, void* base, size_t
     if (base) { w.zb = (char*)base + z0; w.ze = (char*)base + z1; }
     return w;
 }
+// the size entry, forward and backward
+int cortex_geometry(const dwn_cortex_args* a) {
+    if (a->B <= 0 || a->T <= 0 || a->Cin <= 0 || a->C <= 0 || a->groups <= 0) return dwn_set_error(-2, "cortex: B, T, Cin, C, groups must be positive");
+    if (a->Cin % (8ll * a->groups) || a->C % (8ll * a->groups)) return dwn_set_error(-2, "cortex: channels per group must be multiples of 8");
+    if (!dtype_ok(a->dtype)) return dwn_set_error(-2, "cortex: dtype must be DWN_F32 or DWN_BF16");
+    if (!bn_mode_ok(a->training)) return dwn_set_error(-2, "cortex: training must be DWN_BN_EVAL, DWN_BN_TRAIN or DWN_BN_FROZEN");
+    // `M` = B * T rows is an int in both entries and in every launcher behind them
+    if (!fits_int({a->B, a->T})) return dwn_set_error(-2, "cortex: B * T must stay below 2^31");
+    // `grid` of k_cortex_residual_fwd / _bwd_dy / _bwd_dx: one workgroup per 256 of the M * C (M * Cin) elements, a grid dimension
+    const i64 n = (i64)a->B * a->T * (a->C > a->Cin ? a->C : a->Cin);
+    if ((n + 255) / 256 > INT_LIMIT) return dwn_set_error(-2, "cortex: B * T * max(C, Cin) / 256 workgroups must stay below 2^31");
+    return 0;
+}
 }  // namespace
 
 size_t dwn_cortex_workspace_bytes(const dwn_cortex_args* a, int backward) {
-    return carve_cortex(*a, backward, nullptr, 0).bytes;
+    WS_BYTES_OR_0(a, cortex_geometry, carve_cortex(*a, backward, nullptr, 0).bytes);
 }
 int dwn_cortex_forward(const dwn_cortex_args* ap, int device, void* stream) {
-    ENTER(device);
+    ARGS(ap, "cortex_forward");
     const dwn_cortex_args& a = *ap;
-    hipStream_t s = (hipStream_t)stream;
-    if (a.Cin % (8 * a.groups) || a.C % (8 * a.groups)) return dwn_set_error(-2, "cortex: channels per group must be multiples of 8");
+    TRY(cortex_geometry(ap));
+    if (!a.x || !a.out || !a.y || !a.w || !a.bn.coef || !a.bnsc.coef || !a.ws)
+        return dwn_set_error(-1, "cortex_forward: null pointer (x, out, y, w, bn.coef, bnsc.coef, ws)");
     CortexWs w = carve_cortex(a, 0, a.ws, a.ws_bytes);
     if (w.bytes > a.ws_bytes) return dwn_set_error(-6, "cortex_forward: workspace too small");
     // tr: the training path's products (DWN_BN_TRAIN / _FROZEN); bs: batch statistics.  Frozen: coefficients in the prep launch
     const int M = a.B * a.T, Kg = a.Cin / a.groups, Ng = a.C / a.groups, dt = a.dtype, tr = a.training != DWN_BN_EVAL;
     const bool bs = a.training == DWN_BN_TRAIN;
+    PrepArgs pa;
     {
-        PrepArgs pa;
         bool ok = pa.zero(w.zb, ((size_t)(w.ze - w.zb) + 15) & ~(size_t)15);
         ok = ok && pa.packw(a.w, w.wp, 1, a.C, Kg, 0, a.C, Kg);
         if (tr && !bs) ok = ok && pa.bneval(a.bn, a.C, a.eps) && pa.bneval(a.bnsc, a.C, a.eps);
         if (!ok) return dwn_set_error(-2, "cortex_forward: workspace arena must be 16-byte aligned");
-        TRY(k_prep(pa, dt, s));
     }
+    ENTER(device);
+    hipStream_t s = (hipStream_t)stream;
+    TRY(k_prep(pa, dt, s));
     GemmNN g = nn_base(ld_plain(a.x, a.Cin), LD_PLAIN, w.wp, Kg, a.y, a.C, M, Ng, Kg, a.groups);
     g.f32_split = f32_split_of(a.f32_products, !tr);
     // (no statistics epilogue: the batch statistics are summed in double by k_cortex_stats below, frozen statistics need none)
@@ -955,25 +1072,28 @@ int dwn_cortex_forward(const dwn_cortex_args* ap, int device, void* stream) {
                                  dt, s);
 }
 int dwn_cortex_backward(const dwn_cortex_args* ap, int device, void* stream) {
+    ARGS(ap, "cortex_backward");
     const dwn_cortex_args& a = *ap;
-    hipStream_t s = (hipStream_t)stream;
-    g_err[0] = 0;
     if (a.training == DWN_BN_EVAL) return dwn_set_error(-7, "cortex_backward: only training-mode and frozen-statistics backward are built");
-    ENTER(device);
+    TRY(cortex_geometry(ap));
+    if (!a.x || !a.y || !a.w || !a.dout || !a.dx || !a.dw || !a.bn.coef || !a.bnsc.coef || !a.ws)
+        return dwn_set_error(-1, "cortex_backward: null pointer (x, y, w, dout, dx, dw, bn.coef, bnsc.coef, ws)");
     const bool frozen = a.training == DWN_BN_FROZEN;
     CortexWs w = carve_cortex(a, 1, a.ws, a.ws_bytes);
     if (w.bytes > a.ws_bytes) return dwn_set_error(-6, "cortex_backward: workspace too small");
     const int M = a.B * a.T, Kg = a.Cin / a.groups, Ng = a.C / a.groups, dt = a.dtype;
+    PrepArgs pa;
     {
-        PrepArgs pa;
         bool ok = pa.zero(w.zb, ((size_t)(w.ze - w.zb) + 15) & ~(size_t)15);
         ok = ok && pa.packw(a.w, w.wp, a.groups, Ng, Kg, 1, Kg, Ng);       // per group W^T [Kg][Ng]
         // dw is accumulated with atomics by the weight-gradient product: cleared here, in the same launch (as dwn_block_backward
         // clears its dw_*), not by the caller
         ok = ok && pa.zero(a.dw, (size_t)a.C * Kg * sizeof(float));
         if (!ok) return dwn_set_error(-2, "cortex_backward: workspace arena and dw must be 16-byte aligned (C * Cin / groups a multiple of 4)");
-        TRY(k_prep(pa, dt, s));
     }
+    ENTER(device);
+    hipStream_t s = (hipStream_t)stream;
+    TRY(k_prep(pa, dt, s));
     TRY(k_cortex_bwd_reduce(a.y, a.x, a.dout, a.dout_mask, a.dout_mask_ld, a.bn.coef, a.bnsc.coef, a.drop_scale, M, a.T,
                             a.Cin, a.C, a.groups, w.st, w.stsc, dt, s));
     TRY(k_bn_bwd_finalize(bwd_job(w.st, (double)M, a.bn, w.abc, a.C, frozen), bwd_job(w.stsc, (double)M, a.bnsc, w.abcsc, a.C, frozen), s));
@@ -1010,22 +1130,37 @@ ReadoutWs carve_readout(const dwn_readout_args& a, int backward, void* base, siz
     w.bytes = c.off + 256;
     return w;
 }
+// the two size entries, forward and backward
+int readout_geometry(const dwn_readout_args* a) {
+    if (a->B <= 0 || a->T <= 0 || a->Cin <= 0 || a->groups <= 0 || a->n_out <= 0) return dwn_set_error(-2, "readout: B, T, Cin, groups, n_out must be positive");
+    if (a->Cin % (8ll * a->groups)) return dwn_set_error(-2, "readout: in-channels per group must be a multiple of 8");
+    if (!dtype_ok(a->dtype)) return dwn_set_error(-2, "readout: dtype must be DWN_F32 or DWN_BF16");
+    // `M` = B * T rows is an int in both entries and in the GEMMs behind them
+    if (!fits_int({a->B, a->T})) return dwn_set_error(-2, "readout: B * T must stay below 2^31");
+    // ReadoutWs::Npad, Rg, Rp and the `groups * Rp + 63` of k_readout_dbeta_parts are ints: the last one is the largest
+    const i64 rg = ((i64)a->n_out + a->groups - 1) / a->groups, rp = (rg + 63) / 64 * 64;
+    if (a->groups * rp + 63 > INT_LIMIT) return dwn_set_error(-2, "readout: groups * (neurons per group, padded to 64) must stay below 2^31 - 63");
+    // `a.groups * w.Rg * Kg`, the weight gradient's element count (k_fill_f32's n), is an int
+    if (a->groups * rg * (a->Cin / a->groups) > INT_LIMIT) return dwn_set_error(-2, "readout: the padded weight [Npad][Cin / groups] must stay below 2^31 elements");
+    return 0;
+}
 }  // namespace
 
 size_t dwn_readout_workspace_bytes(const dwn_readout_args* a, int backward) {
-    return carve_readout(*a, backward, nullptr, 0).bytes;
+    WS_BYTES_OR_0(a, readout_geometry, carve_readout(*a, backward, nullptr, 0).bytes);
 }
 size_t dwn_readout_wt_bytes(const dwn_readout_args* a) {
-    ReadoutWs w = carve_readout(*a, 0, nullptr, 0);
-    return (size_t)a->groups * (a->Cin / a->groups) * w.ldt * tsize(a->dtype);
+    WS_BYTES_OR_0(a, readout_geometry, (size_t)a->Cin * carve_readout(*a, 0, nullptr, 0).ldt * tsize(a->dtype));
 }
 int dwn_readout_forward(const dwn_readout_args* ap, int device, void* stream) {
-    ENTER(device);
+    ARGS(ap, "readout_forward");
     const dwn_readout_args& a = *ap;
-    hipStream_t s = (hipStream_t)stream;
-    if (a.Cin % (8 * a.groups)) return dwn_set_error(-2, "readout: in-channels per group must be a multiple of 8");
+    TRY(readout_geometry(ap));
+    if (!a.x || !a.w || !a.out || !a.ws) return dwn_set_error(-1, "readout_forward: null pointer (x, w, out, ws)");
     ReadoutWs w = carve_readout(a, 0, a.ws, a.ws_bytes);
     if (w.bytes > a.ws_bytes) return dwn_set_error(-6, "readout_forward: workspace too small");
+    ENTER(device);
+    hipStream_t s = (hipStream_t)stream;
     const int M = a.B * a.T, Kg = a.Cin / a.groups, dt = a.dtype;
     TRY(k_pack_weight_dual(a.w, w.wp, a.wt, a.groups, w.Rg, Kg, w.Rp, w.ldp, w.ldt, dt, s));   // both operand layouts, one read of the weight
     LoadDesc x = ld_plain(a.x, a.Cin);
@@ -1045,13 +1180,17 @@ int dwn_readout_forward(const dwn_readout_args* ap, int device, void* stream) {
     return 0;
 }
 int dwn_readout_backward(const dwn_readout_args* ap, int device, void* stream) {
-    if (ap && (ap->beta_dev != nullptr) != (ap->dbeta != nullptr))       // (answered before the device is entered)
-        return dwn_set_error(-2, "readout_backward: beta_dev and dbeta come together (both null: the fixed softplus_beta)");
-    ENTER(device);
+    ARGS(ap, "readout_backward");
     const dwn_readout_args& a = *ap;
-    hipStream_t s = (hipStream_t)stream;
+    if ((a.beta_dev != nullptr) != (a.dbeta != nullptr))
+        return dwn_set_error(-2, "readout_backward: beta_dev and dbeta come together (both null: the fixed softplus_beta)");
+    TRY(readout_geometry(ap));
+    if (!a.x || !(a.wt || a.w) || !a.out || !a.dout || !a.dx || !a.dw || !a.ws)
+        return dwn_set_error(-1, "readout_backward: null pointer (x, w or wt, out, dout, dx, dw, ws)");
     ReadoutWs w = carve_readout(a, 1, a.ws, a.ws_bytes);
     if (w.bytes > a.ws_bytes) return dwn_set_error(-6, "readout_backward: workspace too small");
+    ENTER(device);
+    hipStream_t s = (hipStream_t)stream;
     const int M = a.B * a.T, Kg = a.Cin / a.groups, dt = a.dtype;
     const void* wt = a.wt;                       // per group W^T [Kg][Rp], zero padded: kept from the forward, or packed now
     if (!wt) { TRY(k_pack_weight_dual(a.w, nullptr, w.wp, a.groups, w.Rg, Kg, w.Rp, w.ldp, w.ldt, dt, s)); wt = w.wp; }
@@ -1086,24 +1225,28 @@ int dwn_readout_backward(const dwn_readout_args* ap, int device, void* stream) {
 // ------------------------------------------------------------------------------------------------ loss / optimizer
 int dwn_poisson_loss_forward(const float* pred, const float* target, const float* w, long long per_sample,
                              long long total, float eps, double* loss_acc, int device, void* stream) {
+    NEEDS(pred && target && w && loss_acc, "poisson_loss_forward: null pointer (pred, target, w, loss_acc)");
     ENTER(device);
     return k_poisson_fwd(pred, target, w, per_sample, total, eps, loss_acc, (hipStream_t)stream);
 }
 int dwn_poisson_loss_backward(const float* pred, const float* target, const float* w, const float* gscale,
                               long long per_sample, long long total, float eps, float* dpred, int device,
                               void* stream) {
+    NEEDS(pred && target && w && dpred, "poisson_loss_backward: null pointer (pred, target, w, dpred)");      // (gscale is optional)
     ENTER(device);
     return k_poisson_bwd(pred, target, w, gscale, per_sample, total, eps, dpred, (hipStream_t)stream);
 }
 int dwn_f64_to_f32(const double* src, float* dst, int n, int device, void* stream) {
+    NEEDS(src && dst, "f64_to_f32: null pointer (src, dst)");
     ENTER(device);
     return k_f64_to_f32(src, dst, n, (hipStream_t)stream);
 }
 int dwn_adamw_ema_multi(const dwn_tensor_entry* list, int ntensors, int max_blocks, double lr, double beta1,
                         double beta2, double eps, double weight_decay, long long step, double ema_decay,
                         double grad_scale, int device, void* stream) {
-    ENTER(device);
+    NEEDS(list || ntensors <= 0, "adamw: null table");
     if (step < 1) return dwn_set_error(-2, "adamw: step must be >= 1");
+    ENTER(device);
     const double bc1 = 1.0 - pow(beta1, (double)step);
     const double bc2 = 1.0 - pow(beta2, (double)step);
     return k_adamw_ema(list, ntensors, max_blocks, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2,
@@ -1112,6 +1255,7 @@ int dwn_adamw_ema_multi(const dwn_tensor_entry* list, int ntensors, int max_bloc
 }
 int dwn_ema_lerp_multi(const dwn_tensor_entry* list, int ntensors, int max_blocks, double decay, int device,
                        void* stream) {
+    NEEDS(list || ntensors <= 0, "ema_lerp: null table");
     ENTER(device);
     return k_ema_lerp(list, ntensors, max_blocks, (float)decay, (float)(1.0 - decay), (hipStream_t)stream);
 }
@@ -1162,16 +1306,25 @@ int dwn_adamw_ema_multi_guarded(const dwn_guarded_entry* list, int ntensors, int
 int dwn_pw_bwd_fused_supported(int dtype, long long M, int E, int Cin) {
     return pw_bwd_fused_supported(dtype, M, E, Cin) ? 1 : 0;
 }
-size_t dwn_pw_backward_workspace_bytes(int E, int Cin, int dtype) {
-    return (size_t)Cin * (E + Cin) * tsize(dtype) + 256 + (pw_fold_floats(Cin) + pw_wgrad_tacc_floats(E, Cin)) * sizeof(float) + 256;
+static size_t pw_ws_bytes(int E, int Cin, int dtype) {
+    return (size_t)Cin * ((size_t)E + Cin) * tsize(dtype) + 256 + (pw_fold_floats(Cin) + pw_wgrad_tacc_floats(E, Cin)) * sizeof(float) + 256;
+}
+size_t dwn_pw_backward_workspace_bytes(int E, int Cin, int dtype) {      // 0 for widths or a dtype dwn_pw_backward refuses
+    return E > 0 && Cin > 0 && E % 8 == 0 && Cin % 8 == 0 && dtype_ok(dtype) ? pw_ws_bytes(E, Cin, dtype) : 0;
 }
 int dwn_pw_backward(const dwn_pw_bwd_args* a, int dtype, int device, void* stream) {
-    ENTER(device);
-    if (!a || !a->dh1 || !a->a0 || !a->w_pw || !a->abc || !a->da0 || !a->dw || !a->ws)
-        return dwn_set_error(-1, "pw_backward: null pointer");
+    ARGS(a, "pw_backward");
     if (a->E <= 0 || a->Cin <= 0 || a->E % 8 || a->Cin % 8 || a->M <= 0 || a->M > 0x7fffffffLL)
         return dwn_set_error(-2, "pw_backward: E and Cin must be positive multiples of 8, 0 < M < 2^31");
-    if (a->ws_bytes < dwn_pw_backward_workspace_bytes(a->E, a->Cin, dtype)) return dwn_set_error(-6, "pw_backward: workspace too small");
+    if (!dtype_ok(dtype)) return dwn_set_error(-2, "pw_backward: dtype must be DWN_F32 or DWN_BF16");
+    if (a->res && (!a->res_abc || a->res_C % a->Cin || a->res_C / a->Cin < 1 || a->res_C / a->Cin > 2))
+        return dwn_set_error(-2, "pw_backward: the shortcut term needs res_abc and res_C in {Cin, 2 Cin}");
+    if (a->res && !pw_bwd_fused_supported(dtype, a->M, a->E, a->Cin))
+        return dwn_set_error(-3, "pw_backward: the shortcut term is built into the one-pass kernel only (dwn_pw_bwd_fused_supported)");
+    if (!a->dh1 || !a->a0 || !a->w_pw || !a->abc || !a->da0 || !a->dw || !a->ws)
+        return dwn_set_error(-1, "pw_backward: null pointer (dh1, a0, w_pw, abc, da0, dw, ws)");
+    if (a->ws_bytes < pw_ws_bytes(a->E, a->Cin, dtype)) return dwn_set_error(-6, "pw_backward: workspace too small");
+    ENTER(device);
     hipStream_t s = (hipStream_t)stream;
     Carver c(a->ws, a->ws_bytes);
     void* bp = c.take<char>((size_t)a->Cin * (a->E + a->Cin) * tsize(dtype));
@@ -1188,34 +1341,24 @@ int dwn_pw_backward(const dwn_pw_bwd_args* a, int dtype, int device, void* strea
 
 int dwn_assemble_inputs(const dwn_clip_desc* descs, int B, int T, int H0, int W0, int H, int W, float pad_fill,
                         float* x, int device, void* stream) {
-    ENTER(device);
-    if (!descs || !x) return dwn_set_error(-1, "assemble_inputs: null pointer");
+    NEEDS(descs && x, "assemble_inputs: null pointer (descs, x)");
     if (B <= 0 || T <= 0 || H0 <= 0 || W0 <= 0) return dwn_set_error(-2, "assemble_inputs: B, T, H0, W0 must be positive");
     if (H < H0 || W < W0) return dwn_set_error(-2, "assemble_inputs: output frame smaller than the video");
+    ENTER(device);
     return k_assemble_inputs(descs, B, T, H0, W0, H, W, pad_fill, x, (hipStream_t)stream);
 }
 
 int dwn_assemble_targets(const dwn_clip_desc* descs, int B, int T, float* const* targets, const int* n_neurons,
                          int n_mice, int max_neurons, float* mice_weights, int device, void* stream) {
-    ENTER(device);
-    if (!descs || !targets || !n_neurons || !mice_weights) return dwn_set_error(-1, "assemble_targets: null pointer");
+    NEEDS(descs && targets && n_neurons && mice_weights, "assemble_targets: null pointer (descs, targets, n_neurons, mice_weights)");
     if (B <= 0 || T <= 0 || n_mice <= 0 || max_neurons <= 0)
         return dwn_set_error(-2, "assemble_targets: B, T, n_mice, max_neurons must be positive");
     if (B > 65535 || n_mice > 65535) return dwn_set_error(-2, "assemble_targets: B and n_mice are grid dimensions (<= 65535)");
+    ENTER(device);
     return k_assemble_targets(descs, B, T, targets, n_neurons, n_mice, max_neurons, mice_weights, (hipStream_t)stream);
 }
 
-// ---- the analysis entries below share three openings and one video-plane check; no argument check needs a device
-// the prologue: clear the error, reject a null argument struct
-#define ARGS(a, who) do { g_err[0] = 0; if (!(a)) return dwn_set_error(-1, who ": null arguments"); } while (0)
-// the workspace a->ws / a->ws_bytes against `need` bytes (what `getter` answers) and an alignment.  The code is -3 everywhere but
-// in the two *_backward entries of the gains (-2), and the alignment is the entry's own: both are part of the interface.
-#define WS_CHECK(a, code, who, need, getter, align) do { \
-    if ((a)->ws_bytes < (need) || ((size_t)(a)->ws & ((align) - 1))) \
-        return dwn_set_error(code, who ": workspace smaller than " getter " or not " #align "-byte aligned"); } while (0)
-// a *_ws_bytes entry: 0 and no error left behind when the arguments are null or their geometry is bad
-#define WS_BYTES_OR_0(a, geometry, bytes) do { if (!(a) || geometry(a) != 0) { g_err[0] = 0; return 0; } return (bytes); } while (0)
-
+// ---- the analysis entries below share one video-plane check
 // One plane of a [B][Cin][T][H][W] video, the channels [c, c + nc) and a window in it.  `parts` picks what is checked, always in
 // this order: the plane (sizes, channels, counts), the window, the cell, the per-clip element bounds of the MEI entries.
 enum { PL_PLANE = 1, PL_WINDOW = 2, PL_EMPTY_OK = 4, PL_CELL = 8, PL_CLIP = 16 };      // PL_EMPTY_OK: wh == ww == 0 at 0, 0 is the whole plane

@@ -343,6 +343,7 @@ class BlockFn(torch.autograd.Function):
         # y1 is not written where the stencils rebuild it (eval; bf16 training where both directions are built: the backward then
         # gets no y1 either), y3 not where the eval-mode temporal pass emits z3 directly
         writes = L.lib.dwn_block_forward_writes(C.byref(a))
+        L.check(min(writes, 0), "dwn_block_forward_writes")      # a refused geometry answers its negative code, not a write set
         y1 = torch.empty(B, T, Hin, Win, Cmid, dtype=dtype, device=dev) if writes & 1 else None
         y3 = torch.empty_like(y2) if writes & 2 else None
         a.y1 = _ptr(y1); a.y2 = y2.data_ptr(); a.y3 = _ptr(y3); a.y4 = y4.data_ptr()

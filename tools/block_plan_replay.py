@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Host answers of the block composite, one line per argument set (development tool; no device needed).
+"""Host answers of the model's composites, one line per argument set (development tool; no device needed).
 
 Replays the grid of tests/test_host_block_plan.py plus ragged and refused arguments and prints, for each, the forward and
-backward dwn_block_workspace_bytes, dwn_block_forward_writes and the (rc, message) of dwn_block_backward's device-free checks.
+backward dwn_block_workspace_bytes, dwn_block_forward_writes and the (rc, message) of dwn_block_backward's device-free checks;
+then the size entries of the stem, the cortex, the readout and conv_pw's backward over the same block shapes, the benchmarked
+model's and the model tests' cortex and readout widths and the ten-readout configuration (lines tagged `size`).
 Run once per library (DWN_LIB_PATH, DWN_DETERMINISTIC) and `diff` the outputs: a host-only change of csrc/dwn_api.hip leaves no
-differing line.
+differing line among the `grid` and `size` lines (valid arguments); the `ragged` lines also show what a refused geometry answers.
 
 usage: block_plan_replay.py > answers.txt
 """
@@ -14,7 +16,9 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sensorium_amd._lib as L
-from tests.test_host_block_plan import answers, block_args, grid
+import bench
+from tests.test_gpu_block import CASES
+from tests.test_host_block_plan import answers, bench_cases, block_args, grid
 
 
 def backward_check(a):
@@ -28,6 +32,39 @@ def backward_check(a):
 def line(tag, a):
     fields = "dtype training B T Hin Win Hout Wout Cin Cmid Cout stride ks kt se_r y1_mode pwl_bwd".split()
     return f"{tag} {' '.join(str(getattr(a, f)) for f in fields)} -> {answers(L, a)} {backward_check(a)}"
+
+
+def sizes():
+    """the stem, cortex, readout and conv_pw-backward size entries; returns the number of lines"""
+    lib, n = L.lib, 0
+    dtypes, modes = (L.DWN_F32, L.DWN_BF16), (L.BN_EVAL, L.BN_TRAIN, L.BN_FROZEN)
+    for cin, _, _, exp, _, B, T, H, W in CASES + bench_cases():
+        for dtype in dtypes:
+            for mode in modes:      # the stem in front of a first block of this shape
+                s = L.StemArgs(); s.dtype = dtype; s.training = mode; s.B = B; s.Cin = 5; s.C0 = cin; s.S = T * H * W
+                print(f"size stem {dtype} {mode} {B} 5 {cin} {s.S} -> {lib.dwn_stem_workspace_bytes(C.byref(s))}")
+            print(f"size pw_backward {dtype} {cin * exp} {cin} -> {lib.dwn_pw_backward_workspace_bytes(cin * exp, cin, dtype)}")
+            n += len(modes) + 1
+    # (last core width, cortex widths): the model tests' tiny configuration and the benchmarked one
+    tiny, full = (16, (32, 64)), (bench.CORE_FEATURES[-1], bench.model_params()["nn_module"][1]["cortex_features"])
+    for (first, widths), shapes, readouts in ((tiny, ((2, 6), (3, 5)), (7, 10)), (full, ((32, 32), (2, 8)), bench.NUM_NEURONS_ALL)):
+        for B, T in shapes:
+            for dtype in dtypes:
+                for cin, cout in zip((first,) + tuple(widths), widths):
+                    for mode in modes:
+                        c = L.CortexArgs(); c.dtype = dtype; c.training = mode; c.B = B; c.T = T; c.Cin = cin; c.C = cout; c.groups = 2
+                        print(f"size cortex {dtype} {mode} {B} {T} {cin} {cout} 2 -> "
+                              f"{lib.dwn_cortex_workspace_bytes(C.byref(c), 0)} {lib.dwn_cortex_workspace_bytes(C.byref(c), 1)}")
+                        n += 1
+                for n_out in readouts:
+                    for drop, wt, beta in ((0, 0, 0), (256, 0, 0), (0, 256, 0), (256, 256, 256)):      # the pointers that choose slices
+                        r = L.ReadoutArgs(); r.dtype = dtype; r.B = B; r.T = T; r.Cin = widths[-1]; r.groups = 2; r.n_out = n_out
+                        r.drop_mask = drop or None; r.wt = wt or None; r.beta_dev = beta or None
+                        print(f"size readout {dtype} {B} {T} {widths[-1]} 2 {n_out} {drop} {wt} {beta} -> "
+                              f"{lib.dwn_readout_workspace_bytes(C.byref(r), 0)} {lib.dwn_readout_workspace_bytes(C.byref(r), 1)} "
+                              f"{lib.dwn_readout_wt_bytes(C.byref(r))}")
+                        n += 1
+    return n
 
 
 def main():
@@ -50,6 +87,7 @@ def main():
             for a in ragged:
                 print(line("ragged", a))
                 n += 1
+    n += sizes()
     print(f"tuples {n}")
 
 
